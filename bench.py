@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py — multimodal forward samples/s (224x224 image + 50 tokens) @ ViT-L/14 + Perceiver + 24L/2048d.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`); every other
+figure of the line (`roofline`, `parity`, `cpu_baseline`, the other precision modes, `c3`, `batch1`, `decode`,
+`training_step`, `kernel_breakdown`) is measured only with `--full` and is null otherwise.  `--dump-outputs DIR` writes
+what the last timed step returned (a fixed sample of the logits, float32 .npy) so two builds can be compared.
 
 One process per GPU (RCCL over xGMI for N > 1).  A "step" is one pass of the hot path
 (`Kosmos.forward`, /root/reference/kosmosx/model.py:208-253) over one per-GPU shard of synthetic
@@ -78,7 +83,35 @@ def parse():
     ap.add_argument("--streams", type=int, default=1, help="micro-batch the shard over S HIP streams (overlaps kernel tails)")
     ap.add_argument("--gemm-tile", type=int, default=0, help="kernel-variant override (kx_set_tuning key 1), A/B only")
     ap.add_argument("--tune", default="", help="A/B only: comma list of kx_set_tuning key=value pairs, e.g. 4=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the instrumented roofline pass, the other precision "
+                         "modes, parity and the CPU baseline, and the c3 / batch-1 / decode / training legs (off: the line "
+                         "carries the headline only; --no-extra, --no-cpu-baseline and --prof-steps trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to DIR/<name>.npy (float32): the logits of "
+                         "the first and the last sample of the shard and a fixed, seeded sample of the whole logits tensor")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20          # elements of the seeded whole-tensor sample (4 MB in float32)
+DUMP_SEED = 20240
+DUMP_SAMPLE_BYTES = 28 << 20  # cap per dumped sample: 2 x 28 MB + 4 MB stays under 64 MB
+
+
+def dump_outputs(out, dirname):
+    """What the timed path returned in its last step, as float32 .npy files (< 64 MB in all): the logits of the first and
+    the last sample (every position, up to DUMP_SAMPLE_BYTES each), and DUMP_SAMPLE elements of the whole tensor at flat
+    indices drawn from a fixed seed (sorted)."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    flat = out.reshape(-1)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),),
+                        generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values.to(out.device)
+    rows = max(1, DUMP_SAMPLE_BYTES // (out.shape[-1] * 4))         # positions kept per sample (all 114 by default)
+    arrays = {"logits_first_sample": out[0, :rows], "logits_last_sample": out[-1, :rows], "logits_seeded_sample": flat[idx]}
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a.float().cpu().numpy())
 
 
 _PMC_TILES = {"160x128": "gemm_kernel<{T},160,128", "128x128": "gemm_kernel<{T},128,128", "64x64": "gemm_kernel<{T},64,64",
@@ -378,7 +411,7 @@ def main():
     t_build = time.time()
     model = Kosmos._from_config(cfg, seed=0).eval()            # identical weights on every rank (replicated)
     cpu_weights = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from helpers import oracle_weights
         cpu_weights = oracle_weights(model)                     # shares the CPU storage, no copy
     model = model.to(dev)
@@ -467,10 +500,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert out.shape[-1] == cfg.vocab and out.shape[-2] == Tt + cfg.perceiver.latents
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # ---- roofline leg: the same step, instrumented launch by launch with HIP events on the launch stream ----
     roofline, breakdown, gemm_shapes = None, None, None
-    if rank == 0 and args.prof_steps > 0:
+    if rank == 0 and args.full and args.prof_steps > 0:
         model.use_hip_graphs = False                        # per-launch events cannot be recorded under capture/replay
         _hip.prof_enable(True)
         for _ in range(args.prof_steps):
@@ -534,7 +569,7 @@ def main():
 
     # ---- the same step in the other precision modes (single-GPU run only; reported next to the headline, never as it) ----
     other_modes = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not force_dist and args.full and not args.no_cpu_baseline:
         other_modes = {}
         for mode in [m for m in ("bf16", "mixed", "f16c", "bf16x3", "fp32") if m != args.precision]:
             model.precision = mode
@@ -554,7 +589,7 @@ def main():
     _ops.set_objective("latency")                            # the legs below issue one request at a time
     # ---- SURVEY 8f row 1 next to the headline: one training step of the text decoder (never part of `value`) ----
     training = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_cpu_baseline and not args.no_extra:
+    if rank == 0 and world == 1 and not force_dist and args.full and not args.no_cpu_baseline and not args.no_extra:
         try:
             from kosmosx.model import KosmosLanguage
             from kosmosx.training import LanguageModelTrainer
@@ -610,7 +645,7 @@ def main():
     # ---- BASELINE.json configs[2] ("C3"): text-only KosmosLanguage forward, B = 32, T = 2046 (2048 overflows the reference's
     # position table) — the config the north star's ">= 40 % of bf16 MFMA peak" is quoted on.  bf16 and f16c. ----
     c3 = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_extra:
+    if rank == 0 and world == 1 and not force_dist and args.full and not args.no_extra:
         try:
             c3 = c3_leg(cfg, dev, _hip, check=not args.no_cpu_baseline)
         except Exception as e:
@@ -623,7 +658,7 @@ def main():
     # bf16, the mode the same line marks meets_tolerance: false).  "mixed" / "f16c" steps run fp32 products on block-scaled
     # 16-bit weights streamed as 2.125 bytes each (Decoder._forward_incremental; an f16c row would stream 4).
     decode, decode_check = None, None
-    if rank == 0 and world == 1 and not force_dist and not args.no_extra:
+    if rank == 0 and world == 1 and not force_dist and args.full and not args.no_extra:
         try:
             from kosmosx.model import KosmosLanguage
             d = cfg.decoder
@@ -681,7 +716,7 @@ def main():
 
     # ---- BASELINE.json configs[1]: batch 1 (one 224x224 image + 50 tokens), one request at a time: weight-streaming bound ----
     batch1 = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_extra:
+    if rank == 0 and world == 1 and not force_dist and args.full and not args.no_extra:
         batch1 = {}
         live_bytes = 3.20e9                                   # bf16 operand copies of the live weights
         for mode in ("bf16", "mixed"):
@@ -827,6 +862,7 @@ def main():
             "value": round(total / elapsed, 3), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": DTYPE_NAMES[args.precision], "data": "synthetic",
+            "full": bool(args.full),
             "config": {"workload": f"{B} samples/GPU/step, each 1x3x224x224 image + {Tt} text tokens -> logits "
                                    f"[{Tt + cfg.perceiver.latents},{cfg.vocab}]; CLIP ViT-L/14 + Perceiver(257->64) + "
                                    "24L/2048d sub-LN XPos decoder, random-init weights (BASELINE.json configs[3] per-GPU share)",

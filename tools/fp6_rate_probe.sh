@@ -10,7 +10,7 @@ P=$PWD/kosmos-x_amd/build/fp6probe/libkosmosx_hip_fp6probe.so
 for rnd in 1 2; do
   for lib in default "$P"; do
     if [[ $lib == default ]]; then unset KOSMOSX_HIP_LIB; else export KOSMOSX_HIP_LIB=$lib; fi
-    python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); g={(x['M'],x['N'],x['K']):x for x in d.get('gemm_shapes',[])}
 print('$(basename $lib)', 'ms/step', d['ms_per_step'], 'samples/s', d['value'], ' '.join(f\"{k[1]}x{k[2]}:{v['ms_per_step']:.2f}ms\" for k,v in g.items() if k[0]==3648))"

@@ -3,7 +3,7 @@
 # Every profile file is named for what it contains: the B = 32 kernel table profiles the step and
 # nothing else (--no-extra --no-cpu-baseline --prof-steps 0), the decode tables are per precision.
 #   tests      pytest -m gpu                                   -> pytest_gpu.log
-#   bench      python bench.py (driver's command, 10 steps)    -> bench_default.json
+#   bench      python bench.py --full (10 steps)               -> bench_default.json
 #   prof32     rocprofv3 --kernel-trace --stats of the B = 32 step only -> kernel_stats_mixed_b32_step_only.csv
 #   profdec    ... of tools/bench_decode.py --precision mixed / bf16    -> kernel_stats_decode_{mixed,bf16}.csv
 #   profb1     ... of the batch-1 forward (bf16)                        -> kernel_stats_b1_bf16.csv
@@ -28,7 +28,7 @@ case $WHAT in
     timeout 2400 python -m pytest tests -m gpu -q --maxfail=30 -p no:cacheprovider --durations=8 -s > $O/pytest_gpu.log 2>&1
     grep -E "passed|failed" $O/pytest_gpu.log | tail -3; grep -E "^(FAILED|ERROR)" $O/pytest_gpu.log | head -30 ;;
   bench)
-    timeout 1200 python bench.py --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench.err; tail -c 400 $O/bench_default.json; echo; tail -3 $O/bench.err ;;
+    timeout 1200 python bench.py --full --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench.err; tail -c 400 $O/bench_default.json; echo; tail -3 $O/bench.err ;;
   prof32)  stats mixed_b32_step_only python $PWD/bench.py --steps 5 --warmup 2 --pipeline 1 --no-cpu-baseline --no-extra --prof-steps 0 ;;   # one stream: durations are each kernel alone on the chip
   profdec) stats decode_mixed python $PWD/tools/bench_decode.py --precision mixed
            stats decode_bf16 python $PWD/tools/bench_decode.py --precision bf16 ;;
@@ -39,7 +39,7 @@ case $WHAT in
       PMC_OUT=$O/pmc_decode/$mode PMC_GROUPS="fetch write" PMC_CMD="python $PWD/tools/bench_decode.py --precision $mode --steps 16" bash tools/pmc_round.sh
     done ;;
   c3)      timeout 400 python tools/bench_c3.py > $O/c3_bf16.json 2>/dev/null; tail -c 300 $O/c3_bf16.json; echo ;;
-  b1)      timeout 300 python bench.py --batch 1 --pipeline 1 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_b1.json 2>/dev/null; tail -c 300 $O/bench_b1.json; echo ;;
+  b1)      timeout 300 python bench.py --full --batch 1 --pipeline 1 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_b1.json 2>/dev/null; tail -c 300 $O/bench_b1.json; echo ;;
   decode)  for mode in bf16 mixed fp32; do for b in 1 4 8 16; do
              echo "== $mode B=$b"; timeout 300 python tools/bench_decode.py --precision $mode --batch $b 2>/dev/null | tail -1; done; done > $O/decode_modes.log; cat $O/decode_modes.log ;;
   train)   timeout 300 python tools/bench_train.py --precision bf16 > $O/train_bf16.json 2>/dev/null; tail -c 300 $O/train_bf16.json; echo ;;
