@@ -336,6 +336,60 @@ int kx_token_range(const int64_t* tokens, int64_t n, int64_t* out2, void* stream
 
 
 /* ------------------------------------------------------------------------------------------
+ * Token sampling on the device — the end of a decode step (added within ABI 7: one struct, two functions and one
+ * kx_struct_id value are appended; no existing layout moves, so kx_version() stays 7).
+ *
+ * kx_sample_logits: one launch, one workgroup per row of fp32 logits [B, V] (leading dimension ld >= V; any V >= 1, rows
+ * need no alignment).  Per row b, in the order of the `transformers` logits processors:
+ *   1. repetition penalty r (1 = off): every id in history[b, 0:hist_len], once per distinct id: l > 0 ? l / r : l * r;
+ *   2. temperature T: x = l / T.  T == 0 or do_sample == 0: GREEDY — arg max of the penalised logits, lowest index among
+ *      exact ties, no filter, no random numbers;
+ *   3. top-k (k <= 0 or k >= V = off): keep x_i >= the k-th largest value (ties at the threshold are all kept);
+ *   4. top-p (p >= 1 = off): with the softmax renormalised over what top-k kept, keep token i iff the probability mass of
+ *      tokens with STRICTLY greater x is < p.  A value threshold: always keeps the arg max, independent of any sort order;
+ *   5. draw: arg max over the kept set of x_i - log(-log(u_i)) (Gumbel-max), lowest index on exact ties,
+ *      u_i = (2 (w >> 9) + 1) 2^-24 with w = word (i & 3) of Philox4x32-10(counter = (position, sequence id, i >> 2, 0),
+ *      key = seed): position = args.position (the absolute position of the token being generated), sequence id =
+ *      sequence_ids[b] (its low 32 bits; NULL = the row index b).  A sequence's draws depend on (seed, its id, the position,
+ *      its logits) only — not on the batch row it occupies, the batch size, or the launch geometry;
+ *   6. -inf and NaN logits are never selected; a row with no candidate emits pad_id and is marked finished;
+ *   7. finished [B] uint8 (in/out, may be NULL): a finished row emits pad_id; a row that draws eos_id (< 0 = none) emits it
+ *      and becomes finished;
+ *   8. outputs: next_token [B] int64 (required: what kx_embed_step reads in the next step); optional out_tokens[b * out_ld +
+ *      out_col], history[b * hist_ld + hist_len] (append: hist_ld > hist_len), kept_count [B] int32 and keep_mask [B, V]
+ *      uint8 (the kept set; under greedy: the candidates).
+ * Bit-for-bit reproducible: thresholds come from integer histograms (counts; exp(x - max) in 2^-40 fixed point), maxima from
+ * (value, index) pairs — no floating-point sum whose order the hardware chooses.  x, the penalty and 1/T are IEEE fp32.
+ * x saturates as fp32 does: where l / T overflows, negative logits become -inf and drop out of the candidate set, positive ones
+ * become +inf and tie at the maximum (exp(inf - inf) counts as 1); the draw is then among those ties.
+ * Limits (KX_ERR_UNSUPPORTED): V <= 2^23; with a repetition penalty V <= 327680 (the history bitmap is kept in LDS).
+ * Argument errors name the argument and are reported before any launch.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_sample_args) of the caller ("stale binding" otherwise) */
+  int32_t do_sample;                          /* 0 = greedy */
+  const float* logits; int64_t ld; int64_t B; int64_t V;
+  float temperature; int32_t top_k; float top_p; float repetition_penalty;
+  uint64_t seed; int64_t position;
+  const int64_t* sequence_ids;                /* [B] or NULL */
+  int64_t* history; int64_t hist_ld; int64_t hist_len;
+  uint8_t* finished;
+  int64_t eos_id; int64_t pad_id;
+  int64_t* next_token;
+  int64_t* out_tokens; int64_t out_ld; int64_t out_col;
+  int32_t* kept_count; uint8_t* keep_mask;
+} kx_sample_args;
+int kx_sample_logits(const kx_sample_args* args, void* stream);
+
+/* Embedding of one generated token per sequence: out[b] = embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b] when
+ * pos_b >= 0), tokens [B] int64 ON THE DEVICE (kx_sample_logits' next_token), out [B, d] fp32.  The row kx_embed_splice
+ * writes for a text token, additions in the same order: KosmosLanguage / u1_alias = 0: pos_a = the token's position,
+ * pos_b = -1; the multimodal prompt with u1_alias = 1: pos_a = its text index, pos_b = its spliced index (text index +
+ * n_img).  Ids are clamped to [0, vocab) for memory safety; either position beyond the table returns KX_ERR_INVALID_ARG
+ * ("position ... out of range"), as kx_embed_splice does. */
+int kx_embed_step(const int64_t* tokens, const float* embed, const float* pos, float* out, int64_t B, int64_t d,
+                  int64_t vocab, int64_t max_pos, int64_t pos_a, int64_t pos_b, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stage-level entry points (what kosmosx.model calls).  Weight structs hold device pointers
  * to tensors packed by the Python side from the reference's state_dict key namespace
  * (SURVEY.md §8b); `w*` GEMM operands are in the dtype of `prec`, everything else fp32.
@@ -351,7 +405,8 @@ int kx_token_range(const int64_t* tokens, int64_t n, int64_t* out2, void* stream
 typedef enum {
   KX_STRUCT_GEMM_ARGS = 0, KX_STRUCT_ATTN_ARGS = 1, KX_STRUCT_VIT_LAYER = 2, KX_STRUCT_VIT_WEIGHTS = 3,
   KX_STRUCT_PERCEIVER_LAYER = 4, KX_STRUCT_PERCEIVER_WEIGHTS = 5, KX_STRUCT_DECODER_LAYER = 6,
-  KX_STRUCT_DECODER_WEIGHTS = 7, KX_STRUCT_RESAMPLE_PLAN = 8, KX_STRUCT_PROF_RECORD = 9, KX_STRUCT_COUNT = 10
+  KX_STRUCT_DECODER_WEIGHTS = 7, KX_STRUCT_RESAMPLE_PLAN = 8, KX_STRUCT_PROF_RECORD = 9, KX_STRUCT_SAMPLE_ARGS = 10,
+  KX_STRUCT_COUNT = 11
 } kx_struct_id;
 /* sizeof() of the struct as this library was compiled; 0 for an unknown id.  Pure host arithmetic. */
 size_t kx_struct_bytes(int32_t id);

@@ -302,6 +302,7 @@ extern "C" size_t kx_struct_bytes(int32_t id) {
     case KX_STRUCT_DECODER_WEIGHTS: return sizeof(kx_decoder_weights);
     case KX_STRUCT_RESAMPLE_PLAN: return sizeof(kx_resample_plan);
     case KX_STRUCT_PROF_RECORD: return sizeof(kx_prof_record);
+    case KX_STRUCT_SAMPLE_ARGS: return sizeof(kx_sample_args);
     default: return 0;
   }
 }

@@ -1,0 +1,373 @@
+// Token sampling on the device (kx_sample_logits) and the one-row embedding launch that feeds a sampled token back into
+// the decoder (kx_embed_step): the last piece of autoregressive decoding.  Contract: include/kosmosx_hip.h.
+//
+// One launch per decode step, one 1024-thread workgroup per sequence, nothing shared between workgroups.  Everything that
+// decides a result is either an exact integer operation or a per-element fp32 expression, so a row's outputs do not depend
+// on the order in which lanes, waves or atomics happen to run:
+//   * x_i (penalised logit / T) is mapped to an order-preserving 32-bit key; maxima are taken over (key, ~index) pairs;
+//   * the k-th largest value and the top-p threshold are found by radix select on that key (11 + 11 + 10 bits) over a
+//     2048-bin LDS histogram of 64-bit INTEGER sums: element counts for top-k, exp(x_i - max) in 2^-40 fixed point for top-p
+//     (integer adds commute, so the LDS atomics may land in any order);
+//   * the draw is a Gumbel arg max with Philox4x32-10 addressed by (seed, sequence id, position, element index).
+// Every loop has a trip count fixed by V, the histogram size or the wave width; there is no waiting on other threads
+// beyond __syncthreads().
+#include "kx_common.h"
+
+namespace {
+
+constexpr int SB = 1024;                          // threads per workgroup (16 waves)
+constexpr int SW = SB / 64;
+constexpr int BINS = 2048;
+constexpr unsigned KEY_MIN_VALID = 0x00800000u;   // key(-FLT_MAX): every finite value and +inf map at or above it, -inf below
+constexpr long long KX_SAMPLE_MAX_V = 1ll << 23;  // 2^23 values of at most 2^40 each stay below 2^63
+constexpr long long KX_SAMPLE_MAX_V_PENALTY = 40960ll * 8;   // the history bitmap lives in LDS next to the histogram
+
+struct SampleParams {
+  const float* logits; long long ld; int V;
+  float T, p, r; int k, greedy, pen;
+  unsigned long long seed; unsigned position;
+  const long long* seq;
+  long long* history; long long hist_ld; int hist_len;
+  unsigned char* finished; long long eos, pad;
+  long long* next; long long* out_tokens; long long out_ld, out_col;
+  int* kept_count; unsigned char* keep_mask;
+};
+
+__device__ __forceinline__ unsigned f2key(float x) {
+  const unsigned b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// x_i: repetition penalty (ids in the row's history, once per distinct id), then temperature; both IEEE fp32 divisions.
+// NaN and -inf come back as -inf (never a candidate), -0 as +0 (one key per value).
+__device__ __forceinline__ float load_x(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, int i) {
+  float l = row[i];
+  if (a.pen && ((bitmap[i >> 5] >> (i & 31)) & 1u)) l = l > 0.f ? l / a.r : l * a.r;
+  if (!a.greedy) l = l / a.T;
+  if (!(l > -__builtin_inff())) l = -__builtin_inff();
+  if (l == 0.f) l = 0.f;
+  return l;
+}
+
+// exp(x - m) in 2^-40 fixed point (truncated); x == m gives exactly 2^40, also when both are +inf
+__device__ __forceinline__ unsigned long long mass_fix(float x, float m) {
+  const float e = x == m ? 1.0f : expf(x - m);
+  return (unsigned long long)(e * 1099511627776.0f);
+}
+
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long r = red[0];
+#pragma unroll
+  for (int w = 1; w < SW; ++w) r = red[w] > r ? red[w] : r;
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long r = red[0];
+#pragma unroll
+  for (int w = 1; w < SW; ++w) r += red[w];
+  __syncthreads();
+  return r;
+}
+
+// The largest key K (among candidates with key >= limit) whose weight at or above it reaches `target`:
+//   MASS = false: weight = element count  -> K = the target-th largest value;
+//   MASS = true : weight = mass_fix       -> K = the smallest value whose strictly-greater mass is still below target.
+// Three histogram passes fix the key's digits from the top; `carry` is the weight strictly above the chosen bin.
+// Returns false (key untouched) when the whole weight stays below target.
+template <bool MASS>
+__device__ bool radix_select(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, float m,
+                             unsigned limit, unsigned long long target, unsigned long long* hist,
+                             unsigned long long* gsum, unsigned long long* sel, unsigned& key_out) {
+  const int tid = threadIdx.x;
+  unsigned prefix = 0, pmask = 0;
+  unsigned long long carry = 0;
+#pragma unroll 1
+  for (int level = 0; level < 3; ++level) {
+    const int shift = level == 0 ? 21 : (level == 1 ? 10 : 0);
+    const unsigned dmask = level == 2 ? 1023u : 2047u;
+    for (int j = tid; j < BINS; j += SB) hist[j] = 0;
+    __syncthreads();
+#pragma unroll 4
+    for (int i = tid; i < a.V; i += SB) {            // consecutive lanes read consecutive logits
+      const float x = load_x(a, row, bitmap, i);
+      const unsigned key = f2key(x);
+      if (key >= limit && (key & pmask) == prefix) {
+        const unsigned long long inc = MASS ? mass_fix(x, m) : 1ull;
+        if (inc) atomicAdd(&hist[(key >> shift) & dmask], inc);
+      }
+    }
+    __syncthreads();
+    // Scan from the top in two steps, every LDS read with consecutive lanes on consecutive bins: the 32 sums of 64-bin
+    // groups (two per wave), then wave 0 picks the group and the bin inside it.
+    for (int g = (tid >> 6) * 2; g < (tid >> 6) * 2 + 2; ++g) {
+      unsigned long long v = hist[g * 64 + (tid & 63)];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if ((tid & 63) == 0) gsum[g] = v;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const unsigned long long gs = tid < 32 ? gsum[31 - tid] : 0ull;         // lane 0 = the top group
+      unsigned long long incl = gs;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += t;
+      }
+      const unsigned long long hit = __ballot(tid < 32 && carry + incl >= target);
+      if (hit == 0) {
+        if (tid == 0) sel[0] = ~0ull;
+      } else {
+        const int fl = __ffsll((long long)hit) - 1;
+        const int G = 31 - fl;
+        const unsigned long long above = __shfl(carry + incl - gs, fl, 64);   // weight strictly above group G
+        const unsigned long long h = hist[G * 64 + 63 - tid];                 // lane 0 = the group's top bin
+        unsigned long long incl2 = h;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned long long t = __shfl_up(incl2, o, 64);
+          if (tid >= o) incl2 += t;
+        }
+        const unsigned long long hit2 = __ballot(above + incl2 >= target);    // non-empty: the group's total reaches target
+        if (tid == __ffsll((long long)hit2) - 1) {
+          sel[0] = (unsigned long long)(G * 64 + 63 - tid);
+          sel[1] = above + incl2 - h;
+        }
+      }
+    }
+    __syncthreads();
+    const unsigned long long bin = sel[0];
+    if (bin == ~0ull) { __syncthreads(); return false; }
+    carry = sel[1];
+    prefix |= (unsigned)bin << shift;
+    pmask |= dmask << shift;
+  }
+  __syncthreads();
+  key_out = prefix;
+  return true;
+}
+
+__global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a) {
+  __shared__ unsigned long long hist[BINS];
+  __shared__ unsigned long long red[SW];
+  __shared__ unsigned long long gsum[BINS / 64];
+  __shared__ unsigned long long sel[2];
+  extern __shared__ unsigned bitmap[];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const float* __restrict__ row = a.logits + b * a.ld;
+  unsigned char* mask = a.keep_mask ? a.keep_mask + b * a.V : nullptr;
+
+  long long tok = a.pad;
+  int fin = 0, kept = 0;
+  if (a.finished && a.finished[b]) {                  // (uniform: one byte, read by every thread)
+    if (mask) for (int i = tid; i < a.V; i += SB) mask[i] = 0;
+  } else {
+    if (a.pen) {
+      const int words = (a.V + 31) >> 5;
+      for (int j = tid; j < words; j += SB) bitmap[j] = 0;
+      __syncthreads();
+      for (int j = tid; j < a.hist_len; j += SB) {
+        const long long id = a.history[b * a.hist_ld + j];
+        if (id >= 0 && id < a.V) atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+      }
+      __syncthreads();
+    }
+    // arg max of x, lowest index among exact ties: max over (key << 32 | ~index)
+    unsigned long long best = 0;
+#pragma unroll 4
+    for (int i = tid; i < a.V; i += SB) {
+      const unsigned long long pk = ((unsigned long long)f2key(load_x(a, row, bitmap, i)) << 32) | (0xffffffffu - (unsigned)i);
+      best = pk > best ? pk : best;
+    }
+    best = block_max_u64(best, red);
+    const unsigned kmax = (unsigned)(best >> 32);
+    if (kmax < KEY_MIN_VALID) {                       // no candidate: pad, and the row is finished
+      fin = 1;
+      if (mask) for (int i = tid; i < a.V; i += SB) mask[i] = 0;
+    } else if (a.greedy) {
+      tok = 0xffffffffu - (unsigned)best;
+      if (mask || a.kept_count) {                     // greedy applies no filter: the debug outputs report the candidates
+        unsigned long long c = 0;
+        for (int i = tid; i < a.V; i += SB) {
+          const bool v = f2key(load_x(a, row, bitmap, i)) >= KEY_MIN_VALID;
+          if (mask) mask[i] = v;
+          c += v;
+        }
+        kept = (int)block_sum_u64(c, red);
+      }
+    } else {
+      const float m = key2f(kmax);
+      unsigned tau = KEY_MIN_VALID;
+      if (a.k > 0 && a.k < a.V) {
+        unsigned kk;
+        if (radix_select<false>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
+      }
+      if (a.p < 1.0f) {
+        unsigned long long z = 0;                     // mass of what top-k kept
+#pragma unroll 4
+        for (int i = tid; i < a.V; i += SB) {
+          const float x = load_x(a, row, bitmap, i);
+          if (f2key(x) >= tau) z += mass_fix(x, m);
+        }
+        z = block_sum_u64(z, red);
+        // keep iff (mass strictly above) < p Z; the masses are integers, so "< p Z" is "< ceil(p Z)"
+        const unsigned long long target = (unsigned long long)ceil((double)a.p * (double)z);
+        unsigned kp;
+        if (radix_select<true>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
+      }
+      // Gumbel arg max over the kept set {key >= tau}; Philox block `base / 4` serves elements base .. base + 3, so here
+      // (and only here) a thread owns four consecutive elements
+      const unsigned long long ctr = ((unsigned long long)(unsigned)(a.seq ? a.seq[b] : b) << 32) | a.position;
+      unsigned long long gbest = 0, c = 0;
+      for (int base = tid * 4; base < a.V; base += SB * 4) {
+        float xs[4];
+        bool kp[4], any = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = base + e;
+          kp[e] = false;
+          xs[e] = 0.f;
+          if (i < a.V) {
+            xs[e] = load_x(a, row, bitmap, i);
+            kp[e] = f2key(xs[e]) >= tau;
+            if (mask) mask[i] = kp[e];
+          }
+          any |= kp[e];
+        }
+        if (any) {
+          unsigned w[4];
+          philox4x32_10(ctr, (unsigned)(base >> 2), a.seed, w);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (kp[e]) {
+              const float u = (float)(2u * (w[e] >> 9) + 1u) * 5.9604644775390625e-8f;      // odd / 2^24: exact, inside (0, 1)
+              const float score = xs[e] - logf(-logf(u));
+              const unsigned long long pk = ((unsigned long long)f2key(score) << 32) | (0xffffffffu - (unsigned)(base + e));
+              gbest = pk > gbest ? pk : gbest;
+              ++c;
+            }
+          }
+        }
+      }
+      gbest = block_max_u64(gbest, red);
+      kept = (int)block_sum_u64(c, red);
+      tok = 0xffffffffu - (unsigned)gbest;
+    }
+    if (!fin && a.eos >= 0 && tok == a.eos) fin = 1;
+  }
+  if (tid == 0) {
+    a.next[b] = tok;
+    if (a.out_tokens) a.out_tokens[b * a.out_ld + a.out_col] = tok;
+    if (a.history) a.history[b * a.hist_ld + a.hist_len] = tok;
+    if (a.finished && fin) a.finished[b] = 1;
+    if (a.kept_count) a.kept_count[b] = kept;
+  }
+}
+
+// out[b] = embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b]): the row embed_splice_kernel writes for a text token whose
+// first / second position rows are pos_a / pos_b, in the same order of additions.
+__global__ __launch_bounds__(256) void embed_step_kernel(const long long* __restrict__ tokens, const float* __restrict__ embed,
+                                                         const float* __restrict__ pos, float* __restrict__ out, int d,
+                                                         long long vocab, long long pos_a, long long pos_b) {
+  const long long b = blockIdx.x;
+  long long id = tokens[b];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);   // memory safety only
+  const float4* src = reinterpret_cast<const float4*>(embed + id * d);
+  const float4* pa = reinterpret_cast<const float4*>(pos + (2 + pos_a) * d);
+  const float4* pb = pos_b >= 0 ? reinterpret_cast<const float4*>(pos + (2 + pos_b) * d) : nullptr;
+  float4* o = reinterpret_cast<float4*>(out + b * d);
+  for (int c = threadIdx.x; c < (d >> 2); c += 256) {
+    float4 v = src[c];
+    const float4 a1 = pa[c];
+    v.x += a1.x; v.y += a1.y; v.z += a1.z; v.w += a1.w;
+    if (pb) { const float4 a2 = pb[c]; v.x += a2.x; v.y += a2.y; v.z += a2.z; v.w += a2.w; }
+    o[c] = v;
+  }
+}
+
+}  // namespace
+
+extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) {
+  KX_REQUIRE(args != nullptr, "kx_sample_logits: null args");
+  KX_REQUIRE(args->struct_bytes == sizeof(kx_sample_args),
+             "kx_sample_logits: stale binding — caller declares kx_sample_args as %u bytes, this library (ABI %d) as %zu",
+             (unsigned)args->struct_bytes, KX_ABI_VERSION, sizeof(kx_sample_args));
+  KX_REQUIRE(args->logits != nullptr, "kx_sample_logits: null logits");
+  KX_REQUIRE(args->next_token != nullptr, "kx_sample_logits: null next_token");
+  KX_REQUIRE(args->B >= 1 && args->B <= 0x7fffffffll, "kx_sample_logits: B=%lld must be >= 1", (long long)args->B);
+  KX_REQUIRE(args->V >= 1, "kx_sample_logits: V=%lld must be >= 1", (long long)args->V);
+  KX_REQUIRE(args->ld >= args->V, "kx_sample_logits: ld=%lld is smaller than V=%lld", (long long)args->ld, (long long)args->V);
+  KX_REQUIRE(args->temperature >= 0.0f, "kx_sample_logits: temperature=%g must be >= 0", (double)args->temperature);
+  KX_REQUIRE(args->top_p > 0.0f, "kx_sample_logits: top_p=%g must be > 0", (double)args->top_p);
+  KX_REQUIRE(args->repetition_penalty > 0.0f, "kx_sample_logits: repetition_penalty=%g must be > 0",
+             (double)args->repetition_penalty);
+  KX_REQUIRE(args->hist_len >= 0 && args->hist_len <= 0x7fffffffll, "kx_sample_logits: hist_len=%lld must be >= 0",
+             (long long)args->hist_len);
+  KX_REQUIRE(args->history == nullptr || args->hist_ld > args->hist_len,
+             "kx_sample_logits: hist_ld=%lld leaves no room to append after hist_len=%lld", (long long)args->hist_ld,
+             (long long)args->hist_len);
+  KX_REQUIRE(args->out_tokens == nullptr || (args->out_col >= 0 && args->out_col < args->out_ld),
+             "kx_sample_logits: out_col=%lld outside [0, out_ld=%lld)", (long long)args->out_col, (long long)args->out_ld);
+  KX_REQUIRE(args->position >= 0 && args->position <= 0xffffffffll, "kx_sample_logits: position=%lld outside [0, 2^32)",
+             (long long)args->position);
+  if (args->V > KX_SAMPLE_MAX_V) {
+    kx_set_error("kx_sample_logits: V=%lld exceeds %lld (64-bit fixed-point mass)", (long long)args->V, KX_SAMPLE_MAX_V);
+    return KX_ERR_UNSUPPORTED;
+  }
+  SampleParams p;
+  p.logits = args->logits; p.ld = args->ld; p.V = (int)args->V;
+  p.greedy = (!args->do_sample || args->temperature == 0.0f) ? 1 : 0;
+  p.T = args->temperature; p.p = args->top_p; p.r = args->repetition_penalty; p.k = args->top_k;
+  p.pen = (args->repetition_penalty != 1.0f && args->history != nullptr && args->hist_len > 0) ? 1 : 0;
+  if (p.pen && args->V > KX_SAMPLE_MAX_V_PENALTY) {
+    kx_set_error("kx_sample_logits: repetition_penalty with V=%lld exceeds %lld (the history bitmap is kept in LDS)",
+                 (long long)args->V, KX_SAMPLE_MAX_V_PENALTY);
+    return KX_ERR_UNSUPPORTED;
+  }
+  p.seed = args->seed; p.position = (unsigned)args->position;
+  p.seq = (const long long*)args->sequence_ids;
+  p.history = (long long*)args->history; p.hist_ld = args->hist_ld; p.hist_len = (int)args->hist_len;
+  p.finished = args->finished; p.eos = args->eos_id; p.pad = args->pad_id;
+  p.next = (long long*)args->next_token; p.out_tokens = (long long*)args->out_tokens;
+  p.out_ld = args->out_ld; p.out_col = args->out_col;
+  p.kept_count = args->kept_count; p.keep_mask = args->keep_mask;
+  const size_t lds = p.pen ? (size_t)((args->V + 31) / 32) * 4 : 0;
+  KxProfScope prof(KX_K_MISC, args->B, args->V, 0, (hipStream_t)stream);
+  hipLaunchKernelGGL(sample_kernel, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p);
+  KX_CHECK_LAUNCH("kx_sample_logits");
+  return KX_OK;
+}
+
+extern "C" int kx_embed_step(const int64_t* tokens, const float* embed, const float* pos, float* out, int64_t B,
+                             int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_a, int64_t pos_b, void* stream) {
+  KX_REQUIRE(tokens && embed && pos && out, "kx_embed_step: null pointer");
+  KX_REQUIRE(B > 0 && B <= 0x7fffffffll && d > 0 && d % 4 == 0 && vocab > 0, "kx_embed_step: bad shape B=%lld d=%lld vocab=%lld",
+             (long long)B, (long long)d, (long long)vocab);
+  KX_REQUIRE((((uintptr_t)embed | (uintptr_t)pos | (uintptr_t)out) & 15) == 0, "kx_embed_step: pointers must be 16-byte aligned");
+  // the same condition and wording as kx_embed_splice (the Python boundary turns it into the reference's IndexError)
+  KX_REQUIRE(pos_a >= 0 && pos_a + 2 < max_pos, "kx_embed_step: position %lld out of range for a %lld-row table",
+             (long long)(pos_a + 2), (long long)max_pos);
+  KX_REQUIRE(pos_b < 0 || pos_b + 2 < max_pos, "kx_embed_step: position %lld out of range for a %lld-row table",
+             (long long)(pos_b + 2), (long long)max_pos);
+  KxProfScope prof(KX_K_EMBED, B, d, 0, (hipStream_t)stream);
+  hipLaunchKernelGGL(embed_step_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const long long*)tokens,
+                     embed, pos, out, (int)d, (long long)vocab, (long long)pos_a, (long long)pos_b);
+  KX_CHECK_LAUNCH("kx_embed_step");
+  return KX_OK;
+}

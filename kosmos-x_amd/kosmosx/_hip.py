@@ -128,6 +128,20 @@ class ResamplePlan(C.Structure):
                 ("span_px", i32), ("hbounds", vp), ("hcoef", vp), ("vbounds", vp), ("vcoef", vp)]
 
 
+class SampleArgs(C.Structure):
+    """kx_sample_args; struct_bytes is filled in at construction ("stale binding" check of kx_sample_logits)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("do_sample", i32), ("logits", vp), ("ld", i64), ("B", i64), ("V", i64),
+                ("temperature", f32), ("top_k", i32), ("top_p", f32), ("repetition_penalty", f32),
+                ("seed", C.c_uint64), ("position", i64), ("sequence_ids", vp),
+                ("history", vp), ("hist_ld", i64), ("hist_len", i64), ("finished", vp), ("eos_id", i64), ("pad_id", i64),
+                ("next_token", vp), ("out_tokens", vp), ("out_ld", i64), ("out_col", i64),
+                ("kept_count", vp), ("keep_mask", vp)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -148,6 +162,8 @@ SYMBOLS = {
     "kx_row_stats_finalize": (C.c_int, [vp, i64, i64, i64, f32, vp, vp]),
     "kx_embed_splice": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp]),
     "kx_token_range": (C.c_int, [vp, i64, vp, vp]),
+    "kx_sample_logits": (C.c_int, [C.POINTER(SampleArgs), vp]),
+    "kx_embed_step": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp]),
     "kx_set_tuning": (C.c_int, [C.c_int, C.c_int]),
     "kx_prof_enable": (C.c_int, [C.c_int]),
     "kx_prof_collect": (C.c_int, [C.POINTER(ProfRecord), C.c_int]),
@@ -201,7 +217,7 @@ SYMBOLS = {
 
 
 STRUCT_IDS = [GemmArgs, AttnArgs, VitLayer, VitWeights, PerceiverLayer, PerceiverWeights, DecoderLayer, DecoderWeights,
-              ResamplePlan, ProfRecord]            # index = kx_struct_id
+              ResamplePlan, ProfRecord, SampleArgs]            # index = kx_struct_id
 
 
 def lib_path() -> Path:

@@ -795,10 +795,13 @@ class Decoder(_PackedMixin, nn.Module):
         return logits
 
     # -- incremental decoding ---------------------------------------------------
-    def _forward_incremental(self, tokens, state: dict, passed_x, prec: str) -> torch.Tensor:
+    def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None) -> torch.Tensor:
         """torchscale's incremental_state protocol: the first call runs the whole prefix and fills the KV cache,
         every later call is given the token history (only its last token and its length are used, as upstream's
-        `tokens[:, -1:]`) and appends one position.  ``state`` is an opaque dict owned by the caller."""
+        `tokens[:, -1:]`) and appends one position.  ``state`` is an opaque dict owned by the caller.
+        ``next_token`` (later steps only, used by generate()): the step's token as an int64 [B] tensor the device sampler
+        wrote (kx_sample_logits: ids < vocab by construction, so no range read-back), embedded by kx_embed_step with
+        position rows ``next_pos`` = (pos_a, pos_b); default (t, -1), what ``embed(..., pos_offset=t)`` adds."""
         if self.args.activation_fn != "gelu":
             raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
                                       "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
@@ -872,6 +875,15 @@ class Decoder(_PackedMixin, nn.Module):
         if passed_x is not None:
             _require_cuda(passed_x, "passed_x")
             x = passed_x[:, -1:].to(torch.float32).clone(memory_format=torch.contiguous_format)
+        elif next_token is not None:
+            _require_cuda(next_token, "next_token")
+            pos_a, pos_b = (t, -1) if next_pos is None else next_pos
+            x = torch.empty((next_token.shape[0], 1, D), dtype=torch.float32, device=emb.device)
+            rc = lib.kx_embed_step(next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), x.data_ptr(), next_token.shape[0], D,
+                                   emb.shape[0], pos.shape[0], int(pos_a), int(pos_b), _stream())
+            if rc == 1 and "out of range" in H.last_error():
+                raise IndexError("index out of range in self: " + H.last_error())
+            H.check(rc, "kx_embed_step")
         else:
             x = self.embed(tokens[:, -1:], prec, pos_offset=t, defer_check=True)
         if x.shape[0] != B:
@@ -1112,6 +1124,40 @@ class Kosmos(nn.Module):
             return self._forward_graphed(text_tokens, images)
         return self._forward_impl(text_tokens, images)
 
+    def generate(self, text_tokens: torch.Tensor, images: torch.Tensor, max_new_tokens: int, *, do_sample=False,
+                 temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1,
+                 sequence_ids=None, eos_poll=8, output_logits=False):
+        """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
+        rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
+        [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
+        KV cache, then one decode step + one sampling launch per token with the token kept on the device
+        (kosmosx.generation).  A generated token enters the decoder exactly as it would as part of ``text_tokens`` in
+        forward().  Sampling (``do_sample``): temperature -> top-k -> top-p after the repetition penalty, reproducible from
+        (seed, sequence id, position)."""
+        from . import generation
+        if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
+            raise TypeError("text_tokens and images must be instances of torch.Tensor")
+        _warn_train_mode(self)
+        _require_cuda(text_tokens, "text_tokens")
+        _require_cuda(images, "images")
+        if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
+            raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
+        n_img = self.cfg.perceiver.latents
+        T = text_tokens.shape[1] + n_img
+        generation.check_budget(self.decoder, T, max_new_tokens)
+        prec = self.precision
+        with torch.no_grad():
+            img = self.clip_model.run(images, prec, self._ws)
+            img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
+            x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
+            state = {"max_len": T + max_new_tokens}
+            logits = self.decoder._forward_incremental(None, state, x, prec)
+            return generation.generate_loop(
+                self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens,
+                pos_shift=n_img if self.switches.u1_inplace_alias else 0, do_sample=do_sample, temperature=temperature,
+                top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed, eos_token_id=eos_token_id,
+                pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll, output_logits=output_logits)
+
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
         synchronises, so the whole launch sequence is capturable).  Worth it when the forward is launch-bound
@@ -1204,6 +1250,28 @@ class KosmosLanguage(nn.Module):
             return self.decoder._forward_incremental(x, inc, None, self.precision)
         model_input = self.decoder.embed(x, self.precision)         # :319
         return self.decoder.run(model_input, self.precision)        # :320
+
+    def generate(self, x: torch.Tensor, max_new_tokens: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
+                 repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
+                 output_logits=False):
+        """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate."""
+        from . import generation
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("x must be an instance of torch.Tensor")
+        _warn_train_mode(self)
+        _require_cuda(x, "x")
+        if x.dim() != 2:
+            raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
+        T = x.shape[1]
+        generation.check_budget(self.decoder, T, max_new_tokens)
+        with torch.no_grad():
+            state = {"max_len": T + max_new_tokens}
+            logits = self.decoder._forward_incremental(x, state, None, self.precision)
+            return generation.generate_loop(
+                self.decoder, self.precision, state, logits, x.long(), max_new_tokens, do_sample=do_sample,
+                temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
+                eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
+                output_logits=output_logits)
 
 
 class KosmosTokenizer:

@@ -364,3 +364,50 @@ def embed_splice(tokens, embed, pos, img=None, u1_alias=True, splice_at=2, pos_o
                                   embed.shape[0], pos.shape[0], splice_at, int(u1_alias), pos_offset, _stream())
     H.check(rc, "kx_embed_splice")
     return out
+
+
+def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
+                  position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
+                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0):
+    """Next token of every row of fp32 `logits` [B, V] (row stride >= V), drawn on the device by one launch
+    (kx_sample_logits in include/kosmosx_hip.h: repetition penalty -> temperature -> top-k -> top-p -> Gumbel-max draw
+    addressed by (seed, sequence id, position); greedy when ``do_sample`` is false or ``temperature`` is 0).
+
+    history [B, >= hist_len + 1] int64: the ids the repetition penalty looks at; the new token is appended at column
+    ``hist_len``.  finished [B] uint8 (in/out): finished rows emit ``pad_token_id``, a row that draws ``eos_token_id``
+    becomes finished.  out [B] int64 / out_tokens [B, n] int64 with ``out_col``: caller-owned places for the result.
+    Returns next_token [B] int64 (and kept_count [B] int32, keep_mask [B, V] uint8 with ``return_debug``)."""
+    _need_cuda(logits, sequence_ids, history, finished, out, out_tokens)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("sample_logits: logits must be fp32 [B, V] with unit column stride")
+    for name, t, dt in (("sequence_ids", sequence_ids, torch.int64), ("history", history, torch.int64),
+                        ("finished", finished, torch.uint8), ("out", out, torch.int64), ("out_tokens", out_tokens, torch.int64)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"sample_logits: {name} must be a contiguous {dt} tensor")
+    B, V = logits.shape
+    for name, t in (("sequence_ids", sequence_ids), ("finished", finished), ("out", out)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"sample_logits: {name} must have shape [{B}]")
+    for name, t in (("history", history), ("out_tokens", out_tokens)):
+        if t is not None and (t.dim() != 2 or t.shape[0] != B):
+            raise ValueError(f"sample_logits: {name} must be [{B}, n]")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    a = H.SampleArgs()
+    a.do_sample = int(bool(do_sample))
+    a.logits, a.ld, a.B, a.V = logits.data_ptr(), (logits.stride(0) if B > 1 else max(logits.stride(0), V)), B, V
+    a.temperature, a.top_k, a.top_p, a.repetition_penalty = float(temperature), int(top_k), float(top_p), float(repetition_penalty)
+    a.seed, a.position = int(seed) & 0xFFFFFFFFFFFFFFFF, int(position)
+    a.sequence_ids = H.ptr(sequence_ids)
+    a.history, a.hist_ld, a.hist_len = H.ptr(history), (0 if history is None else history.shape[1]), int(hist_len)
+    a.finished = H.ptr(finished)
+    a.eos_id, a.pad_id = (-1 if eos_token_id is None else int(eos_token_id)), int(pad_token_id)
+    a.next_token = out.data_ptr()
+    a.out_tokens, a.out_ld, a.out_col = H.ptr(out_tokens), (0 if out_tokens is None else out_tokens.shape[1]), int(out_col)
+    kept = mask = None
+    if return_debug:
+        kept = torch.empty(B, dtype=torch.int32, device=logits.device)
+        mask = torch.empty((B, V), dtype=torch.uint8, device=logits.device)
+        a.kept_count, a.keep_mask = kept.data_ptr(), mask.data_ptr()
+    H.check(H.load().kx_sample_logits(C.byref(a), _stream()), "kx_sample_logits")
+    return (out, kept, mask) if return_debug else out

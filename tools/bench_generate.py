@@ -1,0 +1,110 @@
+"""generate() on the full-size text decoder: ms per token of
+  (a) KosmosLanguage.generate() — decode step + the fused on-device sampler, token kept on the device;
+  (b) the same loop with a sampler composed from torch ops (sort / softmax / cumsum / multinomial) and a host token feed
+      through the public incremental path — what a caller had to write before generate() existed;
+  (c) the bare decode step (tools/bench_decode.py's loop) in the same process.
+One JSON line per batch size.  --only a|b|c restricts the run to one variant (for a kernel trace of that variant alone)."""
+import argparse, json, os, sys, time
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "kosmos-x_amd")]
+os.environ.setdefault("KOSMOSX_NO_LOGGING_CONFIG", "1")
+import torch
+from kosmosx import _hip
+from kosmosx.model import KosmosLanguage
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batches", default="1,4,8,16")
+ap.add_argument("--prefix", type=int, default=114)
+ap.add_argument("--new", type=int, default=64)
+ap.add_argument("--precision", default="mixed")
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--only", default="abc")
+a = ap.parse_args()
+dev = torch.device("cuda", 0)
+V = 32002
+m = KosmosLanguage(vocab_size=V, dim=2048, _seed=0).eval().to(dev)
+m.precision = a.precision
+KW = dict(do_sample=True, temperature=0.8, top_k=50, top_p=0.9, seed=1)
+
+
+def torch_sample(logits, gen):
+    """temperature -> top-k -> top-p -> multinomial, the usual composition (transformers' order)."""
+    x = logits / 0.8
+    kth = torch.topk(x, 50, dim=-1).values[:, -1:]
+    x = x.masked_fill(x < kth, float("-inf"))
+    srt, idx = torch.sort(x, dim=-1, descending=False)
+    cum = srt.softmax(-1).cumsum(-1)
+    drop = cum <= 1.0 - 0.9
+    drop[:, -1] = False
+    x = x.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
+    return torch.multinomial(x.softmax(-1), 1, generator=gen)
+
+
+def run_a(tok):
+    return m.generate(tok, a.new, **KW)
+
+
+def run_b(tok):
+    gen = torch.Generator(device=dev).manual_seed(1)
+    state, seq = {"max_len": a.prefix + a.new}, tok
+    out = m(seq, incremental_state=state)
+    for g in range(a.new):
+        nxt = torch_sample(out[:, -1], gen)
+        seq = torch.cat([seq, torch.from_numpy(nxt.cpu().numpy()).to(dev)], 1)     # host token feed
+        if g + 1 < a.new:
+            out = m(seq, incremental_state=state)
+    return seq[:, a.prefix:]
+
+
+def run_c(tok_all):
+    state = {"max_len": a.prefix + a.new}
+    out = m(tok_all[:, : a.prefix], incremental_state=state)
+    for t in range(a.prefix, a.prefix + a.new - 1):
+        out = m(tok_all[:, : t + 1], incremental_state=state)
+    return out
+
+
+def timed(fn, arg):
+    best = None
+    for rep in range(a.reps + 1):                               # rep 0 = warm-up (packs weights, sizes workspaces)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(arg)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if rep:
+            best = dt if best is None else min(best, dt)
+    return best
+
+
+with torch.no_grad():
+    for B in (int(b) for b in a.batches.split(",")):
+        tok_all = torch.randint(0, V, (B, a.prefix + a.new), generator=torch.Generator().manual_seed(0)).to(dev)
+        tok = tok_all[:, : a.prefix].contiguous()
+        # every variant runs one prefill and new - 1 decode steps; the prefill is measured on its own and subtracted
+        pre = timed(lambda t: m(t, incremental_state={"max_len": a.prefix + a.new}), tok)
+        res = {"workload": f"KosmosLanguage generate, B={B}, prefix {a.prefix}, {a.new} new tokens, {a.precision}, "
+                           "top_k=50 top_p=0.9 temperature=0.8", "prefill_ms": round(pre * 1e3, 3)}
+        for name, fn, arg in (("a", run_a, tok), ("b", run_b, tok), ("c", run_c, tok_all)):
+            if name in a.only:
+                res[{"a": "a_generate_fused_ms_per_token", "b": "b_torch_sampler_ms_per_token",
+                     "c": "c_bare_decode_step_ms_per_token"}[name]] = round((timed(fn, arg) - pre) / (a.new - 1) * 1e3, 4)
+        # launches per token, counted by the library's own per-launch records: generate(3 tokens) - generate(2 tokens) is one
+        # decode step + its embedding + the sampler; the bare step is one more call of the public incremental path
+        counts = []
+        for n_new in (2, 3):
+            _hip.prof_enable(True)
+            m.generate(tok, n_new, **KW)
+            torch.cuda.synchronize()
+            counts.append(len(_hip.prof_collect()))
+        state = {"max_len": a.prefix + a.new}
+        m(tok, incremental_state=state)
+        torch.cuda.synchronize()
+        _hip.prof_enable(True)
+        m(tok_all[:, : a.prefix + 1], incremental_state=state)
+        torch.cuda.synchronize()
+        bare = len(_hip.prof_collect())
+        _hip.prof_enable(False)
+        res["launches_per_generated_token"], res["launches_per_bare_step"] = counts[1] - counts[0], bare
+        print(json.dumps(res), flush=True)
