@@ -545,6 +545,53 @@ int kx_attention_decode(const void* qkv, void* kcache, void* vcache, void* out, 
                         int64_t B, int64_t H, int64_t t, int64_t Tmax, int32_t prec, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged batches: every sequence at its own position, held ON THE DEVICE (added within ABI 7: functions only, no struct and
+ * no existing signature changes, so kx_version() stays 7).
+ *
+ * positions [B] int32 (device): positions[b] = the number of tokens sequence b has in the cache = the absolute position of
+ * the token its next step appends.  A step's launch arguments are then the same for every token: what changes from one
+ * token to the next is device memory only (kx_sample_logits_ragged advances the array).
+ *
+ * Positions cannot be validated by the host per step, so the kernels check them: a row whose position is outside the cache
+ * or the tables reads and writes nothing for that row and ORs a bit into the sticky *error_word (int32, device, zeroed by
+ * the caller once; read it whenever the host synchronises anyway — kosmosx.generation: at the stop poll and after the loop).
+ *
+ * kx_attention_decode_ragged: kx_attention_decode with t = positions[b] per sequence; appends the new k / v to cache row
+ *   positions[b].  Same slots, key order and arithmetic: where all positions equal t, the bits of kx_attention_decode at t.
+ * kx_step_prepare: the start of a ragged step, one launch.  Per sequence b with t = positions[b]:
+ *   x[b] = embed[tokens[b]] + pos[2 + t]                           (pos_shift == 0; kx_embed_step(pos_a = t, pos_b = -1))
+ *   x[b] = embed[tokens[b]] + pos[2 + t - pos_shift] + pos[2 + t]  (pos_shift  > 0; kx_embed_step(t - pos_shift, t))
+ *   with kx_embed_step's order of additions, and xpos_rows[k][b][0:32] = row t of table k (k = 0..3: xq_cs, xq_ss, xk_cs,
+ *   xk_ss, each [xpos_len, 32] fp32) — the [B, 32] tables a qkv GEMM over the M = B rows of the step reads with xpos_T = B.
+ *   The four tables and xpos_rows [4, B, 32] may all be NULL (no XPos).  KX_RAGGED_ERR_TABLE: t < pos_shift, t + 2 >= max_pos
+ *   or t >= xpos_len; that row of x and of xpos_rows is not written, so the caller initialises both buffers once (zeros):
+ *   what a rejected row then computes until the error word is read is finite and deterministic.
+ * kx_sample_logits_ragged: kx_sample_logits with the Philox position of row b = positions[b] + advance (args->position is
+ *   ignored).  advance != 0: one lane of the row's workgroup stores that value back after the draw, finished rows included —
+ *   so the first call after a prefill runs with advance = 0 and every later one with advance = 1, and no other launch or
+ *   host scalar moves the positions.  Everything else as kx_sample_logits.
+ * kx_decoder_decode_step_ragged: kx_step_prepare + kx_decoder_decode_step with per-sequence positions.  tokens [B] int64
+ *   (device), embed [vocab, dim], pos [max_pos, dim]; x [B, 1, dim] fp32 scratch (the step's residual stream); xq_*, xk_*
+ *   the FULL [Tmax, 32] tables (one centring, as for the prefill); xpos_rows [4, B, 32] fp32 scratch.  x and xpos_rows
+ *   are zeroed by the caller before the first step (see kx_step_prepare).  Both step paths
+ *   (weight streaming up to 16 sequences, tile GEMMs above) run their qkv launch with xpos_T = B on xpos_rows. */
+typedef enum { KX_RAGGED_ERR_TABLE = 1, KX_RAGGED_ERR_CACHE = 2 } kx_ragged_error;
+int kx_attention_decode_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                               int64_t B, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
+                               int32_t* error_word, void* stream);
+int kx_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
+                    const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
+                    float* xpos_rows, int64_t B, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
+                    int64_t xpos_len, int32_t* error_word, void* stream);
+int kx_sample_logits_ragged(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream);
+int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                  int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t B,
+                                  const int32_t* positions, const float* xq_cs, const float* xq_ss, const float* xk_cs,
+                                  const float* xk_ss, float* xpos_rows, void* kcache, void* vcache, int64_t Tmax,
+                                  void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
+                                  int32_t* error_word, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before
  * Kosmos.forward, on the device.  Integer / byte work; results are bit-identical to the HF processor.
  * ------------------------------------------------------------------------------------------ */

@@ -1140,6 +1140,9 @@ struct DecodeParams {
   float* stats_out;                          // [B, H, 2] or null
   int H, D, t;                               // t = number of tokens already cached (the new one goes to row t)
 };
+// the ragged form: t = positions[b] instead of DecodeParams.t, checked against Tmax in the kernel (err: the sticky error word)
+struct RaggedParams { const int* positions; int* err; int Tmax; };
+template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
 
 template <typename T> struct Ld4;
 template <> struct Ld4<bf16_t> {
@@ -1161,33 +1164,50 @@ template <> struct Ld4<float> {
 // qkv row itself, not back through the cache — are all requested before anything is waited for; the cache append is a
 // side store nobody in this launch reads.  (First version: append, barrier, q, then the keys in rounds of 128 — four to
 // five dependent round trips, 9.9 us per launch for 150 keys.)  Same slots, same key order per slot, same arithmetic.
-template <typename T>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p) {
+// RAGGED: every sequence has its own number of cached keys, positions[b] in device memory — one scalar load per workgroup,
+// requested first; q, the first round of keys and the new k / v go out together once it is there (a position cannot be
+// prefetched past: it decides every address).  Everything after that is the same code on `t`, so a batch of equal positions
+// gives the bits of the uniform launch.  A position outside the cache is the caller's error: the workgroup writes nothing
+// (no cache row, no output) and sets KX_RAGGED_ERR_CACHE in the sticky error word.
+// The ragged launch passes one more kernel argument (R = RaggedParams); the uniform launch has an empty pack, i.e. the signature
+// and kernel-argument layout it always had.
+template <typename T, typename... R>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, const R... r) {
+  constexpr bool RAGGED = sizeof...(R) != 0;
   __shared__ float sm_m[16], sm_l[16], sm_o[16][64];
   typedef typename Ld4<T>::raw raw;
   constexpr int UK = Ld4<T>::UK;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = lane >> 4, li = lane & 15;              // 16-lane group = one key at a time; lane = dims 4li..4li+3
   const int h = blockIdx.x, b = blockIdx.y;
+  int t = p.t;
+  if constexpr (RAGGED) {
+    const RaggedParams& rp = first_arg(r...);
+    t = rp.positions[b];
+    if (t < 0 || t >= rp.Tmax) {                            // (uniform over the workgroup: nobody reaches a barrier)
+      if (tid == 0) atomicOr(rp.err, KX_RAGGED_ERR_CACHE);
+      return;
+    }
+  }
   const long long es = sizeof(T);
   const char* qrow = p.qkv + ((long long)b * p.qkv_row + (long long)h * 64 + 4 * li) * es;
   char* kc = p.kcache + ((long long)b * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
   char* vc = p.vcache + ((long long)b * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
   const char* knew = qrow + (long long)p.D * es;          // the new token (key t): k | v of the qkv row
   const char* vnew = qrow + 2ll * p.D * es;
-  const int nkeys = p.t + 1;
+  const int nkeys = t + 1;
   const int slot = wave * 4 + grp;
   const raw qr = *reinterpret_cast<const raw*>(qrow);
   raw kr[UK], vr[UK];
 #pragma unroll
   for (int u = 0; u < UK; ++u) {                           // (slots past the end re-read the last key and drop it)
-    const int j = min(slot + 16 * u, p.t);
-    kr[u] = *reinterpret_cast<const raw*>(j == p.t ? knew : kc + (long long)j * p.cache_row * es);
-    vr[u] = *reinterpret_cast<const raw*>(j == p.t ? vnew : vc + (long long)j * p.cache_row * es);
+    const int j = min(slot + 16 * u, t);
+    kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
+    vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
   }
   if (wave == 0 && grp < 2) {                              // append row t: 64 k + 64 v elements per head
     const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
-    *reinterpret_cast<raw*>((grp == 0 ? kc : vc) + (long long)p.t * p.cache_row * es) = nv;
+    *reinterpret_cast<raw*>((grp == 0 ? kc : vc) + (long long)t * p.cache_row * es) = nv;
   }
   float q[4];
   Ld4<T>::unpack(qr, q);
@@ -1196,9 +1216,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p) 
     if (j0 != slot) {                                      // contexts beyond the first round: one more round trip each
 #pragma unroll
       for (int u = 0; u < UK; ++u) {
-        const int j = min(j0 + 16 * u, p.t);
-        kr[u] = *reinterpret_cast<const raw*>(j == p.t ? knew : kc + (long long)j * p.cache_row * es);
-        vr[u] = *reinterpret_cast<const raw*>(j == p.t ? vnew : vc + (long long)j * p.cache_row * es);
+        const int j = min(j0 + 16 * u, t);
+        kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
+        vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
       }
     }
 #pragma unroll
@@ -1296,15 +1316,17 @@ int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t
   return KX_OK;
 }
 
-extern "C" int kx_attention_decode(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
-                                   int64_t B, int64_t H, int64_t t, int64_t Tmax, int32_t prec, void* stream) {
-  KX_REQUIRE(qkv && kcache && vcache && out, "kx_attention_decode: null pointer");
-  KX_REQUIRE(B > 0 && H > 0 && t >= 0 && t < Tmax, "kx_attention_decode: position %lld outside the cache of %lld rows",
+// positions == nullptr: the uniform launch at host position t; else the ragged launch (t unused)
+static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, void* vcache, void* out, int32_t odt,
+                                 float* stats_out, int64_t B, int64_t H, int64_t t, const int32_t* positions, int32_t* err,
+                                 int64_t Tmax, int32_t prec, void* stream) {
+  KX_REQUIRE(qkv && kcache && vcache && out, "%s: null pointer", fn);
+  KX_REQUIRE(B > 0 && H > 0 && t >= 0 && t < Tmax, "%s: position %lld outside the cache of %lld rows", fn,
              (long long)t, (long long)Tmax);
-  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "kx_attention_decode: bad precision");
+  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "%s: bad precision", fn);
   KX_REQUIRE((odt == KX_F16C) == (prec == KX_PREC_F16C) || odt == KX_F32,
-             "kx_attention_decode: KX_PREC_F16C (fp32 q / cache, exact softmax) writes KX_F16C rows or fp32");
-  KX_REQUIRE(B < 65536 && H < 65536, "kx_attention_decode: B/H exceed the grid limits");
+             "%s: KX_PREC_F16C (fp32 q / cache, exact softmax) writes KX_F16C rows or fp32", fn);
+  KX_REQUIRE(B < 65536 && H < 65536, "%s: B/H exceed the grid limits", fn);
   DecodeParams p;
   const int64_t D = H * 64;
   p.qkv = (const char*)qkv; p.qkv_row = 3 * D;
@@ -1313,14 +1335,36 @@ extern "C" int kx_attention_decode(const void* qkv, void* kcache, void* vcache, 
   const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;
   p.kcache = (char*)kcache; p.vcache = (char*)vcache; p.cache_batch = Tmax * D;
   p.cache_head = head_major ? Tmax * 64 : 64; p.cache_row = head_major ? 64 : D;
-  KX_REQUIRE(odt != KX_F16P || (prec == KX_PREC_F32 && ((uintptr_t)out & 15) == 0), "kx_attention_decode: KX_F16P rows come from the fp32 step, 16-byte aligned");
+  KX_REQUIRE(odt != KX_F16P || (prec == KX_PREC_F32 && ((uintptr_t)out & 15) == 0), "%s: KX_F16P rows come from the fp32 step, 16-byte aligned", fn);
   p.out = out; p.out_row = odt == KX_F16C ? 2 * D : D; p.o_bf16 = odt == KX_BF16; p.o_f16c = odt == KX_F16C; p.stats_out = stats_out;
   p.o_pieces = odt == KX_F16P;
   p.H = (int)H; p.D = (int)D; p.t = (int)t;
+  const RaggedParams r{positions, err, (int)Tmax};
   hipStream_t s = (hipStream_t)stream;
-  KxProfScope prof(prec == KX_PREC_BF16 ? KX_K_ATTN_BF16 : KX_K_ATTN_F32, B * H, 1, t + 1, s);
-  if (prec == KX_PREC_BF16) hipLaunchKernelGGL(attn_decode_kernel<bf16_t>, dim3((unsigned)H, (unsigned)B), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(attn_decode_kernel<float>, dim3((unsigned)H, (unsigned)B), dim3(256), 0, s, p);
-  KX_CHECK_LAUNCH("kx_attention_decode");
+  KxProfScope prof(prec == KX_PREC_BF16 ? KX_K_ATTN_BF16 : KX_K_ATTN_F32, B * H, 1, positions ? Tmax : t + 1, s);
+  const dim3 grid((unsigned)H, (unsigned)B);
+  if (positions) {
+    if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams>), grid, dim3(256), 0, s, p, r);
+    else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams>), grid, dim3(256), 0, s, p, r);
+  } else {
+    if (prec == KX_PREC_BF16) hipLaunchKernelGGL(attn_decode_kernel<bf16_t>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(attn_decode_kernel<float>, grid, dim3(256), 0, s, p);
+  }
+  KX_CHECK_LAUNCH(fn);
   return KX_OK;
+}
+
+extern "C" int kx_attention_decode(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                                   int64_t B, int64_t H, int64_t t, int64_t Tmax, int32_t prec, void* stream) {
+  return attention_decode_impl("kx_attention_decode", qkv, kcache, vcache, out, odt, stats_out, B, H, t, nullptr, nullptr, Tmax,
+                               prec, stream);
+}
+
+extern "C" int kx_attention_decode_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                                          int64_t B, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
+                                          int32_t* error_word, void* stream) {
+  KX_REQUIRE(positions && error_word, "kx_attention_decode_ragged: null positions / error_word");
+  KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll, "kx_attention_decode_ragged: Tmax=%lld outside the 32-bit positions", (long long)Tmax);
+  return attention_decode_impl("kx_attention_decode_ragged", qkv, kcache, vcache, out, odt, stats_out, B, H, 0, positions, error_word,
+                               Tmax, prec, stream);
 }

@@ -685,25 +685,28 @@ extern "C" int kx_decoder_prefill(const kx_decoder_weights* w, float* x, int64_t
                               stream, kcache, vcache, Tmax);
 }
 
-extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const float* xq_cs,
-                                      const float* xq_ss, const float* xk_cs, const float* xk_ss, void* kcache,
-                                      void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
-                                      size_t workspace_bytes, int32_t prec, void* stream) {
+// positions == nullptr: every sequence at host position t, xq_* / xk_* = row t of the tables (xpos_T = 1).  Else the ragged
+// step: sequence b at positions[b] (device), xq_* / xk_* = [B, 32] tables holding each sequence's row (xpos_T = B).
+static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const int32_t* positions,
+                            int32_t* error_word, const float* xq_cs, const float* xq_ss, const float* xk_cs,
+                            const float* xk_ss, void* kcache, void* vcache, int64_t Tmax, void* logits, int32_t ldt,
+                            void* workspace, size_t workspace_bytes, int32_t prec, void* stream) {
+  const int64_t xT = positions ? B : 1;
   const int tfmt = prec == KX_PREC_F32W24 ? 2 : prec == KX_PREC_F32W16 ? 3 : 1;   // what the streaming copies (w*_t) hold
   if (prec == KX_PREC_F32W24 || prec == KX_PREC_F32W16) prec = KX_PREC_F32;
-  KX_REQUIRE(w && x && logits && workspace && kcache && vcache, "kx_decoder_decode_step: null pointer");
+  KX_REQUIRE(w && x && logits && workspace && kcache && vcache, "%s: null pointer", fn);
   KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_decode_step");
   KX_REQUIRE(prec != KX_PREC_BF16X3 && prec != KX_PREC_F16,
-             "kx_decoder_decode_step: incremental decoding is offered in bf16, fp32 and f16c (fp32 cache)");
-  KX_REQUIRE(B > 0 && t >= 0 && t < Tmax, "kx_decoder_decode_step: position %lld outside the cache of %lld rows",
+             "%s: incremental decoding is offered in bf16, fp32 and f16c (fp32 cache)", fn);
+  KX_REQUIRE(B > 0 && t >= 0 && t < Tmax, "%s: position %lld outside the cache of %lld rows", fn,
              (long long)t, (long long)Tmax);
-  KX_REQUIRE(w->dim == w->heads * 64, "kx_decoder_decode_step: head_dim must be 64");
-  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss), "kx_decoder_decode_step: XPos rows for position t missing");
-  KX_REQUIRE(((uintptr_t)workspace & 255) == 0, "kx_decoder_decode_step: workspace must be 256-byte aligned");
+  KX_REQUIRE(w->dim == w->heads * 64, "%s: head_dim must be 64", fn);
+  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss), "%s: XPos rows for position t missing", fn);
+  KX_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   const DecBufs d = dec_plan(w, B, 1, prec, (char*)workspace);
   if (d.total > workspace_bytes) {
-    kx_set_error("kx_decoder_decode_step: workspace %zu < required %zu", workspace_bytes, d.total);
+    kx_set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, d.total);
     return KX_ERR_WORKSPACE;
   }
   const int64_t M = B, D = w->dim, F = w->ffn;
@@ -732,10 +735,10 @@ extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int
     // the compressed plane formats ARE the weights of such a step: a layer without its streaming copies would make gemv16 fall
     // back to the row-major operand while its producers already wrote KX_F16P rows (garbage logits, no error)
     if (tfmt >= 2) {
-      KX_REQUIRE(w->wout_t, "kx_decoder_decode_step: KX_PREC_F32W24 / KX_PREC_F32W16 need the streaming copy wout_t");
+      KX_REQUIRE(w->wout_t, "%s: KX_PREC_F32W24 / KX_PREC_F32W16 need the streaming copy wout_t", fn);
       for (int i = 0; i < w->layers; ++i)
         KX_REQUIRE(w->layer[i].wqkv_t && w->layer[i].wo_t && w->layer[i].w1_t && w->layer[i].w2_t,
-                   "kx_decoder_decode_step: KX_PREC_F32W24 / KX_PREC_F32W16 need wqkv_t / wo_t / w1_t / w2_t of layer %d", i);
+                   "%s: KX_PREC_F32W24 / KX_PREC_F32W16 need wqkv_t / wo_t / w1_t / w2_t of layer %d", fn, i);
     }
     const int gv = kx_tuning_get(KX_TUNE_GEMV_VARIANT);
     const bool pieces = tfmt == 3 && M >= 3 && gv != 1 && gv != 4 && gv != 5 && gv < 10 && kx_tuning_get(KX_TUNE_DECODE_PIECES) != 1;
@@ -744,11 +747,16 @@ extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int
       const kx_decoder_layer& L = w->layer[i];
       Gemv16 q{pa, D, L.wqkv, D, d.qkv, 3 * D, ct, M, 3 * D};
       q.bias = L.bqkv; q.qscale = 0.125f; q.qcols = D; q.ln_g = L.sa_g; q.ln_b = L.sa_b; q.eps = w->eps; q.a_add = pb;
-      if (w->xpos) { q.xq_cs = xq_cs; q.xq_ss = xq_ss; q.xk_cs = xk_cs; q.xk_ss = xk_ss; q.xT = 1; q.xdim = D; }
+      if (w->xpos) { q.xq_cs = xq_cs; q.xq_ss = xq_ss; q.xk_cs = xk_cs; q.xk_ss = xk_ss; q.xT = xT; q.xdim = D; }
       q.W_tiled = L.wqkv_t; q.tiled_fmt = tfmt; q.prec = prec;
       KX_TRY(gemv16(q, s));
-      KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, pieces ? KX_F16P : ct,
-                                 w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
+      if (positions)
+        KX_TRY(kx_attention_decode_ragged(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
+                                          pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B, w->heads, positions, Tmax, prec,
+                                          error_word, stream));
+      else
+        KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, pieces ? KX_F16P : ct,
+                                   w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
       float *qa = pair ? d.ya : pa, *qb = pair ? d.yb : nullptr;   // what out_proj writes
       Gemv16 o{d.att, D, L.wo, D, qa, D, KX_F32, M, D};
       o.bias = L.bo; o.residual = pa; o.residual2 = pb; o.eps = w->eps;
@@ -777,12 +785,16 @@ extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int
   for (int i = 0; i < w->layers; ++i) {
     const kx_decoder_layer& L = w->layer[i];
     KX_TRY(ln(x, nullptr, L.sa_g, L.sa_b, d.h, ct, M, D, w->eps, s));
-    // XPos rows of absolute position t (xpos_T = 1: every batch row is the same position)
+    // XPos rows of absolute position t (xpos_T = 1: every batch row is the same position; ragged: xpos_T = B, row m its own)
     KX_FAM(0);
     KX_TRY(gemm(d.h, D, L.wqkv, D, d.qkv, 3 * D, qdt(prec), M, 3 * D, L.bqkv, nullptr, 0, 0.125f, D, prec, s,
-                w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? 1 : 0, w->xpos ? D : 0));
-    KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                               w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
+                w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? xT : 0, w->xpos ? D : 0));
+    if (positions)
+      KX_TRY(kx_attention_decode_ragged(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
+                                        w->subln ? d.partials : nullptr, B, w->heads, positions, Tmax, prec, error_word, stream));
+    else
+      KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
+                                 w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
     if (w->subln) {
       KX_TRY(kx_row_stats_finalize(d.partials, M, w->heads, 64, w->eps, d.stats, stream));
       KX_FAM(1);
@@ -812,4 +824,32 @@ extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int
   KX_FAM(4);
   KX_TRY(gemm(d.h, D, w->wout, D, logits, w->vocab, ldt, M, w->vocab, nullptr, nullptr, 0, 1.f, 0, prec, s));
   return KX_OK;
+}
+
+extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const float* xq_cs,
+                                      const float* xq_ss, const float* xk_cs, const float* xk_ss, void* kcache,
+                                      void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
+                                      size_t workspace_bytes, int32_t prec, void* stream) {
+  return decode_step_impl("kx_decoder_decode_step", w, x, B, t, nullptr, nullptr, xq_cs, xq_ss, xk_cs, xk_ss, kcache, vcache, Tmax, logits, ldt, workspace,
+                          workspace_bytes, prec, stream);
+}
+
+extern "C" int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const int64_t* tokens, const float* embed,
+                                             const float* pos, int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x,
+                                             int64_t B, const int32_t* positions, const float* xq_cs, const float* xq_ss,
+                                             const float* xk_cs, const float* xk_ss, float* xpos_rows, void* kcache,
+                                             void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
+                                             size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
+  KX_REQUIRE(w && positions && error_word, "kx_decoder_decode_step_ragged: null pointer");
+  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_decode_step_ragged");
+  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
+             "kx_decoder_decode_step_ragged: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
+  KX_REQUIRE(B > 0 && Tmax > 0, "kx_decoder_decode_step_ragged: empty batch / cache");
+  const bool xp = w->xpos != 0;
+  KX_TRY(kx_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
+                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, B, w->dim, vocab, max_pos, pos_shift, Tmax,
+                         error_word, stream));
+  const float* r = xp ? xpos_rows : nullptr;
+  return decode_step_impl("kx_decoder_decode_step_ragged", w, x, B, 0, positions, error_word, r, r ? r + B * 32 : nullptr, r ? r + 2 * B * 32 : nullptr,
+                          r ? r + 3 * B * 32 : nullptr, kcache, vcache, Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
 }

@@ -89,7 +89,9 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
 //   MASS = true : weight = mass_fix       -> K = the smallest value whose strictly-greater mass is still below target.
 // Three histogram passes fix the key's digits from the top; `carry` is the weight strictly above the chosen bin.
 // Returns false (key untouched) when the whole weight stays below target.
-template <bool MASS>
+// (OWNER: one instantiation per kernel that calls it, so that each stays a single-caller function the compiler folds into its
+// kernel exactly as it did when there was one kernel)
+template <bool MASS, bool OWNER>
 __device__ bool radix_select(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, float m,
                              unsigned limit, unsigned long long target, unsigned long long* hist,
                              unsigned long long* gsum, unsigned long long* sel, unsigned& key_out) {
@@ -162,7 +164,16 @@ __device__ bool radix_select(const SampleParams& a, const float* __restrict__ ro
   return true;
 }
 
-__global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a) {
+// RAGGED: the Philox position of row b is positions[b] + advance (device memory, one word per row) instead of a.position, and
+// with advance != 0 thread 0 stores it back after the draw — the same launch moves the row on.  Nothing else differs.
+// The ragged launch passes one more kernel argument (R = RaggedPos); the uniform launch has an empty pack, i.e. the signature and
+// kernel-argument layout it always had.
+struct RaggedPos { int* positions; int advance; };
+template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
+
+template <typename... R>
+__global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const R... r) {
+  constexpr bool RAGGED = sizeof...(R) != 0;
   __shared__ unsigned long long hist[BINS];
   __shared__ unsigned long long red[SW];
   __shared__ unsigned long long gsum[BINS / 64];
@@ -216,7 +227,7 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a) {
       unsigned tau = KEY_MIN_VALID;
       if (a.k > 0 && a.k < a.V) {
         unsigned kk;
-        if (radix_select<false>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
+        if (radix_select<false, RAGGED>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
       }
       if (a.p < 1.0f) {
         unsigned long long z = 0;                     // mass of what top-k kept
@@ -229,11 +240,14 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a) {
         // keep iff (mass strictly above) < p Z; the masses are integers, so "< p Z" is "< ceil(p Z)"
         const unsigned long long target = (unsigned long long)ceil((double)a.p * (double)z);
         unsigned kp;
-        if (radix_select<true>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
+        if (radix_select<true, RAGGED>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
       }
       // Gumbel arg max over the kept set {key >= tau}; Philox block `base / 4` serves elements base .. base + 3, so here
       // (and only here) a thread owns four consecutive elements
-      const unsigned long long ctr = ((unsigned long long)(unsigned)(a.seq ? a.seq[b] : b) << 32) | a.position;
+      // (RAGGED: thread 0 stores the advanced position below, behind the barriers of the two reductions that follow this read)
+      unsigned position = a.position;
+      if constexpr (RAGGED) position = (unsigned)(first_arg(r...).positions[b] + first_arg(r...).advance);
+      const unsigned long long ctr = ((unsigned long long)(unsigned)(a.seq ? a.seq[b] : b) << 32) | position;
       unsigned long long gbest = 0, c = 0;
       for (int base = tid * 4; base < a.V; base += SB * 4) {
         float xs[4];
@@ -277,6 +291,45 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a) {
     if (a.history) a.history[b * a.hist_ld + a.hist_len] = tok;
     if (a.finished && fin) a.finished[b] = 1;
     if (a.kept_count) a.kept_count[b] = kept;
+    if constexpr (RAGGED) {
+      const RaggedPos& rp = first_arg(r...);
+      if (rp.advance) rp.positions[b] = rp.positions[b] + rp.advance;
+    }
+  }
+}
+
+// The start of a ragged decode step: embed_step_kernel with the row's own position rows, read from positions[b], and the
+// gather of the row's four XPos table rows into [B, 32] tables (see kx_step_prepare in include/kosmosx_hip.h).
+__global__ __launch_bounds__(256) void step_prepare_kernel(const long long* __restrict__ tokens, const float* __restrict__ embed,
+                                                           const float* __restrict__ pos, const int* __restrict__ positions,
+                                                           const float* __restrict__ t0, const float* __restrict__ t1,
+                                                           const float* __restrict__ t2, const float* __restrict__ t3,
+                                                           float* __restrict__ out, float* __restrict__ xrows, int B, int d,
+                                                           long long vocab, long long max_pos, int pos_shift, long long xpos_len,
+                                                           int* err) {
+  const long long b = blockIdx.x;
+  const long long t = positions[b];
+  if (t < pos_shift || t + 2 >= max_pos || (xrows && t >= xpos_len)) {   // the caller's error: nothing of this row is read or written
+    if (threadIdx.x == 0) atomicOr(err, KX_RAGGED_ERR_TABLE);
+    return;
+  }
+  long long id = tokens[b];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);   // memory safety only
+  const float4* src = reinterpret_cast<const float4*>(embed + id * d);
+  const float4* pa = reinterpret_cast<const float4*>(pos + (2 + t - pos_shift) * d);
+  const float4* pb = pos_shift ? reinterpret_cast<const float4*>(pos + (2 + t) * d) : nullptr;
+  float4* o = reinterpret_cast<float4*>(out + b * d);
+  for (int c = threadIdx.x; c < (d >> 2); c += 256) {
+    float4 v = src[c];
+    const float4 a1 = pa[c];
+    v.x += a1.x; v.y += a1.y; v.z += a1.z; v.w += a1.w;
+    if (pb) { const float4 a2 = pb[c]; v.x += a2.x; v.y += a2.y; v.z += a2.z; v.w += a2.w; }
+    o[c] = v;
+  }
+  if (xrows && threadIdx.x < 128) {                   // 4 tables x 32 values
+    const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
+    const float* tb = k == 0 ? t0 : k == 1 ? t1 : k == 2 ? t2 : t3;
+    xrows[((long long)k * B + b) * 32 + j] = tb[t * 32 + j];
   }
 }
 
@@ -303,7 +356,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const long long* __rest
 
 }  // namespace
 
-extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) {
+static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream) {
   KX_REQUIRE(args != nullptr, "kx_sample_logits: null args");
   KX_REQUIRE(args->struct_bytes == sizeof(kx_sample_args),
              "kx_sample_logits: stale binding — caller declares kx_sample_args as %u bytes, this library (ABI %d) as %zu",
@@ -324,7 +377,7 @@ extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) {
              (long long)args->hist_len);
   KX_REQUIRE(args->out_tokens == nullptr || (args->out_col >= 0 && args->out_col < args->out_ld),
              "kx_sample_logits: out_col=%lld outside [0, out_ld=%lld)", (long long)args->out_col, (long long)args->out_ld);
-  KX_REQUIRE(args->position >= 0 && args->position <= 0xffffffffll, "kx_sample_logits: position=%lld outside [0, 2^32)",
+  KX_REQUIRE(positions || (args->position >= 0 && args->position <= 0xffffffffll), "kx_sample_logits: position=%lld outside [0, 2^32)",
              (long long)args->position);
   if (args->V > KX_SAMPLE_MAX_V) {
     kx_set_error("kx_sample_logits: V=%lld exceeds %lld (64-bit fixed-point mass)", (long long)args->V, KX_SAMPLE_MAX_V);
@@ -340,7 +393,7 @@ extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) {
                  (long long)args->V, KX_SAMPLE_MAX_V_PENALTY);
     return KX_ERR_UNSUPPORTED;
   }
-  p.seed = args->seed; p.position = (unsigned)args->position;
+  p.seed = args->seed; p.position = positions ? 0u : (unsigned)args->position;
   p.seq = (const long long*)args->sequence_ids;
   p.history = (long long*)args->history; p.hist_ld = args->hist_ld; p.hist_len = (int)args->hist_len;
   p.finished = args->finished; p.eos = args->eos_id; p.pad = args->pad_id;
@@ -349,8 +402,39 @@ extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) {
   p.kept_count = args->kept_count; p.keep_mask = args->keep_mask;
   const size_t lds = p.pen ? (size_t)((args->V + 31) / 32) * 4 : 0;
   KxProfScope prof(KX_K_MISC, args->B, args->V, 0, (hipStream_t)stream);
-  hipLaunchKernelGGL(sample_kernel, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p);
+  if (positions) hipLaunchKernelGGL(sample_kernel<RaggedPos>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+                                    RaggedPos{(int*)positions, (int)advance});
+  else hipLaunchKernelGGL(sample_kernel<>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p);
   KX_CHECK_LAUNCH("kx_sample_logits");
+  return KX_OK;
+}
+
+extern "C" int kx_sample_logits(const kx_sample_args* args, void* stream) { return sample_impl(args, nullptr, 0, stream); }
+
+extern "C" int kx_sample_logits_ragged(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream) {
+  KX_REQUIRE(positions != nullptr, "kx_sample_logits_ragged: null positions");
+  KX_REQUIRE(advance >= 0 && advance <= 0x7fffffffll, "kx_sample_logits_ragged: advance=%lld must be >= 0", (long long)advance);
+  return sample_impl(args, positions, advance, stream);
+}
+
+extern "C" int kx_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
+                               const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
+                               float* xpos_rows, int64_t B, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
+                               int64_t xpos_len, int32_t* error_word, void* stream) {
+  KX_REQUIRE(tokens && embed && pos && positions && x && error_word, "kx_step_prepare: null pointer");
+  KX_REQUIRE(B > 0 && B <= 0x7fffffffll && d > 0 && d % 4 == 0 && d <= 0x7fffffffll && vocab > 0,
+             "kx_step_prepare: bad shape B=%lld d=%lld vocab=%lld", (long long)B, (long long)d, (long long)vocab);
+  KX_REQUIRE((((uintptr_t)embed | (uintptr_t)pos | (uintptr_t)x) & 15) == 0, "kx_step_prepare: pointers must be 16-byte aligned");
+  KX_REQUIRE(max_pos > 2 && pos_shift >= 0 && pos_shift <= 0x7fffffffll, "kx_step_prepare: bad max_pos=%lld / pos_shift=%lld",
+             (long long)max_pos, (long long)pos_shift);
+  const bool tabs = xq_cs || xq_ss || xk_cs || xk_ss || xpos_rows;
+  KX_REQUIRE(!tabs || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows && xpos_len > 0),
+             "kx_step_prepare: the four XPos tables, xpos_rows and xpos_len > 0 are given together or not at all");
+  KxProfScope prof(KX_K_EMBED, B, d, 1, (hipStream_t)stream);
+  hipLaunchKernelGGL(step_prepare_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const long long*)tokens, embed,
+                     pos, (const int*)positions, xq_cs, xq_ss, xk_cs, xk_ss, x, xpos_rows, (int)B, (int)d, (long long)vocab,
+                     (long long)max_pos, (int)pos_shift, (long long)xpos_len, (int*)error_word);
+  KX_CHECK_LAUNCH("kx_step_prepare");
   return KX_OK;
 }
 

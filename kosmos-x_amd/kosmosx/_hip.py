@@ -19,6 +19,7 @@ KX_PREC_BF16, KX_PREC_F32, KX_PREC_BF16X3, KX_PREC_F16C, KX_PREC_F16, KX_PREC_F3
 KX_F32, KX_BF16, KX_BF16X3, KX_F16C, KX_F16, KX_F16P, KX_F16HL = 0, 1, 2, 3, 4, 5, 6
 KX_ACT_NONE, KX_ACT_GELU, KX_ACT_QUICK_GELU = 0, 1, 2
 KX_ATTN_FULL, KX_ATTN_CAUSAL = 0, 1
+KX_RAGGED_ERR_TABLE, KX_RAGGED_ERR_CACHE = 1, 2
 KX_ACT_RELU, KX_ACT_SWISH = 5, 6
 ACTS = {"none": KX_ACT_NONE, "gelu": KX_ACT_GELU, "quick_gelu": KX_ACT_QUICK_GELU, "relu": KX_ACT_RELU, "swish": KX_ACT_SWISH}
 PRECS = {"bf16": KX_PREC_BF16, "fp32": KX_PREC_F32, "bf16x3": KX_PREC_BF16X3, "f16c": KX_PREC_F16C, "f16": KX_PREC_F16}
@@ -177,6 +178,11 @@ SYMBOLS = {
     "kx_decoder_decode_step": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, i32,
                                          vp, C.c_size_t, i32, vp]),
     "kx_attention_decode": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, i64, i32, vp]),
+    "kx_attention_decode_ragged": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, i32, vp, vp]),
+    "kx_step_prepare": (C.c_int, [vp] * 10 + [i64] * 6 + [vp, vp]),
+    "kx_sample_logits_ragged": (C.c_int, [C.POINTER(SampleArgs), vp, i64, vp]),
+    "kx_decoder_decode_step_ragged": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp,
+                                                vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),
     "kx_decoder_forward": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, i32, vp,
                                      C.c_size_t, i32, vp]),
     "kx_clip_preprocess_workspace_bytes": (C.c_size_t, [i64, i32, i32]),

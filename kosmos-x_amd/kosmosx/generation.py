@@ -4,23 +4,32 @@ The loop stays on the device: kx_sample_logits reads the logits row a step has j
 device memory, kx_embed_step gathers its embedding for the next step.  The host only enqueues; its one read is the stop
 poll, every ``eos_poll`` steps and only when an ``eos_token_id`` is given.
 
-Not offered: ragged prompts / padding masks, beam search, compaction of finished rows, replaying the step
-as a captured graph.
+Ragged batches (``prompt_lengths``): every row has its own position, an int32 word in device memory that the sampler
+advances (kx_sample_logits_ragged) and the decode step reads (kx_decoder_decode_step_ragged) — a step's launch arguments are
+then the same for every token.  Each row generates what it would generate alone.
+
+Not offered: beam search, compaction of finished rows, replaying the step as a captured graph, padding masks
+in ``Decoder.forward`` (``self_attn_padding_mask``).
 """
 from __future__ import annotations
 
+import operator
+
 import torch
 
+from . import _hip as H
 from . import ops
 
 
 def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
-                  seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False):
+                  seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_tokens`` [B, Tt] int64: what the repetition penalty sees before the first new token.  ``pos_shift`` > 0: the
     prompt holds that many spliced rows that are not tokens and text rows carry two position rows (the multimodal prompt
-    under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t]."""
+    under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t].
+    ``lengths`` (host ints, validated by resolve_prompt_lengths): the ragged batch — row b's sequence has lengths[b] <= T
+    positions (spliced rows included), the rest of its prompt is right padding whose ids mask_padding replaced."""
     B, T, V = logits.shape
     dev = logits.device
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
@@ -34,23 +43,53 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     if sequence_ids is not None:
         sequence_ids = sequence_ids.to(device=dev, dtype=torch.int64).contiguous()
     kept = []
-    row = logits[:, -1]                                                   # [B, V] view, row stride T * V
+    positions = None
+    if lengths is not None:
+        # Row b's first token comes from logits[b, lengths[b] - 1]; from here on its position lives on the device.  The padded
+        # history slots already hold the row's own first prompt token (mask_padding): the penalty is applied once per distinct
+        # id, so the duplicates change nothing and every row keeps the common hist_len.
+        last = torch.tensor([l - 1 for l in lengths], dtype=torch.int64, device=dev)
+        row = logits[torch.arange(B, device=dev), last]                   # [B, V]
+        positions = torch.tensor(lengths, dtype=torch.int32, device=dev)
+        state.update(positions=positions, pos_max=max(lengths))
+        decoder._ragged_scratch(state, dev)                               # (before the first sampler launch: no fill between steps)
+        err = state["error"]                                              # the step kernels' sticky error word
+    else:
+        row = logits[:, -1]                                               # [B, V] view, row stride T * V
     n = 0
     for g in range(max_new_tokens):
-        ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                          do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
-                          hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                          out=nxt, out_tokens=out, out_col=g)
+        if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
+            ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                              do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
+                              history=history, hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id,
+                              pad_token_id=pad_token_id, out=nxt, out_tokens=out, out_col=g)
+        else:
+            ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                              do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
+                              hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                              out=nxt, out_tokens=out, out_col=g)
         if output_logits:
             kept.append(row.clone())
         n = g + 1
         if n == max_new_tokens:
             break
-        if eos_token_id is not None and eos_poll > 0 and n % eos_poll == 0 and bool(finished.all()):
-            break                                                         # the loop's only device-to-host read
+        if eos_token_id is not None and eos_poll > 0 and n % eos_poll == 0:
+            if positions is None:
+                if bool(finished.all()):
+                    break                                                 # the loop's only device-to-host read
+            else:                                                         # ... which also brings the step kernels' error word
+                done, word = torch.stack([finished.min().to(torch.int32), err[0]]).tolist()
+                _raise_position_error(word, state)
+                if done:
+                    break
+        if positions is not None:
+            row = decoder._forward_incremental(None, state, None, prec, next_token=nxt, pos_shift=pos_shift)[:, 0]
+            continue
         t = T + g
         pos = (t - pos_shift, t) if pos_shift else (t, -1)
         row = decoder._forward_incremental(None, state, None, prec, next_token=nxt, next_pos=pos)[:, 0]
+    if positions is not None:
+        _raise_position_error(int(err.item()), state)                     # device positions are validated by the kernels, not here
     out = out[:, :n]
     if output_logits:
         return out, torch.stack(kept, dim=1)
@@ -66,3 +105,45 @@ def check_budget(decoder, T: int, max_new_tokens: int):
     if T + max_new_tokens > rows:
         raise IndexError(f"index out of range in self: {T} prompt positions + {max_new_tokens} new tokens exceed the "
                          f"{rows}-row position table / cache")
+
+
+def _raise_position_error(word: int, state: dict):
+    """The sticky word of the ragged step kernels (kx_ragged_error): a row's device position left the table / the cache."""
+    if word:
+        what = " and ".join(name for bit, name in ((H.KX_RAGGED_ERR_TABLE, "the position / XPos tables"),
+                                                   (H.KX_RAGGED_ERR_CACHE, "the KV cache")) if word & bit)
+        raise IndexError(f"index out of range in self: a row's device position left {what} (host-side maximum "
+                         f"{state.get('pos_max')}, cache of {state.get('max_len')} rows); that row's step wrote nothing")
+
+
+def resolve_prompt_lengths(prompt_lengths, B: int, width: int, min_len: int = 1) -> list:
+    """``prompt_lengths`` (a sequence of B ints or an integer tensor) -> a host list of B ints in [min_len, width], or
+    ValueError.  Host data is taken as it is; a device tensor is read back once."""
+    if isinstance(prompt_lengths, torch.Tensor):
+        if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
+            raise ValueError(f"prompt_lengths must hold integers, got a {prompt_lengths.dtype} tensor")
+        if prompt_lengths.dim() != 1:
+            raise ValueError(f"prompt_lengths must have {B} entries, got shape {tuple(prompt_lengths.shape)}")
+        lens = prompt_lengths.tolist()                     # (the one read of a device tensor)
+    else:
+        try:
+            lens = [operator.index(l) for l in prompt_lengths]
+        except TypeError:
+            raise ValueError(f"prompt_lengths must be a sequence of {B} integers or an integer tensor, got {prompt_lengths!r}") from None
+    if len(lens) != B:
+        raise ValueError(f"prompt_lengths must have {B} entries (one per row), got {len(lens)}")
+    for b, l in enumerate(lens):
+        if l < min_len:
+            raise ValueError(f"prompt_lengths[{b}] = {l}: a prompt has at least {min_len} token" + ("s" if min_len > 1 else "")
+                             + (" (the image is spliced after two text tokens)" if min_len == 2 else ""))
+        if l > width:
+            raise ValueError(f"prompt_lengths[{b}] = {l} exceeds the padded width {width}")
+    return lens
+
+
+def mask_padding(tokens: torch.Tensor, lengths: list) -> torch.Tensor:
+    """``tokens`` [B, T] int64 with the columns at and after lengths[b] replaced by the row's own first token: whatever the
+    padding held is never embedded or range-checked, and the repetition penalty's history sees no id the prompt lacks."""
+    T = tokens.shape[1]
+    lens = torch.tensor(lengths, dtype=torch.int64, device=tokens.device)
+    return torch.where(torch.arange(T, device=tokens.device)[None, :] < lens[:, None], tokens, tokens[:, :1])

@@ -795,13 +795,19 @@ class Decoder(_PackedMixin, nn.Module):
         return logits
 
     # -- incremental decoding ---------------------------------------------------
-    def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None) -> torch.Tensor:
+    def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None,
+                             pos_shift: int = 0) -> torch.Tensor:
         """torchscale's incremental_state protocol: the first call runs the whole prefix and fills the KV cache,
         every later call is given the token history (only its last token and its length are used, as upstream's
         `tokens[:, -1:]`) and appends one position.  ``state`` is an opaque dict owned by the caller.
         ``next_token`` (later steps only, used by generate()): the step's token as an int64 [B] tensor the device sampler
         wrote (kx_sample_logits: ids < vocab by construction, so no range read-back), embedded by kx_embed_step with
-        position rows ``next_pos`` = (pos_a, pos_b); default (t, -1), what ``embed(..., pos_offset=t)`` adds."""
+        position rows ``next_pos`` = (pos_a, pos_b); default (t, -1), what ``embed(..., pos_offset=t)`` adds.
+        Ragged batches (generate(prompt_lengths=...)): ``state["positions"]`` is an int32 [B] DEVICE tensor, row b's number of
+        cached tokens, and ``state["pos_max"]`` its host-side maximum (for the budget check and the error messages only).  A
+        later step then takes ``next_token`` and runs kx_decoder_decode_step_ragged: every row at its own position, embedded
+        with the position rows positions[b] (and positions[b] - ``pos_shift`` when that is not 0).  The step does not move
+        the device positions — the sampler that produced ``next_token`` did (kx_sample_logits_ragged)."""
         if self.args.activation_fn != "gelu":
             raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
                                       "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
@@ -849,6 +855,11 @@ class Decoder(_PackedMixin, nn.Module):
             state.update(len=T, max_len=Tmax, batch=B, prec=prec)
             return logits
         t, Tmax, B = state["len"], state["max_len"], state["batch"]           # ---- later steps: one token ----
+        positions = state.get("positions")
+        if positions is not None:
+            if next_token is None or passed_x is not None:
+                raise ValueError("a ragged incremental state (state['positions']) is stepped with next_token only")
+            t = state["pos_max"]                           # the furthest row: what the table / cache must still hold
         if state["prec"] != prec:
             raise RuntimeError("precision changed between incremental steps")
         if t >= Tmax or t + 2 >= pos.shape[0]:
@@ -872,6 +883,8 @@ class Decoder(_PackedMixin, nn.Module):
             w = self._pack(sprec)[0]
         if sprec in ("bf16", "fp32", "w24", "w16") and B <= 16:
             self._pack_decode_tiles(sprec)                 # first decode step: the streaming copy of the weights
+        if positions is not None:
+            return self._ragged_step(state, w, sprec, emb, pos, next_token, positions, pos_shift)
         if passed_x is not None:
             _require_cuda(passed_x, "passed_x")
             x = passed_x[:, -1:].to(torch.float32).clone(memory_format=torch.contiguous_format)
@@ -901,6 +914,40 @@ class Decoder(_PackedMixin, nn.Module):
                                            _stream()), "kx_decoder_decode_step")
         self._finish_check()                               # an IndexError leaves the state where it was (row t is rewritten)
         state["len"] = t + 1
+        return logits
+
+    def _ragged_scratch(self, state: dict, dev):
+        """What a ragged step needs beside the caches, kept with the state (same pointers every step): the kernels' sticky
+        error word, the step's input rows and the gathered XPos rows.  Zeros, not empty: a row kx_step_prepare rejects is not
+        written, and what it computes until the error word is read must be finite and the same every time.  generate() calls
+        this before its first sampler launch, so that no fill lands between two steps."""
+        B, D = state["batch"], self.args.decoder_embed_dim
+        if "error" not in state:
+            state["error"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        if "x_step" not in state:
+            state["x_step"] = torch.zeros((B, 1, D), dtype=torch.float32, device=dev)
+            state["xpos_rows"] = None if state["xpos"][0] is None else torch.zeros((4, B, 32), dtype=torch.float32, device=dev)
+
+    def _ragged_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift) -> torch.Tensor:
+        """One decode step with every row at its own device-resident position (see _forward_incremental)."""
+        lib = H.load()
+        _require_cuda(next_token, "next_token")
+        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
+        if next_token.shape[0] != B or positions.shape[0] != B:
+            raise ValueError("batch size changed between incremental steps")
+        dev = emb.device
+        self._ragged_scratch(state, dev)
+        logits = torch.empty((B, 1, w.vocab), dtype=torch.float32, device=dev)
+        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
+               else H.PACK_PRECS[sprec])
+        need = lib.kx_decoder_workspace_bytes(C.byref(w), B, 1, pid)
+        buf = self._ws.get(need, dev)
+        H.check(lib.kx_decoder_decode_step_ragged(
+            C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
+            state["x_step"].data_ptr(), B, positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
+            state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits.data_ptr(), H.KX_F32, buf.data_ptr(),
+            buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_ragged")
+        state["pos_max"] += 1
         return logits
 
     # -- torchscale-compatible surface ------------------------------------------------------------
@@ -1126,14 +1173,17 @@ class Kosmos(nn.Module):
 
     def generate(self, text_tokens: torch.Tensor, images: torch.Tensor, max_new_tokens: int, *, do_sample=False,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1,
-                 sequence_ids=None, eos_poll=8, output_logits=False):
+                 sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
         KV cache, then one decode step + one sampling launch per token with the token kept on the device
         (kosmosx.generation).  A generated token enters the decoder exactly as it would as part of ``text_tokens`` in
         forward().  Sampling (``do_sample``): temperature -> top-k -> top-p after the repetition penalty, reproducible from
-        (seed, sequence id, position)."""
+        (seed, sequence id, position).
+        ``prompt_lengths`` (B ints or an integer tensor): a ragged batch — row b's prompt is ``text_tokens[b, :prompt_lengths[b]]``
+        (at least 2 tokens: the image is spliced after two), the columns after it are right padding and are ignored whatever
+        they hold.  Each row generates what it would generate alone, with the same seed and ``sequence_ids[b]``."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1143,20 +1193,28 @@ class Kosmos(nn.Module):
         if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
             raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
         n_img = self.cfg.perceiver.latents
+        lens = None
+        if prompt_lengths is not None:
+            lens = generation.resolve_prompt_lengths(prompt_lengths, text_tokens.shape[0], text_tokens.shape[1], min_len=2)
+            text_tokens = text_tokens[:, :max(lens)]                         # columns no row uses
         T = text_tokens.shape[1] + n_img
         generation.check_budget(self.decoder, T, max_new_tokens)
         prec = self.precision
         with torch.no_grad():
+            if lens is not None:
+                text_tokens = generation.mask_padding(text_tokens.long(), lens)
             img = self.clip_model.run(images, prec, self._ws)
             img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
             x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
             state = {"max_len": T + max_new_tokens}
+            # (ragged: the right-padded prefill needs no mask — the argument is spelled out in KosmosLanguage.generate)
             logits = self.decoder._forward_incremental(None, state, x, prec)
             return generation.generate_loop(
                 self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens,
                 pos_shift=n_img if self.switches.u1_inplace_alias else 0, do_sample=do_sample, temperature=temperature,
                 top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed, eos_token_id=eos_token_id,
-                pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll, output_logits=output_logits)
+                pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll, output_logits=output_logits,
+                lengths=None if lens is None else [n_img + l for l in lens])
 
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
@@ -1253,8 +1311,9 @@ class KosmosLanguage(nn.Module):
 
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
                  repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
-                 output_logits=False):
-        """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate."""
+                 output_logits=False, prompt_lengths=None):
+        """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
+        (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1262,16 +1321,28 @@ class KosmosLanguage(nn.Module):
         _require_cuda(x, "x")
         if x.dim() != 2:
             raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
+        lens = None
+        if prompt_lengths is not None:
+            lens = generation.resolve_prompt_lengths(prompt_lengths, x.shape[0], x.shape[1], min_len=1)
+            x = x[:, :max(lens)]                                             # columns no row uses
         T = x.shape[1]
         generation.check_budget(self.decoder, T, max_new_tokens)
         with torch.no_grad():
+            if lens is not None:
+                x = generation.mask_padding(x.long(), lens)
             state = {"max_len": T + max_new_tokens}
+            # Ragged prompts go through the ordinary prefill, right-padded, with no padding mask and no new kernel: attention is
+            # causal, so a real position (< len_b) never has a padded key (>= len_b) among the keys it sees, and every other
+            # operation of the decoder works on a row alone.  The padded rows compute finite values (their ids are the row's first
+            # token, mask_padding) that nobody uses: the first token is drawn from logits[b, len_b - 1], and cache row
+            # len_b + g of sequence b is overwritten by the row's own g-th generated token in the very launch whose query is the
+            # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row).
             logits = self.decoder._forward_incremental(x, state, None, self.precision)
             return generation.generate_loop(
                 self.decoder, self.precision, state, logits, x.long(), max_new_tokens, do_sample=do_sample,
                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
                 eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-                output_logits=output_logits)
+                output_logits=output_logits, lengths=lens)
 
 
 class KosmosTokenizer:

@@ -368,7 +368,7 @@ def embed_splice(tokens, embed, pos, img=None, u1_alias=True, splice_at=2, pos_o
 
 def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
                   position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
-                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0):
+                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0):
     """Next token of every row of fp32 `logits` [B, V] (row stride >= V), drawn on the device by one launch
     (kx_sample_logits in include/kosmosx_hip.h: repetition penalty -> temperature -> top-k -> top-p -> Gumbel-max draw
     addressed by (seed, sequence id, position); greedy when ``do_sample`` is false or ``temperature`` is 0).
@@ -376,16 +376,19 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     history [B, >= hist_len + 1] int64: the ids the repetition penalty looks at; the new token is appended at column
     ``hist_len``.  finished [B] uint8 (in/out): finished rows emit ``pad_token_id``, a row that draws ``eos_token_id``
     becomes finished.  out [B] int64 / out_tokens [B, n] int64 with ``out_col``: caller-owned places for the result.
+    positions [B] int32 (device, in/out): the ragged form (kx_sample_logits_ragged) — row b draws at Philox position
+    ``positions[b] + advance`` and, when ``advance`` is not 0, leaves that value in ``positions[b]``; ``position`` is unused.
     Returns next_token [B] int64 (and kept_count [B] int32, keep_mask [B, V] uint8 with ``return_debug``)."""
-    _need_cuda(logits, sequence_ids, history, finished, out, out_tokens)
+    _need_cuda(logits, sequence_ids, history, finished, out, out_tokens, positions)
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise TypeError("sample_logits: logits must be fp32 [B, V] with unit column stride")
     for name, t, dt in (("sequence_ids", sequence_ids, torch.int64), ("history", history, torch.int64),
-                        ("finished", finished, torch.uint8), ("out", out, torch.int64), ("out_tokens", out_tokens, torch.int64)):
+                        ("finished", finished, torch.uint8), ("out", out, torch.int64), ("out_tokens", out_tokens, torch.int64),
+                        ("positions", positions, torch.int32)):
         if t is not None and (t.dtype != dt or not t.is_contiguous()):
             raise TypeError(f"sample_logits: {name} must be a contiguous {dt} tensor")
     B, V = logits.shape
-    for name, t in (("sequence_ids", sequence_ids), ("finished", finished), ("out", out)):
+    for name, t in (("sequence_ids", sequence_ids), ("finished", finished), ("out", out), ("positions", positions)):
         if t is not None and tuple(t.shape) != (B,):
             raise ValueError(f"sample_logits: {name} must have shape [{B}]")
     for name, t in (("history", history), ("out_tokens", out_tokens)):
@@ -409,5 +412,85 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
         kept = torch.empty(B, dtype=torch.int32, device=logits.device)
         mask = torch.empty((B, V), dtype=torch.uint8, device=logits.device)
         a.kept_count, a.keep_mask = kept.data_ptr(), mask.data_ptr()
-    H.check(H.load().kx_sample_logits(C.byref(a), _stream()), "kx_sample_logits")
+    if positions is not None:
+        a.position = 0
+        H.check(H.load().kx_sample_logits_ragged(C.byref(a), positions.data_ptr(), int(advance), _stream()), "kx_sample_logits_ragged")
+    else:
+        H.check(H.load().kx_sample_logits(C.byref(a), _stream()), "kx_sample_logits")
     return (out, kept, mask) if return_debug else out
+
+
+def embed_step(tokens, embed, pos, pos_a, pos_b=-1):
+    """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
+    kx_embed_step: [B, d] fp32 rows embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b]) for int64 ``tokens`` [B] on the device."""
+    _need_cuda(tokens, embed, pos)
+    B, d = tokens.shape[0], embed.shape[1]
+    out = torch.empty((B, d), dtype=torch.float32, device=embed.device)
+    H.check(H.load().kx_embed_step(tokens.data_ptr(), embed.data_ptr(), pos.data_ptr(), out.data_ptr(), B, d, embed.shape[0],
+                                   pos.shape[0], int(pos_a), int(pos_b), _stream()), "kx_embed_step")
+    return out
+
+
+def step_prepare(tokens, embed, pos, positions, tables=None, pos_shift=0, error_word=None, out=None, xpos_rows=None):
+    """kx_step_prepare, the start of a ragged decode step: per row b the embedding of ``tokens[b]`` (int64 [B]) at position
+    ``positions[b]`` (int32 [B], device; with ``pos_shift`` the two rows positions[b] - pos_shift and positions[b]) and row
+    positions[b] of each of the four XPos ``tables`` ([n, 32] fp32) gathered into [4, B, 32].  A position outside the tables
+    sets KX_RAGGED_ERR_TABLE in ``error_word`` (int32 [1], sticky) and leaves that row untouched.
+    Returns (x [B, d], xpos_rows [4, B, 32] or None, error_word)."""
+    _need_cuda(tokens, embed, pos, positions, error_word, out, xpos_rows, *(tables or ()))
+    if positions.dtype != torch.int32 or not positions.is_contiguous() or tokens.dtype != torch.int64:
+        raise TypeError("step_prepare: tokens must be int64 and positions a contiguous int32 tensor")
+    B, d = tokens.shape[0], embed.shape[1]
+    if error_word is None:
+        error_word = torch.zeros(1, dtype=torch.int32, device=embed.device)
+    if out is None:                                    # (zeros: a rejected row is not written)
+        out = torch.zeros((B, d), dtype=torch.float32, device=embed.device)
+    tp, n = (0, 0, 0, 0), 0
+    if tables is not None:
+        n = tables[0].shape[0]
+        if any(t.dtype != torch.float32 or tuple(t.shape) != (n, 32) or not t.is_contiguous() for t in tables):
+            raise TypeError("step_prepare: tables are four contiguous fp32 [n, 32] tensors")
+        tp = tuple(t.data_ptr() for t in tables)
+        if xpos_rows is None:
+            xpos_rows = torch.zeros((4, B, 32), dtype=torch.float32, device=embed.device)
+    H.check(H.load().kx_step_prepare(tokens.data_ptr(), embed.data_ptr(), pos.data_ptr(), positions.data_ptr(), *tp,
+                                     out.data_ptr(), H.ptr(xpos_rows if tables is not None else None), B, d, embed.shape[0],
+                                     pos.shape[0], int(pos_shift), n, error_word.data_ptr(), _stream()), "kx_step_prepare")
+    return out, (xpos_rows if tables is not None else None), error_word
+
+
+def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=None, out_dtype="f32", stats_out=None):
+    """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
+    The decode step's single-query attention + cache append (kx_attention_decode / kx_attention_decode_ragged).
+    qkv [B, 3 * H * 64] fp32 or bf16 rows of the new token; kcache / vcache [B, H, Tmax, 64] of the same dtype (updated in place).
+    ``t``: every sequence at host position t; ``positions`` [B] int32 on the device: sequence b at positions[b], a position
+    outside the cache sets KX_RAGGED_ERR_CACHE in ``error_word`` (int32 [1], sticky).  out_dtype "f32" | "bf16" | "f16c" | "f16p"
+    (the KX_F16C / KX_F16P operand rows of the fp32 step).  Returns the attention output rows."""
+    _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out)
+    B, Hh, Tmax, hd = kcache.shape
+    if hd != 64 or tuple(qkv.shape) != (B, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError("attention_decode: qkv [B, 3*H*64], caches [B, H, Tmax, 64], contiguous")
+    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("attention_decode: qkv and the caches share one dtype, fp32 or bf16")
+    D = Hh * 64
+    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
+    if out_dtype == "f16c":
+        out = torch.zeros((B, 4 * D), dtype=torch.uint8, device=qkv.device)
+    else:
+        out = torch.zeros((B, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
+    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    lib = H.load()
+    if positions is None:
+        if t is None:
+            raise TypeError("attention_decode: give the host position t or the device positions")
+        H.check(lib.kx_attention_decode(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                        H.ptr(stats_out), B, Hh, int(t), Tmax, prec, _stream()), "kx_attention_decode")
+        return out
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (B,) or not positions.is_contiguous():
+        raise TypeError(f"attention_decode: positions must be a contiguous int32 [{B}] tensor")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError("attention_decode: positions need error_word, an int32 [1] tensor on the device (the kernel's sticky word)")
+    H.check(lib.kx_attention_decode_ragged(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                           H.ptr(stats_out), B, Hh, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
+                                           _stream()), "kx_attention_decode_ragged")
+    return out

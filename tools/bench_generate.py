@@ -3,7 +3,15 @@
   (b) the same loop with a sampler composed from torch ops (sort / softmax / cumsum / multinomial) and a host token feed
       through the public incremental path — what a caller had to write before generate() existed;
   (c) the bare decode step (tools/bench_decode.py's loop) in the same process.
-One JSON line per batch size.  --only a|b|c restricts the run to one variant (for a kernel trace of that variant alone)."""
+One JSON line per batch size.  --only a|b|c restricts the run to one variant (for a kernel trace of that variant alone).
+
+--ragged: the ragged-batch leg instead of (b) and (c).  Row b's prompt has lengths[b] tokens, spread evenly over
+[--min-prefix, --prefix], right-padded to --prefix:
+  (a) uniform generate() over the full-width prompts, as above;
+  (r) generate(prompt_lengths=lengths): ms per token after the (same-shape) prefill, and tokens per second of the whole call;
+  (s) one generate() per row over its own unpadded prompt — what a caller with unequal prompts had to do before: tokens per
+      second over all B calls, prefills included.
+--only a|r|s restricts the run."""
 import argparse, json, os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -19,8 +27,12 @@ ap.add_argument("--prefix", type=int, default=114)
 ap.add_argument("--new", type=int, default=64)
 ap.add_argument("--precision", default="mixed")
 ap.add_argument("--reps", type=int, default=3)
-ap.add_argument("--only", default="abc")
+ap.add_argument("--only", default=None)
+ap.add_argument("--ragged", action="store_true")
+ap.add_argument("--min-prefix", type=int, default=16)
 a = ap.parse_args()
+if a.only is None:
+    a.only = "ars" if a.ragged else "abc"
 dev = torch.device("cuda", 0)
 V = 32002
 m = KosmosLanguage(vocab_size=V, dim=2048, _seed=0).eval().to(dev)
@@ -65,6 +77,19 @@ def run_c(tok_all):
     return out
 
 
+def lengths_of(B):
+    return [a.prefix] if B == 1 else [a.min_prefix + round(i * (a.prefix - a.min_prefix) / (B - 1)) for i in range(B)]
+
+
+def run_r(tok):
+    return m.generate(tok, a.new, prompt_lengths=lengths_of(tok.shape[0]), **KW)
+
+
+def run_s(tok):
+    ids = torch.arange(tok.shape[0], device=dev)
+    return [m.generate(tok[b:b + 1, :L].contiguous(), a.new, sequence_ids=ids[b:b + 1], **KW) for b, L in enumerate(lengths_of(tok.shape[0]))]
+
+
 def timed(fn, arg):
     best = None
     for rep in range(a.reps + 1):                               # rep 0 = warm-up (packs weights, sizes workspaces)
@@ -86,8 +111,18 @@ with torch.no_grad():
         pre = timed(lambda t: m(t, incremental_state={"max_len": a.prefix + a.new}), tok)
         res = {"workload": f"KosmosLanguage generate, B={B}, prefix {a.prefix}, {a.new} new tokens, {a.precision}, "
                            "top_k=50 top_p=0.9 temperature=0.8", "prefill_ms": round(pre * 1e3, 3)}
+        if a.ragged:
+            res["lengths"] = lengths_of(B)
+            if "a" in a.only:
+                res["a_generate_uniform_ms_per_token"] = round((timed(run_a, tok) - pre) / (a.new - 1) * 1e3, 4)
+            if "r" in a.only:
+                dt = timed(run_r, tok)
+                res["r_generate_ragged_ms_per_token"] = round((dt - pre) / (a.new - 1) * 1e3, 4)
+                res["r_ragged_tokens_per_s"] = round(B * a.new / dt, 1)
+            if "s" in a.only:
+                res["s_solo_calls_tokens_per_s"] = round(B * a.new / timed(run_s, tok), 1)
         for name, fn, arg in (("a", run_a, tok), ("b", run_b, tok), ("c", run_c, tok_all)):
-            if name in a.only:
+            if name in a.only and not a.ragged:
                 res[{"a": "a_generate_fused_ms_per_token", "b": "b_torch_sampler_ms_per_token",
                      "c": "c_bare_decode_step_ms_per_token"}[name]] = round((timed(fn, arg) - pre) / (a.new - 1) * 1e3, 4)
         # launches per token, counted by the library's own per-launch records: generate(3 tokens) - generate(2 tokens) is one
@@ -95,7 +130,7 @@ with torch.no_grad():
         counts = []
         for n_new in (2, 3):
             _hip.prof_enable(True)
-            m.generate(tok, n_new, **KW)
+            m.generate(tok, n_new, **(dict(KW, prompt_lengths=lengths_of(B)) if a.ragged else KW))
             torch.cuda.synchronize()
             counts.append(len(_hip.prof_collect()))
         state = {"max_len": a.prefix + a.new}
