@@ -406,7 +406,7 @@ typedef enum {
   KX_STRUCT_GEMM_ARGS = 0, KX_STRUCT_ATTN_ARGS = 1, KX_STRUCT_VIT_LAYER = 2, KX_STRUCT_VIT_WEIGHTS = 3,
   KX_STRUCT_PERCEIVER_LAYER = 4, KX_STRUCT_PERCEIVER_WEIGHTS = 5, KX_STRUCT_DECODER_LAYER = 6,
   KX_STRUCT_DECODER_WEIGHTS = 7, KX_STRUCT_RESAMPLE_PLAN = 8, KX_STRUCT_PROF_RECORD = 9, KX_STRUCT_SAMPLE_ARGS = 10,
-  KX_STRUCT_COUNT = 11
+  KX_STRUCT_BEAM_ARGS = 11, KX_STRUCT_COUNT = 12
 } kx_struct_id;
 /* sizeof() of the struct as this library was compiled; 0 for an unknown id.  Pure host arithmetic. */
 size_t kx_struct_bytes(int32_t id);
@@ -575,7 +575,7 @@ int kx_attention_decode(const void* qkv, void* kcache, void* vcache, void* out, 
  *   the FULL [Tmax, 32] tables (one centring, as for the prefill); xpos_rows [4, B, 32] fp32 scratch.  x and xpos_rows
  *   are zeroed by the caller before the first step (see kx_step_prepare).  Both step paths
  *   (weight streaming up to 16 sequences, tile GEMMs above) run their qkv launch with xpos_T = B on xpos_rows. */
-typedef enum { KX_RAGGED_ERR_TABLE = 1, KX_RAGGED_ERR_CACHE = 2 } kx_ragged_error;
+typedef enum { KX_RAGGED_ERR_TABLE = 1, KX_RAGGED_ERR_CACHE = 2, KX_RAGGED_ERR_GATHER = 4 /* kx_kv_cache_gather */ } kx_ragged_error;
 int kx_attention_decode_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
                                int64_t B, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
                                int32_t* error_word, void* stream);
@@ -590,6 +590,74 @@ int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const int64_t* to
                                   const float* xk_ss, float* xpos_rows, void* kcache, void* vcache, int64_t Tmax,
                                   void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
                                   int32_t* error_word, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Beam search on the device (added within ABI 7: one struct, three functions, one kx_struct_id value and one kx_ragged_error bit
+ * are appended; no existing layout moves, so kx_version() stays 7).
+ *
+ * State per batch row b: W live beams, each with an fp32 cumulative score s_j; a pool of at most W finished hypotheses
+ * (score, end step, parent beam); a `done` byte.
+ *
+ * kx_beam_step — step g (0-based, args->step) ranks Win input beams per batch row: Win = 1 at g = 0 (the prefill ran once per batch
+ * row, not W times), Win = W afterwards.  For input beam j with logits row x = logits[(b * Win + j) * ld + 0:V]:
+ *   - on load: NaN and -inf are never candidates, +inf is clamped to FLT_MAX, -0 is read as +0;
+ *   - m = max x; Z = sum exp(x - m) accumulated as 64-bit integers in 2^-40 fixed point (the sampler's mass: integer adds
+ *     commute, so Z does not depend on execution order); lse = m + logf((float)Z * 2^-40);
+ *   - candidate (j, v) has c = fl(s_j + fl(x_v - lse)), single fp32 operations; a candidate needs c > -inf (a beam whose score
+ *     is -inf offers none);
+ *   - candidates are ranked by c descending, exact ties to the lower flat index j * V + v; the best 2W are walked in rank order.
+ * Walking: a candidate with v == eos_id at rank < W (0-based) enters the pool with score c / (g + 1)^alpha (fp32; alpha =
+ * length_penalty), end step g and parent beam j — a full pool replaces its worst entry (lowest score, the later slot among equal
+ * ones) only if the new score is strictly better; at rank >= W it is skipped.  Any other candidate becomes the next live beam
+ * until W are filled (at most one EOS candidate exists per input beam, so 2W candidates always hold W others when enough finite
+ * candidates exist).  An unfilled slot i gets score -inf, token pad_id and parent i (0 when i >= Win).
+ * Outputs per row b * W + i: next_token int64 (what kx_embed_step reads), parent int32 = j (with next_token: the backpointers of
+ * step g), src_row int32 = b * Win + j (what kx_kv_cache_gather reads), scores_out = s_i.
+ * Done: after the walk row b becomes done when its pool holds W hypotheses and (early_stopping, or worst pool score >= best live
+ * c / (g + 1)^alpha; no live beam counts as -inf).  A done row is frozen from the next step on: its pool never changes, its live
+ * beams keep their scores, their tokens are pad_id and their parents the identity.
+ *
+ * Two launches, no workgroup waits on another: one 1024-thread workgroup per input beam row computes m, Z, lse and writes the
+ * row's own best 2W (key(c), v) pairs to `scratch` (B * Win * 2W uint64; the best 2W of a batch row lie inside the union of these
+ * sets) by 2W exact arg-max passes over (key, ~index) pairs — 2 + 2W reads of the row, consecutive lanes on consecutive logits,
+ * 16-byte loads where the row is 16-byte aligned; one workgroup per batch row then ranks the <= W * 2W <= 512 pairs by counting,
+ * walks them and writes the outputs.  scores_in [B * Win] and scores_out [B * W] may be the same buffer only when Win == W.
+ * Limits: 1 <= W <= 16, Win in {1, W}, V >= 2W, V <= 2^23.  Never allocates, never synchronises.
+ *
+ * kx_beam_finalize — after the last of n steps: every row that is not done offers its live beams (score > -inf) to the pool at
+ * s_i / n^alpha (end step n, parent i) under the same replacement rule; then the R best pool entries per row (score descending,
+ * the earlier slot among equal ones) are backtracked through parent / token ([n, trace_ld] arrays, row g = step g's outputs,
+ * trace_ld >= B * W) into out_tokens [B, R, out_ld] (out_ld >= n; columns 0:n are written: the hypothesis, its EOS, then pad_id)
+ * and out_scores [B, R].  A slot with no hypothesis is all pad_id with score -inf.  One thread per hypothesis.
+ *
+ * kx_kv_cache_gather — dst[l, r, h, 0:t, :] = src[l, src_row[r], h, 0:t, :] for both caches ([L, B, heads, Tmax, 64], elem_bytes
+ * = 4 for the fp32 / f16c cache, 2 for the bf16 cache; 16-byte aligned), src_row [B_dst] int32 ON THE DEVICE.  Rows at and after t
+ * of dst are not written.  src and dst must not overlap (KX_ERR_INVALID_ARG, nothing launched).  A src_row entry outside
+ * [0, B_src) makes that row copy nothing and ORs KX_RAGGED_ERR_GATHER into the sticky *error_word (see "Ragged batches"). */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_beam_args) of the caller ("stale binding" otherwise) */
+  int32_t early_stopping;
+  const float* logits; int64_t ld; int64_t B; int64_t Win; int64_t W; int64_t V;
+  int64_t step; float length_penalty;
+  int64_t eos_id; int64_t pad_id;             /* eos_id < 0 = none */
+  const float* scores_in;                     /* [B * Win] */
+  float* scores_out;                          /* [B * W] */
+  int64_t* next_token;                        /* [B * W] */
+  int32_t* parent;                            /* [B * W] */
+  int32_t* src_row;                           /* [B * W] */
+  float* pool_score; int32_t* pool_end; int32_t* pool_parent;   /* [B * W] each */
+  int32_t* pool_count;                        /* [B], zeroed by the caller before step 0 */
+  uint8_t* done;                              /* [B], zeroed by the caller before step 0 */
+  uint64_t* scratch;                          /* [B * Win * 2W] */
+} kx_beam_args;
+int kx_beam_step(const kx_beam_args* args, void* stream);
+int kx_beam_finalize(const float* scores_live, const uint8_t* done, float* pool_score, int32_t* pool_end, int32_t* pool_parent,
+                     int32_t* pool_count, const int32_t* parent, const int64_t* token, int64_t trace_ld, int64_t B, int64_t W,
+                     int64_t R, int64_t n, float length_penalty, int64_t eos_id, int64_t pad_id, int64_t* out_tokens,
+                     int64_t out_ld, float* out_scores, void* stream);
+int kx_kv_cache_gather(const void* src_k, const void* src_v, void* dst_k, void* dst_v, int64_t L, int64_t B_src, int64_t B_dst,
+                       int64_t heads, int64_t Tmax, int64_t t, int32_t elem_bytes, const int32_t* src_row, int32_t* error_word,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before

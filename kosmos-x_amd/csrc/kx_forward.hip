@@ -303,6 +303,7 @@ extern "C" size_t kx_struct_bytes(int32_t id) {
     case KX_STRUCT_RESAMPLE_PLAN: return sizeof(kx_resample_plan);
     case KX_STRUCT_PROF_RECORD: return sizeof(kx_prof_record);
     case KX_STRUCT_SAMPLE_ARGS: return sizeof(kx_sample_args);
+    case KX_STRUCT_BEAM_ARGS: return sizeof(kx_beam_args);
     default: return 0;
   }
 }

@@ -12,13 +12,11 @@
 // Every loop has a trip count fixed by V, the histogram size or the wave width; there is no waiting on other threads
 // beyond __syncthreads().
 #include "kx_common.h"
+#include "kx_select.h"   // f2key / key2f / mass_fix / block reductions, shared with kx_beam.hip
 
 namespace {
 
-constexpr int SB = 1024;                          // threads per workgroup (16 waves)
-constexpr int SW = SB / 64;
 constexpr int BINS = 2048;
-constexpr unsigned KEY_MIN_VALID = 0x00800000u;   // key(-FLT_MAX): every finite value and +inf map at or above it, -inf below
 constexpr long long KX_SAMPLE_MAX_V = 1ll << 23;  // 2^23 values of at most 2^40 each stay below 2^63
 constexpr long long KX_SAMPLE_MAX_V_PENALTY = 40960ll * 8;   // the history bitmap lives in LDS next to the histogram
 
@@ -33,14 +31,6 @@ struct SampleParams {
   int* kept_count; unsigned char* keep_mask;
 };
 
-__device__ __forceinline__ unsigned f2key(float x) {
-  const unsigned b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // x_i: repetition penalty (ids in the row's history, once per distinct id), then temperature; both IEEE fp32 divisions.
 // NaN and -inf come back as -inf (never a candidate), -0 as +0 (one key per value).
 __device__ __forceinline__ float load_x(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, int i) {
@@ -50,38 +40,6 @@ __device__ __forceinline__ float load_x(const SampleParams& a, const float* __re
   if (!(l > -__builtin_inff())) l = -__builtin_inff();
   if (l == 0.f) l = 0.f;
   return l;
-}
-
-// exp(x - m) in 2^-40 fixed point (truncated); x == m gives exactly 2^40, also when both are +inf
-__device__ __forceinline__ unsigned long long mass_fix(float x, float m) {
-  const float e = x == m ? 1.0f : expf(x - m);
-  return (unsigned long long)(e * 1099511627776.0f);
-}
-
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  unsigned long long r = red[0];
-#pragma unroll
-  for (int w = 1; w < SW; ++w) r = red[w] > r ? red[w] : r;
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  unsigned long long r = red[0];
-#pragma unroll
-  for (int w = 1; w < SW; ++w) r += red[w];
-  __syncthreads();
-  return r;
 }
 
 // The largest key K (among candidates with key >= limit) whose weight at or above it reaches `target`:

@@ -20,6 +20,7 @@ KX_F32, KX_BF16, KX_BF16X3, KX_F16C, KX_F16, KX_F16P, KX_F16HL = 0, 1, 2, 3, 4, 
 KX_ACT_NONE, KX_ACT_GELU, KX_ACT_QUICK_GELU = 0, 1, 2
 KX_ATTN_FULL, KX_ATTN_CAUSAL = 0, 1
 KX_RAGGED_ERR_TABLE, KX_RAGGED_ERR_CACHE = 1, 2
+KX_RAGGED_ERR_GATHER = 4
 KX_ACT_RELU, KX_ACT_SWISH = 5, 6
 ACTS = {"none": KX_ACT_NONE, "gelu": KX_ACT_GELU, "quick_gelu": KX_ACT_QUICK_GELU, "relu": KX_ACT_RELU, "swish": KX_ACT_SWISH}
 PRECS = {"bf16": KX_PREC_BF16, "fp32": KX_PREC_F32, "bf16x3": KX_PREC_BF16X3, "f16c": KX_PREC_F16C, "f16": KX_PREC_F16}
@@ -143,6 +144,18 @@ class SampleArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class BeamArgs(C.Structure):
+    """kx_beam_args; struct_bytes is filled in at construction ("stale binding" check of kx_beam_step)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("early_stopping", i32), ("logits", vp), ("ld", i64), ("B", i64), ("Win", i64),
+                ("W", i64), ("V", i64), ("step", i64), ("length_penalty", f32), ("eos_id", i64), ("pad_id", i64),
+                ("scores_in", vp), ("scores_out", vp), ("next_token", vp), ("parent", vp), ("src_row", vp),
+                ("pool_score", vp), ("pool_end", vp), ("pool_parent", vp), ("pool_count", vp), ("done", vp), ("scratch", vp)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -183,6 +196,9 @@ SYMBOLS = {
     "kx_sample_logits_ragged": (C.c_int, [C.POINTER(SampleArgs), vp, i64, vp]),
     "kx_decoder_decode_step_ragged": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp,
                                                 vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),
+    "kx_beam_step": (C.c_int, [C.POINTER(BeamArgs), vp]),
+    "kx_beam_finalize": (C.c_int, [vp] * 8 + [i64] * 5 + [f32, i64, i64, vp, i64, vp, vp]),
+    "kx_kv_cache_gather": (C.c_int, [vp] * 4 + [i64] * 6 + [i32, vp, vp, vp]),
     "kx_decoder_forward": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, i32, vp,
                                      C.c_size_t, i32, vp]),
     "kx_clip_preprocess_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
@@ -223,7 +239,7 @@ SYMBOLS = {
 
 
 STRUCT_IDS = [GemmArgs, AttnArgs, VitLayer, VitWeights, PerceiverLayer, PerceiverWeights, DecoderLayer, DecoderWeights,
-              ResamplePlan, ProfRecord, SampleArgs]            # index = kx_struct_id
+              ResamplePlan, ProfRecord, SampleArgs, BeamArgs]  # index = kx_struct_id
 
 
 def lib_path() -> Path:

@@ -8,8 +8,13 @@ Ragged batches (``prompt_lengths``): every row has its own position, an int32 wo
 advances (kx_sample_logits_ragged) and the decode step reads (kx_decoder_decode_step_ragged) — a step's launch arguments are
 then the same for every token.  Each row generates what it would generate alone.
 
-Not offered: beam search, compaction of finished rows, replaying the step as a captured graph, padding masks
-in ``Decoder.forward`` (``self_attn_padding_mask``).
+Beam search (``num_beams`` > 1, beam_loop): the prefill runs once per batch row; kx_beam_step ranks the beams x vocab candidates
+of every batch row, keeps the pool of finished hypotheses and the row's done byte and leaves tokens, scores and backpointers in
+device memory; kx_kv_cache_gather re-parents the cache rows into the other of two B * num_beams-row caches; the decode step is the
+uniform one at B * num_beams rows.  kx_beam_finalize backtracks the best hypotheses after the last step.
+
+Not offered: compaction of finished rows, replaying the step as a captured graph, padding masks in
+``Decoder.forward`` (``self_attn_padding_mask``); with beams: ragged prompts, penalties and sampling.
 """
 from __future__ import annotations
 
@@ -94,6 +99,105 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     if output_logits:
         return out, torch.stack(kept, dim=1)
     return out
+
+
+MAX_BEAMS = 16
+
+
+def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
+                    top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lengths=None, sequence_ids=None, output_logits=False,
+                    output_scores=False, output_trace=False, beam_path=False) -> bool:
+    """ValueError (naming the argument) for what generate() refuses, before anything is launched.  Returns whether the call
+    runs beam_loop: ``num_beams`` > 1, or ``beam_path`` (the internal switch that sends num_beams = 1 through it)."""
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or num_beams < 1:
+        raise ValueError(f"num_beams must be a positive integer, got {num_beams!r}")
+    if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or num_return_sequences < 1:
+        raise ValueError(f"num_return_sequences must be a positive integer, got {num_return_sequences!r}")
+    if num_return_sequences > num_beams:
+        raise ValueError(f"num_return_sequences = {num_return_sequences} exceeds num_beams = {num_beams}")
+    if not (num_beams > 1 or beam_path):
+        for name, on in (("output_scores", output_scores), ("output_trace", output_trace)):
+            if on:
+                raise ValueError(f"{name} is an output of beam search: it needs num_beams > 1")
+        return False
+    if num_beams > MAX_BEAMS:
+        raise ValueError(f"num_beams = {num_beams} exceeds {MAX_BEAMS}")
+    if not float(length_penalty) >= 0.0:
+        raise ValueError(f"length_penalty must be >= 0, got {length_penalty!r}")
+    if 2 * num_beams > vocab:
+        raise ValueError(f"num_beams = {num_beams}: a beam step ranks 2 * num_beams candidates, more than the vocabulary of {vocab}")
+    for name, bad in (("do_sample", bool(do_sample)), ("temperature", float(temperature) != 1.0), ("top_k", int(top_k) != 0),
+                      ("top_p", float(top_p) != 1.0), ("repetition_penalty", float(repetition_penalty) != 1.0),
+                      ("prompt_lengths", prompt_lengths is not None), ("sequence_ids", sequence_ids is not None),
+                      ("output_logits", bool(output_logits))):
+        if bad:
+            raise ValueError(f"{name} is not offered together with beam search (num_beams = {num_beams}); see DESIGN.md §7b")
+    return True
+
+
+def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tokens: int, *, num_beams: int, pos_shift: int = 0,
+              length_penalty=1.0, early_stopping=False, num_return_sequences=1, eos_token_id=None, pad_token_id=1, eos_poll=8,
+              output_scores=False, output_trace=False):
+    """Beam search after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (the prefill ran once per batch row).
+    Per token: kx_beam_step on the rows the last step wrote (step 0: the B prefill rows, one input beam each), kx_kv_cache_gather
+    of cache rows 0:t into the other B * W-row cache by the step's src_row, then the uniform decode step at B * W rows and
+    the common host position.  Every buffer is allocated before the first step; the host reads ``done.all()`` at the stop poll
+    and the gather's error word after the loop, nothing else.
+    Returns tokens int64 [B, n] (R = 1) or [B, R, n], then the fp32 [B, R] scores with ``output_scores``, then the trace dict
+    with ``output_trace`` (the contract: include/kosmosx_hip.h, "Beam search on the device")."""
+    B, T, V = logits.shape
+    dev = logits.device
+    W, R, N = int(num_beams), int(num_return_sequences), int(max_new_tokens)
+    BW = B * W
+    pad = int(pad_token_id)
+    zeros = torch.zeros(B, dtype=torch.float32, device=dev)                  # the scores step 0 starts from
+    score = torch.zeros((N, BW), dtype=torch.float32, device=dev)            # row g: the live scores after step g
+    parent = torch.zeros((N, BW), dtype=torch.int32, device=dev)             # rows g of parent / token: step g's backpointers
+    token = torch.full((N, BW), pad, dtype=torch.int64, device=dev)
+    src_row = torch.zeros(BW, dtype=torch.int32, device=dev)
+    pool = (torch.full((B, W), float("-inf"), dtype=torch.float32, device=dev), torch.zeros((B, W), dtype=torch.int32, device=dev),
+            torch.zeros((B, W), dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+    done = torch.zeros(B, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(BW * 2 * W, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    out_tokens = torch.empty((B, R, N), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((B, R), dtype=torch.float32, device=dev)
+    kept = torch.zeros((N, BW, V), dtype=torch.float32, device=dev) if output_trace else None
+    src = (state["kcache"], state["vcache"])                                # the B-row prefill cache, dropped after step 0
+    L, _, nh, Tmax, hd = src[0].shape
+    caches = [tuple(torch.empty((L, BW, nh, Tmax, hd), dtype=src[0].dtype, device=dev) for _ in range(2)) for _ in range(2)]
+    row = logits[:, -1]                                                      # [B, V] view, row stride T * V
+    n = 0
+    for g in range(N):
+        if kept is not None:
+            (kept[0].view(B, W, V)[:, 0] if g == 0 else kept[g]).copy_(row)
+        ops.beam_step(row, zeros if g == 0 else score[g - 1], num_beams=W, step=g, pool=pool, done=done, scores_out=score[g],
+                      next_token=token[g], parent=parent[g], src_row=src_row, scratch=scratch, length_penalty=length_penalty,
+                      early_stopping=early_stopping, eos_token_id=eos_token_id, pad_token_id=pad)
+        n = g + 1
+        if n == N:
+            break
+        if eos_token_id is not None and eos_poll > 0 and n % eos_poll == 0 and bool(done.all()):
+            break                                                            # the loop's only device-to-host read
+        t = T + g
+        dst = caches[g & 1]
+        ops.kv_cache_gather(src[0], src[1], dst[0], dst[1], t, src_row, err)
+        state.update(kcache=dst[0], vcache=dst[1], batch=BW)
+        src = dst
+        pos = (t - pos_shift, t) if pos_shift else (t, -1)
+        row = decoder._forward_incremental(None, state, None, prec, next_token=token[g], next_pos=pos)[:, 0]
+    ops.beam_finalize(score[n - 1], done, pool, parent, token, n, num_return_sequences=R, length_penalty=length_penalty,
+                      eos_token_id=eos_token_id, pad_token_id=pad, out_tokens=out_tokens, out_scores=out_scores)
+    if int(err.item()):                                                      # src_row is the beam step's own output
+        raise RuntimeError("beam search: kx_kv_cache_gather met a source row outside the cache (KX_RAGGED_ERR_GATHER)")
+    seqs = out_tokens[:, :, :n]
+    res = [seqs[:, 0] if R == 1 else seqs]
+    if output_scores:
+        res.append(out_scores)
+    if output_trace:
+        res.append(dict(logits=kept[:n], parent=parent[:n], token=token[:n], score=score[:n], pool_score=pool[0], pool_end=pool[1],
+                        pool_parent=pool[2], pool_count=pool[3], done=done))
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def check_budget(decoder, T: int, max_new_tokens: int):

@@ -1173,7 +1173,8 @@ class Kosmos(nn.Module):
 
     def generate(self, text_tokens: torch.Tensor, images: torch.Tensor, max_new_tokens: int, *, do_sample=False,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1,
-                 sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None):
+                 sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0,
+                 early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1183,10 +1184,22 @@ class Kosmos(nn.Module):
         (seed, sequence id, position).
         ``prompt_lengths`` (B ints or an integer tensor): a ragged batch — row b's prompt is ``text_tokens[b, :prompt_lengths[b]]``
         (at least 2 tokens: the image is spliced after two), the columns after it are right padding and are ignored whatever
-        they hold.  Each row generates what it would generate alone, with the same seed and ``sequence_ids[b]``."""
+        they hold.  Each row generates what it would generate alone, with the same seed and ``sequence_ids[b]``.
+        ``num_beams`` W in 2..16: beam search with W live beams per batch row (kosmosx.generation.beam_loop) -> the best
+        hypothesis of every row, int64 [B, n], or the ``num_return_sequences`` = R <= W best, [B, R, n], best first, each
+        padded with ``pad_token_id`` after its EOS.  A hypothesis of n generated tokens (its EOS included) scores
+        sum_logprob / n ** ``length_penalty``; ``early_stopping``: a row stops as soon as it holds W finished hypotheses
+        (otherwise once no live beam can still beat the worst of them).  ``output_scores``: also the fp32 [B, R] scores;
+        ``output_trace`` (debug / tests): also a dict of the per-step device tensors.  Greedy only: sampling, the filters, the
+        repetition penalty, ``prompt_lengths``, ``sequence_ids`` and ``output_logits`` raise ValueError together with beams."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
+        beams = generation.check_beam_args(
+            self.embed.weight.shape[0], num_beams=num_beams, length_penalty=length_penalty, num_return_sequences=num_return_sequences,
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+            prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
+            output_trace=output_trace, beam_path=_beam_path)
         _warn_train_mode(self)
         _require_cuda(text_tokens, "text_tokens")
         _require_cuda(images, "images")
@@ -1209,6 +1222,12 @@ class Kosmos(nn.Module):
             state = {"max_len": T + max_new_tokens}
             # (ragged: the right-padded prefill needs no mask — the argument is spelled out in KosmosLanguage.generate)
             logits = self.decoder._forward_incremental(None, state, x, prec)
+            if beams:
+                return generation.beam_loop(
+                    self.decoder, prec, state, logits, max_new_tokens, num_beams=num_beams,
+                    pos_shift=n_img if self.switches.u1_inplace_alias else 0, length_penalty=length_penalty,
+                    early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
+                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace)
             return generation.generate_loop(
                 self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens,
                 pos_shift=n_img if self.switches.u1_inplace_alias else 0, do_sample=do_sample, temperature=temperature,
@@ -1311,12 +1330,19 @@ class KosmosLanguage(nn.Module):
 
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
                  repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
-                 output_logits=False, prompt_lengths=None):
+                 output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
-        (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token)."""
+        (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
+        arguments that go with it: beam search, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
+        beams = generation.check_beam_args(
+            self.embed.weight.shape[0], num_beams=num_beams, length_penalty=length_penalty, num_return_sequences=num_return_sequences,
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+            prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
+            output_trace=output_trace, beam_path=_beam_path)
         _warn_train_mode(self)
         _require_cuda(x, "x")
         if x.dim() != 2:
@@ -1338,6 +1364,11 @@ class KosmosLanguage(nn.Module):
             # len_b + g of sequence b is overwritten by the row's own g-th generated token in the very launch whose query is the
             # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row).
             logits = self.decoder._forward_incremental(x, state, None, self.precision)
+            if beams:
+                return generation.beam_loop(
+                    self.decoder, self.precision, state, logits, max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
+                    early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
+                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace)
             return generation.generate_loop(
                 self.decoder, self.precision, state, logits, x.long(), max_new_tokens, do_sample=do_sample,
                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,

@@ -494,3 +494,97 @@ def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=
                                            H.ptr(stats_out), B, Hh, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
                                            _stream()), "kx_attention_decode_ragged")
     return out
+
+
+def beam_step(logits, scores_in, *, num_beams, step, pool, done, scores_out, next_token, parent, src_row, scratch,
+              length_penalty=1.0, early_stopping=False, eos_token_id=None, pad_token_id=1):
+    """One beam-search step (kx_beam_step in include/kosmosx_hip.h) over fp32 `logits` [B * Win, V] (row stride >= V), Win = 1 at
+    ``step`` 0 and ``num_beams`` (W) afterwards, with the input beams' fp32 ``scores_in`` [B * Win].
+
+    Caller-owned state and outputs, all on the device: ``pool`` = (score fp32, end int32, parent int32, each [B, W]; count int32
+    [B]), ``done`` uint8 [B] (count and done zeroed before step 0); ``scores_out`` fp32, ``next_token`` int64, ``parent`` int32,
+    ``src_row`` int32, each [B * W]; ``scratch`` int64 with at least B * Win * 2W elements.  Returns None."""
+    ps, pe, pp, pc = pool
+    _need_cuda(logits, scores_in, ps, pe, pp, pc, done, scores_out, next_token, parent, src_row, scratch)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("beam_step: logits must be fp32 [B * Win, V] with unit column stride")
+    W = int(num_beams)
+    rows, V = logits.shape
+    Win = 1 if int(step) == 0 else W
+    if W < 1 or rows % Win:
+        raise ValueError(f"beam_step: {rows} logits rows are not a multiple of Win = {Win}")
+    B = rows // Win
+    for name, t, dt, n in (("scores_in", scores_in, torch.float32, B * Win), ("scores_out", scores_out, torch.float32, B * W),
+                           ("next_token", next_token, torch.int64, B * W), ("parent", parent, torch.int32, B * W),
+                           ("src_row", src_row, torch.int32, B * W), ("pool score", ps, torch.float32, B * W),
+                           ("pool end", pe, torch.int32, B * W), ("pool parent", pp, torch.int32, B * W),
+                           ("pool count", pc, torch.int32, B), ("done", done, torch.uint8, B)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise TypeError(f"beam_step: {name} must be a contiguous {dt} tensor of {n} elements")
+    if scratch.dtype != torch.int64 or not scratch.is_contiguous() or scratch.numel() < B * Win * 2 * W:
+        raise TypeError(f"beam_step: scratch must be a contiguous int64 tensor of at least {B * Win * 2 * W} elements")
+    a = H.BeamArgs()
+    a.early_stopping = int(bool(early_stopping))
+    a.logits, a.ld, a.B, a.Win, a.W, a.V = logits.data_ptr(), (logits.stride(0) if rows > 1 else max(logits.stride(0), V)), B, Win, W, V
+    a.step, a.length_penalty = int(step), float(length_penalty)
+    a.eos_id, a.pad_id = (-1 if eos_token_id is None else int(eos_token_id)), int(pad_token_id)
+    a.scores_in, a.scores_out = scores_in.data_ptr(), scores_out.data_ptr()
+    a.next_token, a.parent, a.src_row = next_token.data_ptr(), parent.data_ptr(), src_row.data_ptr()
+    a.pool_score, a.pool_end, a.pool_parent, a.pool_count = ps.data_ptr(), pe.data_ptr(), pp.data_ptr(), pc.data_ptr()
+    a.done, a.scratch = done.data_ptr(), scratch.data_ptr()
+    H.check(H.load().kx_beam_step(C.byref(a), _stream()), "kx_beam_step")
+
+
+def beam_finalize(scores_live, done, pool, parent, token, n, *, num_return_sequences=1, length_penalty=1.0, eos_token_id=None,
+                  pad_token_id=1, out_tokens=None, out_scores=None):
+    """kx_beam_finalize: offer the live beams of the rows that are not done to the pool, then backtrack the R best hypotheses of
+    every row through the ``parent`` int32 / ``token`` int64 [>= n, B * W] backpointers of ``n`` steps.
+    Returns (out_tokens int64 [B, R, >= n] — columns 0:n written —, out_scores fp32 [B, R])."""
+    ps, pe, pp, pc = pool
+    _need_cuda(scores_live, done, ps, pe, pp, pc, parent, token, out_tokens, out_scores)
+    B, W = ps.shape
+    R, n = int(num_return_sequences), int(n)
+    if (parent.dtype != torch.int32 or token.dtype != torch.int64 or parent.dim() != 2 or tuple(parent.shape) != tuple(token.shape)
+            or parent.shape[0] < n or parent.shape[1] != B * W or not (parent.is_contiguous() and token.is_contiguous())):
+        raise TypeError(f"beam_finalize: parent int32 / token int64 must be contiguous [>= {n}, {B * W}] tensors")
+    for name, t, dt, m in (("scores_live", scores_live, torch.float32, B * W), ("done", done, torch.uint8, B),
+                           ("pool score", ps, torch.float32, B * W), ("pool end", pe, torch.int32, B * W),
+                           ("pool parent", pp, torch.int32, B * W), ("pool count", pc, torch.int32, B)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != m:
+            raise TypeError(f"beam_finalize: {name} must be a contiguous {dt} tensor of {m} elements")
+    if out_tokens is None:
+        out_tokens = torch.empty((B, max(R, 1), n), dtype=torch.int64, device=ps.device)
+    if out_scores is None:
+        out_scores = torch.empty((B, max(R, 1)), dtype=torch.float32, device=ps.device)
+    if (out_tokens.dtype != torch.int64 or not out_tokens.is_contiguous() or out_tokens.dim() != 3
+            or tuple(out_tokens.shape[:2]) != (B, R) or out_scores.dtype != torch.float32 or not out_scores.is_contiguous()
+            or tuple(out_scores.shape) != (B, R)):
+        raise TypeError(f"beam_finalize: out_tokens int64 [{B}, {R}, >= n] and out_scores fp32 [{B}, {R}], contiguous")
+    H.check(H.load().kx_beam_finalize(scores_live.data_ptr(), done.data_ptr(), ps.data_ptr(), pe.data_ptr(), pp.data_ptr(),
+                                      pc.data_ptr(), parent.data_ptr(), token.data_ptr(), parent.shape[1], B, W, R, n,
+                                      float(length_penalty), -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id),
+                                      out_tokens.data_ptr(), out_tokens.shape[2], out_scores.data_ptr(), _stream()),
+            "kx_beam_finalize")
+    return out_tokens, out_scores
+
+
+def kv_cache_gather(src_k, src_v, dst_k, dst_v, t, src_row, error_word):
+    """kx_kv_cache_gather: dst[l, r, h, :t] = src[l, src_row[r], h, :t] for the two caches ([L, B, heads, Tmax, 64], fp32 or bf16,
+    contiguous), ``src_row`` int32 [B_dst] on the device.  An entry outside [0, B_src) copies nothing for that row and sets
+    KX_RAGGED_ERR_GATHER in ``error_word`` (int32 [1], sticky).  src and dst must not overlap."""
+    _need_cuda(src_k, src_v, dst_k, dst_v, src_row, error_word)
+    L, Bs, nh, Tmax, hd = src_k.shape
+    Bd = dst_k.shape[1]
+    if hd != 64 or tuple(src_v.shape) != tuple(src_k.shape) or tuple(dst_k.shape) != (L, Bd, nh, Tmax, 64) or tuple(dst_v.shape) != tuple(dst_k.shape):
+        raise ValueError("kv_cache_gather: caches are [L, B, heads, Tmax, 64], k and v alike, src and dst differing in B only")
+    if len({src_k.dtype, src_v.dtype, dst_k.dtype, dst_v.dtype}) != 1 or src_k.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("kv_cache_gather: the four caches share one dtype, fp32 or bf16")
+    if not all(c.is_contiguous() for c in (src_k, src_v, dst_k, dst_v)):
+        raise ValueError("kv_cache_gather: the caches must be contiguous")
+    if src_row.dtype != torch.int32 or tuple(src_row.shape) != (Bd,) or not src_row.is_contiguous():
+        raise TypeError(f"kv_cache_gather: src_row must be a contiguous int32 [{Bd}] tensor")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError("kv_cache_gather: error_word must be an int32 [1] tensor on the device (the kernel's sticky word)")
+    H.check(H.load().kx_kv_cache_gather(src_k.data_ptr(), src_v.data_ptr(), dst_k.data_ptr(), dst_v.data_ptr(), L, Bs, Bd, nh,
+                                        Tmax, int(t), src_k.element_size(), src_row.data_ptr(), error_word.data_ptr(), _stream()),
+            "kx_kv_cache_gather")

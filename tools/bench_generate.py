@@ -11,7 +11,12 @@ One JSON line per batch size.  --only a|b|c restricts the run to one variant (fo
   (r) generate(prompt_lengths=lengths): ms per token after the (same-shape) prefill, and tokens per second of the whole call;
   (s) one generate() per row over its own unpadded prompt — what a caller with unequal prompts had to do before: tokens per
       second over all B calls, prefills included.
---only a|r|s restricts the run."""
+--only a|r|s restricts the run.
+
+--num-beams W: the beam-search leg alone.  Per batch size B, alternating, best of --reps each:
+  (w) generate(num_beams=W) at B rows: ms per token after the prefill (beam step + cache gather + decode step at B * W rows);
+  (p) plain greedy generate() at B * W rows — the decode step of the same width without the search.
+--only w|p restricts the run (for a kernel trace of one variant)."""
 import argparse, json, os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -30,9 +35,10 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--only", default=None)
 ap.add_argument("--ragged", action="store_true")
 ap.add_argument("--min-prefix", type=int, default=16)
+ap.add_argument("--num-beams", type=int, default=0)
 a = ap.parse_args()
 if a.only is None:
-    a.only = "ars" if a.ragged else "abc"
+    a.only = "wp" if a.num_beams else "ars" if a.ragged else "abc"
 dev = torch.device("cuda", 0)
 V = 32002
 m = KosmosLanguage(vocab_size=V, dim=2048, _seed=0).eval().to(dev)
@@ -102,6 +108,44 @@ def timed(fn, arg):
             best = dt if best is None else min(best, dt)
     return best
 
+
+def beam_leg():
+    W = a.num_beams
+    for B in (int(b) for b in a.batches.split(",")):
+        wide = torch.randint(0, V, (B * W, a.prefix), generator=torch.Generator().manual_seed(0)).to(dev)
+        tok = wide[:B].contiguous()
+        mk = lambda rows: (lambda t: m(t, incremental_state={"max_len": a.prefix + a.new}), rows)
+        runs = {"w": (lambda t: m.generate(t, a.new, num_beams=W), tok), "p": (lambda t: m.generate(t, a.new), wide)}
+        pre = {"w": timed(*mk(tok)), "p": timed(*mk(wide))}
+        best = {}
+        for rep in range(a.reps):                               # alternating, so that both see the same clocks
+            for k in a.only:
+                dt = timed_once(*runs[k], warm=rep == 0)
+                best[k] = min(best.get(k, dt), dt)
+        res = {"workload": f"KosmosLanguage beam search, B={B}, num_beams={W}, prefix {a.prefix}, {a.new} new tokens, {a.precision}"}
+        if "w" in best:
+            res["w_beam_ms_per_token"] = round((best["w"] - pre["w"]) / (a.new - 1) * 1e3, 4)
+            res["w_prefill_ms"] = round(pre["w"] * 1e3, 3)
+        if "p" in best:
+            res[f"p_greedy_b{B * W}_ms_per_token"] = round((best["p"] - pre["p"]) / (a.new - 1) * 1e3, 4)
+            res["p_prefill_ms"] = round(pre["p"] * 1e3, 3)
+        print(json.dumps(res), flush=True)
+
+
+def timed_once(fn, arg, warm=False):
+    for rep in range(2 if warm else 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(arg)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    return dt
+
+
+if a.num_beams:
+    with torch.no_grad():
+        beam_leg()
+    sys.exit(0)
 
 with torch.no_grad():
     for B in (int(b) for b in a.batches.split(",")):
