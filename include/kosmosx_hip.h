@@ -275,11 +275,15 @@ int kx_pair_split_errors(unsigned* word_out);
  * Q is expected pre-scaled (and XPos-rotated) by the producing GEMM epilogue.
  * nan_to_num (torchscale applies torch.nan_to_num to the scores before the mask; HF CLIP and flamingo do not): reproduced
  * where it can matter — KX_ATTN_CAUSAL launches (the decoder's self-attention) and kx_attention_decode in KX_PREC_F32, whose
- * operands span the fp32 range: NaN -> 0, +-inf -> +-FLT_MAX, then mask and softmax (tests/test_xpos_kat_gpu.py pins it on
- * an overflowing score row against the torch statement).  KX_PREC_F16 / KX_PREC_F16C operands saturate at +-65504, so a
- * score cannot leave the fp32 range from finite inputs (|s| <= 64 * 65504^2).  DIVERGENCE: KX_PREC_BF16 operands do span
+ * operands span the fp32 range: NaN -> 0, +-inf -> +-FLT_MAX, then mask and softmax (tests/test_xpos_kat_gpu.py pins it for
+ * kx_attention on an overflowing score row against the torch statement, tests/test_attention_decode_gpu.py for
+ * kx_attention_decode against the float64 reference of tests/decode_ref.py).  KX_PREC_F16 / KX_PREC_F16C operands saturate at
+ * +-65504, so a score cannot leave the fp32 range from finite inputs (|s| <= 64 * 65504^2); kx_attention_decode in
+ * KX_PREC_F16C reads the fp32 cache and clamps like KX_PREC_F32.  DIVERGENCE: KX_PREC_BF16 operands do span
  * the fp32 range and that kernel does not clamp — an overflowing bf16 score row yields NaN where the reference yields a
  * one-hot row (bf16 is the throughput mode outside the north star's tolerance; the parity modes are fp32 / f16c / mixed).
+ * DIVERGENCE: the same holds for kx_attention_decode on the bf16 cache (KX_PREC_BF16): no nan_to_num, an overflowing or NaN
+ * score gives a NaN output row for that head.
  *   q: [B, Tq, H, 64] with element strides (q_batch_stride, q_row_stride), head h at +h*64.
  *   k, v: [B, Tk, H, 64] with (kv_batch_stride, kv_row_stride).   dtype of `prec`.
  *   out: [B, Tq, H*64] contiguous rows of out_row_stride elements, dtype odt. */
@@ -632,7 +636,9 @@ int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const int64_t* to
  *
  * kx_kv_cache_gather — dst[l, r, h, 0:t, :] = src[l, src_row[r], h, 0:t, :] for both caches ([L, B, heads, Tmax, 64], elem_bytes
  * = 4 for the fp32 / f16c cache, 2 for the bf16 cache; 16-byte aligned), src_row [B_dst] int32 ON THE DEVICE.  Rows at and after t
- * of dst are not written.  src and dst must not overlap (KX_ERR_INVALID_ARG, nothing launched).  A src_row entry outside
+ * of dst are not written.  Under tuning key 9 = 1 the caches are [L, B, Tmax, heads, 64] and the copy is dst[l, r, 0:t, :, :] =
+ * src[l, src_row[r], 0:t, :, :]: the first t rows of heads * 64 elements per (layer, sequence); the key is read at the call, like
+ * the prefill and the steps read it.  src and dst must not overlap (KX_ERR_INVALID_ARG, nothing launched).  A src_row entry outside
  * [0, B_src) makes that row copy nothing and ORs KX_RAGGED_ERR_GATHER into the sticky *error_word (see "Ragged batches"). */
 typedef struct {
   uint32_t struct_bytes;                      /* = sizeof(kx_beam_args) of the caller ("stale binding" otherwise) */

@@ -238,6 +238,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(const float* __restrict__ 
 }
 
 // one 16-byte vector per thread and iteration; a (layer, row, head) chunk of copy_vecs vectors is contiguous on both sides
+// (`heads` = chunks per (layer, row): 1 under the row-major cache layout, whose chunk is the first t rows of every head)
 __global__ __launch_bounds__(256) void kv_gather_kernel(const uint4* __restrict__ sk, const uint4* __restrict__ sv,
                                                         uint4* __restrict__ dk, uint4* __restrict__ dv,
                                                         const int* __restrict__ src_row, int B_src, int B_dst, int heads,
@@ -346,13 +347,17 @@ extern "C" int kx_kv_cache_gather(const void* src_k, const void* src_v, void* ds
              !ranges_overlap(src_v, sn, dst_k, dn) && !ranges_overlap(src_v, sn, dst_v, dn) && !ranges_overlap(dst_k, dn, dst_v, dn),
              "kx_kv_cache_gather: src and dst caches overlap (the gather is not an in-place permutation)");
   if (t == 0) return KX_OK;
-  const long long vpp = (long long)(pos_bytes / 16);
-  const long long row_vecs = Tmax * vpp, copy_vecs = t * vpp, total = L * B_dst * heads * copy_vecs;
+  // head-major [heads][Tmax][64]: one chunk per (layer, sequence, head); tuning key 9 = 1, [Tmax][heads*64]: the first t rows
+  // of heads*64 elements are ONE contiguous chunk per (layer, sequence)
+  const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;
+  const long long chunks = head_major ? heads : 1;
+  const long long vpp = (long long)(pos_bytes / 16) * (head_major ? 1 : heads);
+  const long long row_vecs = Tmax * vpp, copy_vecs = t * vpp, total = L * B_dst * chunks * copy_vecs;
   const long long blocks = (total + 255) / 256;
   KxProfScope prof(KX_K_MISC, L * B_dst * heads, t, elem_bytes, (hipStream_t)stream);
   hipLaunchKernelGGL(kv_gather_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                      (const uint4*)src_k, (const uint4*)src_v, (uint4*)dst_k, (uint4*)dst_v, (const int*)src_row, (int)B_src,
-                     (int)B_dst, (int)heads, row_vecs, copy_vecs, total, (int*)error_word);
+                     (int)B_dst, (int)chunks, row_vecs, copy_vecs, total, (int*)error_word);
   KX_CHECK_LAUNCH("kx_kv_cache_gather");
   return KX_OK;
 }

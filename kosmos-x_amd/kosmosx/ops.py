@@ -459,17 +459,25 @@ def step_prepare(tokens, embed, pos, positions, tables=None, pos_shift=0, error_
     return out, (xpos_rows if tables is not None else None), error_word
 
 
-def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=None, out_dtype="f32", stats_out=None):
+def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=None, out_dtype="f32", stats_out=None,
+                     layout="head_major"):
     """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
     The decode step's single-query attention + cache append (kx_attention_decode / kx_attention_decode_ragged).
     qkv [B, 3 * H * 64] fp32 or bf16 rows of the new token; kcache / vcache [B, H, Tmax, 64] of the same dtype (updated in place).
     ``t``: every sequence at host position t; ``positions`` [B] int32 on the device: sequence b at positions[b], a position
     outside the cache sets KX_RAGGED_ERR_CACHE in ``error_word`` (int32 [1], sticky).  out_dtype "f32" | "bf16" | "f16c" | "f16p"
-    (the KX_F16C / KX_F16P operand rows of the fp32 step).  Returns the attention output rows."""
+    (the KX_F16C / KX_F16P operand rows of the fp32 step).  Returns the attention output rows.
+    ``layout`` "row_major": the caches are [B, Tmax, H, 64], the layout the library reads under tuning key 9 = 1.  The argument
+    only names the shape that is checked; the caller sets the key (kx_set_tuning(9, 1)) around the call."""
     _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out)
-    B, Hh, Tmax, hd = kcache.shape
-    if hd != 64 or tuple(qkv.shape) != (B, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
-        raise ValueError("attention_decode: qkv [B, 3*H*64], caches [B, H, Tmax, 64], contiguous")
+    if layout not in ("head_major", "row_major"):
+        raise ValueError("attention_decode: layout is 'head_major' or 'row_major'")
+    if layout == "row_major":
+        B, Tmax, Hh, hd = kcache.shape
+    else:
+        B, Hh, Tmax, hd = kcache.shape
+    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (B, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError("attention_decode: qkv [B, 3*H*64], caches [B, H, Tmax, 64] ([B, Tmax, H, 64] row-major), contiguous")
     if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("attention_decode: qkv and the caches share one dtype, fp32 or bf16")
     D = Hh * 64
@@ -568,14 +576,21 @@ def beam_finalize(scores_live, done, pool, parent, token, n, *, num_return_seque
     return out_tokens, out_scores
 
 
-def kv_cache_gather(src_k, src_v, dst_k, dst_v, t, src_row, error_word):
+def kv_cache_gather(src_k, src_v, dst_k, dst_v, t, src_row, error_word, layout="head_major"):
     """kx_kv_cache_gather: dst[l, r, h, :t] = src[l, src_row[r], h, :t] for the two caches ([L, B, heads, Tmax, 64], fp32 or bf16,
     contiguous), ``src_row`` int32 [B_dst] on the device.  An entry outside [0, B_src) copies nothing for that row and sets
-    KX_RAGGED_ERR_GATHER in ``error_word`` (int32 [1], sticky).  src and dst must not overlap."""
+    KX_RAGGED_ERR_GATHER in ``error_word`` (int32 [1], sticky).  src and dst must not overlap.
+    ``layout`` "row_major": the tensors are shaped [L, B, Tmax, heads, 64] (dst[l, r, :t] = src[l, src_row[r], :t]), the layout
+    the library copies under tuning key 9 = 1; the argument only names the shape that is checked, the caller sets the key."""
     _need_cuda(src_k, src_v, dst_k, dst_v, src_row, error_word)
-    L, Bs, nh, Tmax, hd = src_k.shape
+    if layout not in ("head_major", "row_major"):
+        raise ValueError("kv_cache_gather: layout is 'head_major' or 'row_major'")
+    if layout == "row_major":
+        L, Bs, Tmax, nh, hd = src_k.shape
+    else:
+        L, Bs, nh, Tmax, hd = src_k.shape
     Bd = dst_k.shape[1]
-    if hd != 64 or tuple(src_v.shape) != tuple(src_k.shape) or tuple(dst_k.shape) != (L, Bd, nh, Tmax, 64) or tuple(dst_v.shape) != tuple(dst_k.shape):
+    if hd != 64 or tuple(src_v.shape) != tuple(src_k.shape) or tuple(dst_k.shape) != (L, Bd, *src_k.shape[2:]) or tuple(dst_v.shape) != tuple(dst_k.shape):
         raise ValueError("kv_cache_gather: caches are [L, B, heads, Tmax, 64], k and v alike, src and dst differing in B only")
     if len({src_k.dtype, src_v.dtype, dst_k.dtype, dst_v.dtype}) != 1 or src_k.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("kv_cache_gather: the four caches share one dtype, fp32 or bf16")

@@ -210,3 +210,41 @@ def test_kv_cache_gather(dtype, t):
     with pytest.raises(RuntimeError, match="overlap"):
         ops.kv_cache_gather(sk, sv, whole[0], whole[0], t, idx, err)                       # dst_k is dst_v
     assert bool((whole == -3.0).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("t", [0, 1, 7, 10])
+def test_kv_cache_gather_row_major_layout(dtype, t):
+    """Tuning key 9 = 1: the caches are [L, B, Tmax, heads, 64] and dst[l, r, :t] = src[l, src_row[r], :t] — the first t rows of
+    heads * 64 elements per (layer, sequence).  (Copying rows 0:t of [L, B, heads, Tmax, 64] there moves the wrong memory.)
+    Distinct values everywhere in src, so a row taken from another head, position or sequence shows."""
+    L, Bs, Bd, nh, Tmax = 2, 2, 6, 3, 10
+    g = torch.Generator().manual_seed(t)
+    sk, sv = (torch.randn((L, Bs, Tmax, nh, 64), generator=g).to(dtype).cuda() for _ in range(2))
+    dk, dv = (torch.full((L, Bd, Tmax, nh, 64), -3.0, dtype=dtype, device="cuda") for _ in range(2))
+    idx = torch.tensor([1, 0, 0, 1, 1, 0], dtype=torch.int32, device="cuda")
+    bad = torch.tensor([1, 2, 0, -1, 1, 0], dtype=torch.int32, device="cuda")
+    err = torch.zeros(1, dtype=torch.int32, device="cuda")
+    lib = H.load()
+    lib.kx_set_tuning(9, 1)
+    try:
+        ops.kv_cache_gather(sk, sv, dk, dv, t, idx, err, layout="row_major")
+        for src, dst in ((sk, dk), (sv, dv)):
+            assert torch.equal(dst[:, :, :t], src.index_select(1, idx.long())[:, :, :t])
+            assert bool((dst[:, :, t:] == -3.0).all())                      # rows at and after t are not written
+        assert int(err.item()) == 0
+        # an out-of-range source row copies nothing for that row and raises the sticky bit
+        dk.fill_(-3.0), dv.fill_(-3.0)
+        ops.kv_cache_gather(sk, sv, dk, dv, t, bad, err, layout="row_major")
+        ok = [0, 2, 4, 5]
+        for src, dst in ((sk, dk), (sv, dv)):
+            assert torch.equal(dst[:, ok, :t], src.index_select(1, bad[ok].long())[:, :, :t])
+            assert bool((dst[:, [1, 3]] == -3.0).all()) and bool((dst[:, :, t:] == -3.0).all())
+        assert int(err.item()) == (H.KX_RAGGED_ERR_GATHER if t > 0 else 0)
+        # overlapping buffers: an error code, nothing launched
+        whole = torch.full((2, L, Bd, Tmax, nh, 64), -3.0, dtype=dtype, device="cuda")
+        with pytest.raises(RuntimeError, match="overlap"):
+            ops.kv_cache_gather(whole[0], whole[1], whole[0], whole[1], t, idx, err, layout="row_major")
+        assert bool((whole == -3.0).all())
+    finally:
+        lib.kx_set_tuning(9, 0)

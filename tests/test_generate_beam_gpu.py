@@ -214,3 +214,25 @@ def test_repeatable_and_the_default_path_is_untouched():
             logits = lm.decoder._forward_incremental(tok, state, None, lm.precision)
             want = generation.generate_loop(lm.decoder, lm.precision, state, logits, tok.long(), 12, **extra)
         assert torch.equal(got, want) and torch.equal(got, lm.generate(tok, 12, **extra))
+
+
+@pytest.mark.parametrize("prec", ["fp32", "mixed", "bf16"])
+def test_beam_search_under_the_row_major_cache_layout(prec):
+    """Tuning key 9 = 1 (caches [Tmax][heads*64] per sequence): prefill, decode steps and kx_kv_cache_gather all read the key, so
+    the search returns the tokens and scores of the default layout — every step's arithmetic is the same on the same values."""
+    from kosmosx import _hip
+    tok = torch.randint(0, 502, (3, 9), generator=torch.Generator().manual_seed(4)).cuda()
+    lib = _hip.load()
+    res = []
+    for key in (0, 1):
+        lm = _lm(seed=7).to("cuda")
+        lm.precision = prec
+        lib.kx_set_tuning(9, key)
+        try:
+            seqs, scores = lm.generate(tok, 20, num_beams=4, num_return_sequences=4, output_scores=True)
+            torch.cuda.synchronize()
+        finally:
+            lib.kx_set_tuning(9, 0)
+        res.append((seqs.cpu(), scores.cpu()))
+    assert res[0][0].shape == (3, 4, 20) and bool(torch.isfinite(res[0][1]).all())
+    assert torch.equal(res[1][0], res[0][0]) and torch.equal(res[1][1], res[0][1])
