@@ -410,7 +410,7 @@ typedef enum {
   KX_STRUCT_GEMM_ARGS = 0, KX_STRUCT_ATTN_ARGS = 1, KX_STRUCT_VIT_LAYER = 2, KX_STRUCT_VIT_WEIGHTS = 3,
   KX_STRUCT_PERCEIVER_LAYER = 4, KX_STRUCT_PERCEIVER_WEIGHTS = 5, KX_STRUCT_DECODER_LAYER = 6,
   KX_STRUCT_DECODER_WEIGHTS = 7, KX_STRUCT_RESAMPLE_PLAN = 8, KX_STRUCT_PROF_RECORD = 9, KX_STRUCT_SAMPLE_ARGS = 10,
-  KX_STRUCT_BEAM_ARGS = 11, KX_STRUCT_COUNT = 12
+  KX_STRUCT_BEAM_ARGS = 11, KX_STRUCT_CONSTRAIN_ARGS = 12, KX_STRUCT_COUNT = 13
 } kx_struct_id;
 /* sizeof() of the struct as this library was compiled; 0 for an unknown id.  Pure host arithmetic. */
 size_t kx_struct_bytes(int32_t id);
@@ -664,6 +664,54 @@ int kx_beam_finalize(const float* scores_live, const uint8_t* done, float* pool_
 int kx_kv_cache_gather(const void* src_k, const void* src_v, void* dst_k, void* dst_v, int64_t L, int64_t B_src, int64_t B_dst,
                        int64_t heads, int64_t Tmax, int64_t t, int32_t elem_bytes, const int32_t* src_row, int32_t* error_word,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Constraints on what may be emitted and when a row stops (added within ABI 7: one struct, one function and one kx_struct_id
+ * value are appended; no existing layout moves, so kx_version() stays 7).
+ *
+ * kx_constrain_logits: one launch, one 256-thread workgroup per row, issued BEFORE kx_sample_logits or kx_beam_step on the fp32
+ * rows logits [B, V] (any ld >= V) that launch is about to read.  It edits the rows in place: a banned id's logit becomes -inf and
+ * nothing else is written.  The sampler never selects -inf (its rule 6) and to kx_beam_step -inf is never a candidate, so neither
+ * kernel changes.  Bans commute with the repetition penalty (-inf * r == -inf == -inf / r), so constrain-then-sample is the
+ * `transformers` order (processors, then warpers).  A row whose every logit is banned falls under the sampler's rule 6: it emits
+ * pad_id and is finished.
+ *
+ * Row b's LOGICAL token sequence s (length n) is read from history [B, hist_ld] int64, the buffer kx_sample_logits appends to, of
+ * which hist_len physical columns are in use: columns [0, hist_len) when prompt_lens is NULL; otherwise (the ragged batch) columns
+ * [0, prompt_lens[b]) followed by [prompt_width, hist_len) — the columns in between are right padding (copies of the row's first
+ * token) and take part in no match.  history may be NULL with hist_len = 0 (n = 0: the history-free constraints only, as under
+ * beam search).  g = new_tokens is the number of tokens already generated, a host scalar common to all rows.  Per row, in order:
+ *   1. a row with finished[b] != 0 is left untouched;
+ *   2. stop: if g >= 1 and some stop sequence is a suffix of s, finished[b] = 1 and the row gets no bans (the sampler that follows
+ *      emits pad_id: the output keeps the stop sequence and is padded after it, as after an EOS).  The sequence may begin inside
+ *      the prompt; g >= 1 makes its last token a generated one;
+ *   3. no-repeat n-gram (ngram = N >= 1; 0 = off): for every i with i + N - 1 < n and s[i : i+N-1] == s[n-N+1 : n], ban s[i+N-1];
+ *      nothing when n + 1 < N; N = 1 bans every id of s (NoRepeatNGramLogitsProcessor);
+ *   4. bad words: a sequence w of m ids bans w[0] when m == 1, else w[m-1] when n >= m - 1 and s[n-m+1 : n] == w[0 : m-1]
+ *      (NoBadWordsLogitsProcessor);
+ *   5. minimum length: g < min_new and eos_id >= 0 bans eos_id (MinNewTokensLengthLogitsProcessor);
+ *   6. range: an id outside [0, V) — in the history or in a sequence — is compared as a value and never used as an index, and a
+ *      prompt_lens[b] outside [0, prompt_width] is clamped into it: memory safety does not depend on the device data.
+ * Bad and stop sequences are CSR tables on the device: ids int64 and offsets int32 [n + 1].  The offsets are ALSO passed as a host
+ * array (*_off_host, the same n + 1 values) so that the limits are checked before the launch; the kernel skips any device entry
+ * that disagrees with them (a length outside 1..64 or an offset outside [0, off_host[n]]).
+ * The workgroup stages the last 64 ids of s in LDS (what a 64-id suffix, a 63-id n-gram prefix or bad-word prefix can need); threads
+ * stride over the n-gram start positions and over the sequences.  Several threads may store the same -inf to one address.
+ * Limits (KX_ERR_UNSUPPORTED, before any launch): ngram <= 64; every bad or stop sequence 1..64 ids long.  Argument errors name the
+ * argument.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_constrain_args) of the caller ("stale binding" otherwise) */
+  int32_t ngram;                              /* 0 = off */
+  float* logits; int64_t ld; int64_t B; int64_t V;
+  const int64_t* history; int64_t hist_ld; int64_t hist_len;    /* hist_ld > hist_len: the sampler appends after this launch */
+  int64_t prompt_width; const int32_t* prompt_lens;             /* [B] device or NULL */
+  int64_t new_tokens;
+  const int64_t* bad_ids; const int32_t* bad_off; const int32_t* bad_off_host; int64_t n_bad;
+  const int64_t* stop_ids; const int32_t* stop_off; const int32_t* stop_off_host; int64_t n_stop;
+  int64_t min_new; int64_t eos_id;            /* eos_id < 0 = none */
+  uint8_t* finished;                          /* [B] in/out, may be NULL */
+} kx_constrain_args;
+int kx_constrain_logits(const kx_constrain_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before

@@ -304,6 +304,7 @@ extern "C" size_t kx_struct_bytes(int32_t id) {
     case KX_STRUCT_PROF_RECORD: return sizeof(kx_prof_record);
     case KX_STRUCT_SAMPLE_ARGS: return sizeof(kx_sample_args);
     case KX_STRUCT_BEAM_ARGS: return sizeof(kx_beam_args);
+    case KX_STRUCT_CONSTRAIN_ARGS: return sizeof(kx_constrain_args);
     default: return 0;
   }
 }

@@ -156,6 +156,19 @@ class BeamArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class ConstrainArgs(C.Structure):
+    """kx_constrain_args; struct_bytes is filled in at construction ("stale binding" check of kx_constrain_logits)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("ngram", i32), ("logits", vp), ("ld", i64), ("B", i64), ("V", i64),
+                ("history", vp), ("hist_ld", i64), ("hist_len", i64), ("prompt_width", i64), ("prompt_lens", vp),
+                ("new_tokens", i64), ("bad_ids", vp), ("bad_off", vp), ("bad_off_host", vp), ("n_bad", i64),
+                ("stop_ids", vp), ("stop_off", vp), ("stop_off_host", vp), ("n_stop", i64), ("min_new", i64), ("eos_id", i64),
+                ("finished", vp)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -199,6 +212,7 @@ SYMBOLS = {
     "kx_beam_step": (C.c_int, [C.POINTER(BeamArgs), vp]),
     "kx_beam_finalize": (C.c_int, [vp] * 8 + [i64] * 5 + [f32, i64, i64, vp, i64, vp, vp]),
     "kx_kv_cache_gather": (C.c_int, [vp] * 4 + [i64] * 6 + [i32, vp, vp, vp]),
+    "kx_constrain_logits": (C.c_int, [C.POINTER(ConstrainArgs), vp]),
     "kx_decoder_forward": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, i32, vp,
                                      C.c_size_t, i32, vp]),
     "kx_clip_preprocess_workspace_bytes": (C.c_size_t, [i64, i32, i32]),
@@ -239,7 +253,7 @@ SYMBOLS = {
 
 
 STRUCT_IDS = [GemmArgs, AttnArgs, VitLayer, VitWeights, PerceiverLayer, PerceiverWeights, DecoderLayer, DecoderWeights,
-              ResamplePlan, ProfRecord, SampleArgs, BeamArgs]  # index = kx_struct_id
+              ResamplePlan, ProfRecord, SampleArgs, BeamArgs, ConstrainArgs]  # index = kx_struct_id
 
 
 def lib_path() -> Path:

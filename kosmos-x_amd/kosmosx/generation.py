@@ -13,8 +13,14 @@ of every batch row, keeps the pool of finished hypotheses and the row's done byt
 device memory; kx_kv_cache_gather re-parents the cache rows into the other of two B * num_beams-row caches; the decode step is the
 uniform one at B * num_beams rows.  kx_beam_finalize backtracks the best hypotheses after the last step.
 
+Constraints (``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens``, ``stop_sequences``): one kx_constrain_logits launch
+in front of the sampler (or the beam step) sets the banned ids' logits to -inf in place and marks rows that met a stop sequence
+finished; the sampler and the beam step already never pick -inf.  It reads the history buffer the sampler appends to, so the token
+still never leaves the device.  With every constraint at its default the launch is not issued.
+
 Not offered: compaction of finished rows, replaying the step as a captured graph, padding masks in
-``Decoder.forward`` (``self_attn_padding_mask``); with beams: ragged prompts, penalties and sampling.
+``Decoder.forward`` (``self_attn_padding_mask``); with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
+(n-grams, multi-token bad words, stop sequences).
 """
 from __future__ import annotations
 
@@ -28,22 +34,30 @@ from . import ops
 
 def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
-                  seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None):
+                  seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
+                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_tokens`` [B, Tt] int64: what the repetition penalty sees before the first new token.  ``pos_shift`` > 0: the
     prompt holds that many spliced rows that are not tokens and text rows carry two position rows (the multimodal prompt
     under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t].
     ``lengths`` (host ints, validated by resolve_prompt_lengths): the ragged batch — row b's sequence has lengths[b] <= T
-    positions (spliced rows included), the rest of its prompt is right padding whose ids mask_padding replaced."""
+    positions (spliced rows included), the rest of its prompt is right padding whose ids mask_padding replaced.
+    Constraints (check_constraint_args): kx_constrain_logits runs on the row immediately before each sampler launch.  Its
+    history is ``prompt_tokens`` followed by the generated tokens — the TEXT ids only: spliced image rows contribute no ids, so
+    an n-gram, a bad word or a stop sequence may span the splice point.  ``text_lengths`` (ragged batches; default ``lengths``):
+    row b's number of prompt TOKENS, where ``lengths`` counts the spliced rows too.  ``output_logits`` keeps returning the
+    model's own logits, taken before the bans."""
     B, T, V = logits.shape
     dev = logits.device
+    cons = check_constraint_args(V, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                                 min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(B, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
     history = None
     Tt = prompt_tokens.shape[1]
-    if float(repetition_penalty) != 1.0:
-        history = torch.empty((B, Tt + max_new_tokens), dtype=torch.int64, device=dev)
+    if float(repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"]):
+        history = torch.empty((B, Tt + max_new_tokens), dtype=torch.int64, device=dev)           # (the sampler appends with r == 1 too)
         history[:, :Tt] = prompt_tokens
     if sequence_ids is not None:
         sequence_ids = sequence_ids.to(device=dev, dtype=torch.int64).contiguous()
@@ -61,8 +75,20 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         err = state["error"]                                              # the step kernels' sticky error word
     else:
         row = logits[:, -1]                                               # [B, V] view, row stride T * V
+    if cons is not None:                                                  # the one upload: CSR tables and the rows' text lengths
+        bad, stop = (ops.SequenceTable(cons[k], dev) if cons[k] else None for k in ("bad", "stop"))
+        plens = None
+        if lengths is not None:
+            plens = torch.tensor(lengths if text_lengths is None else text_lengths, dtype=torch.int32, device=dev)
     n = 0
     for g in range(max_new_tokens):
+        if output_logits:
+            kept.append(row.clone())                                      # the model's own logits: before any ban (the sampler only reads the row)
+        if cons is not None and (cons["every_step"] or g < cons["min_new"]):
+            ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
+                                 prompt_lens=plens if history is not None else None, new_tokens=g,
+                                 no_repeat_ngram_size=cons["ngram"], bad_words=bad, stop_sequences=stop,
+                                 min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
         if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
@@ -73,12 +99,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                               do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
                               hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                               out=nxt, out_tokens=out, out_col=g)
-        if output_logits:
-            kept.append(row.clone())
         n = g + 1
         if n == max_new_tokens:
             break
-        if eos_token_id is not None and eos_poll > 0 and n % eos_poll == 0:
+        if (eos_token_id is not None or (cons is not None and cons["stop"])) and eos_poll > 0 and n % eos_poll == 0:
             if positions is None:
                 if bool(finished.all()):
                     break                                                 # the loop's only device-to-host read
@@ -102,6 +126,57 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
 
 
 MAX_BEAMS = 16
+MAX_NGRAM = MAX_SEQUENCE = 64           # kx_constrain_logits' limits
+
+
+def _check_sequences(name: str, seqs, vocab: int) -> list:
+    if seqs is None:
+        return []
+    if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__iter__"):
+        raise ValueError(f"{name} must be a list of non-empty lists of token ids, got {seqs!r}")
+    out = []
+    for k, s in enumerate(seqs):
+        try:
+            ids = [operator.index(t) for t in s]
+        except TypeError:
+            raise ValueError(f"{name}[{k}] must be a list of integer token ids, got {s!r}") from None
+        if not ids:
+            raise ValueError(f"{name}[{k}] is empty: a sequence holds at least one token id")
+        if len(ids) > MAX_SEQUENCE:
+            raise ValueError(f"{name}[{k}] holds {len(ids)} ids, more than {MAX_SEQUENCE}")
+        for t in ids:
+            if not 0 <= t < vocab:
+                raise ValueError(f"{name}[{k}] holds the id {t}, outside the vocabulary [0, {vocab})")
+        out.append(ids)
+    return out
+
+
+def check_constraint_args(vocab: int, *, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
+                          eos_token_id=None, num_beams=None):
+    """ValueError (naming the argument) for what generate() refuses of the constraint arguments, before anything is launched.
+    ``num_beams``: given (not None) when the call runs beam search, which offers the history-free constraints only.
+    Returns None when every constraint is at its default (no kx_constrain_logits launch is issued), else a dict: ngram, bad,
+    stop, min_new, reads_history (a history buffer is needed), every_step (something besides the minimum length is on)."""
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    if no_repeat_ngram_size > MAX_NGRAM:
+        raise ValueError(f"no_repeat_ngram_size = {no_repeat_ngram_size} exceeds {MAX_NGRAM}")
+    bad = _check_sequences("bad_words_ids", bad_words_ids, vocab)
+    stop = _check_sequences("stop_sequences", stop_sequences, vocab)
+    if min_new_tokens > 0 and eos_token_id is None:
+        raise ValueError(f"min_new_tokens = {min_new_tokens} needs an eos_token_id: it is the token the minimum length bans")
+    if num_beams is not None:
+        for name, on in (("no_repeat_ngram_size", no_repeat_ngram_size > 0), ("bad_words_ids", any(len(s) > 1 for s in bad)),
+                         ("stop_sequences", bool(stop))):
+            if on:
+                raise ValueError(f"{name}{' with more than one id per entry' if name == 'bad_words_ids' else ''} is not offered "
+                                 f"together with beam search (num_beams = {num_beams}): it needs a per-beam history; see DESIGN.md §7b")
+    if not (no_repeat_ngram_size or bad or stop or min_new_tokens):
+        return None
+    reads = bool(no_repeat_ngram_size or stop or any(len(s) > 1 for s in bad))
+    return dict(ngram=no_repeat_ngram_size, bad=bad, stop=stop, min_new=min_new_tokens, reads_history=reads,
+                every_step=bool(no_repeat_ngram_size or bad or stop))
 
 
 def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
@@ -137,12 +212,14 @@ def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_seq
 
 def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tokens: int, *, num_beams: int, pos_shift: int = 0,
               length_penalty=1.0, early_stopping=False, num_return_sequences=1, eos_token_id=None, pad_token_id=1, eos_poll=8,
-              output_scores=False, output_trace=False):
+              output_scores=False, output_trace=False, bad_words_ids=None, min_new_tokens=0):
     """Beam search after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (the prefill ran once per batch row).
     Per token: kx_beam_step on the rows the last step wrote (step 0: the B prefill rows, one input beam each), kx_kv_cache_gather
     of cache rows 0:t into the other B * W-row cache by the step's src_row, then the uniform decode step at B * W rows and
     the common host position.  Every buffer is allocated before the first step; the host reads ``done.all()`` at the stop poll
     and the gather's error word after the loop, nothing else.
+    ``bad_words_ids`` (single ids only) and ``min_new_tokens``: one kx_constrain_logits launch on the rows before the beam step,
+    with no history — and before the ``output_trace`` copy, so the trace holds what the beam step ranked.
     Returns tokens int64 [B, n] (R = 1) or [B, R, n], then the fp32 [B, R] scores with ``output_scores``, then the trace dict
     with ``output_trace`` (the contract: include/kosmosx_hip.h, "Beam search on the device")."""
     B, T, V = logits.shape
@@ -167,8 +244,13 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
     L, _, nh, Tmax, hd = src[0].shape
     caches = [tuple(torch.empty((L, BW, nh, Tmax, hd), dtype=src[0].dtype, device=dev) for _ in range(2)) for _ in range(2)]
     row = logits[:, -1]                                                      # [B, V] view, row stride T * V
+    cons = check_constraint_args(V, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, eos_token_id=eos_token_id,
+                                 num_beams=W)
+    bad = ops.SequenceTable(cons["bad"], dev) if cons is not None and cons["bad"] else None
     n = 0
     for g in range(N):
+        if cons is not None and (cons["every_step"] or g < cons["min_new"]):
+            ops.constrain_logits(row, new_tokens=g, bad_words=bad, min_new_tokens=cons["min_new"], eos_token_id=eos_token_id)
         if kept is not None:
             (kept[0].view(B, W, V)[:, 0] if g == 0 else kept[g]).copy_(row)
         ops.beam_step(row, zeros if g == 0 else score[g - 1], num_beams=W, step=g, pool=pool, done=done, scores_out=score[g],

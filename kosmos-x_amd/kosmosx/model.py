@@ -1174,7 +1174,8 @@ class Kosmos(nn.Module):
     def generate(self, text_tokens: torch.Tensor, images: torch.Tensor, max_new_tokens: int, *, do_sample=False,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1,
                  sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0,
-                 early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False):
+                 early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
+                 no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1191,7 +1192,14 @@ class Kosmos(nn.Module):
         sum_logprob / n ** ``length_penalty``; ``early_stopping``: a row stops as soon as it holds W finished hypotheses
         (otherwise once no live beam can still beat the worst of them).  ``output_scores``: also the fp32 [B, R] scores;
         ``output_trace`` (debug / tests): also a dict of the per-step device tensors.  Greedy only: sampling, the filters, the
-        repetition penalty, ``prompt_lengths``, ``sequence_ids`` and ``output_logits`` raise ValueError together with beams."""
+        repetition penalty, ``prompt_lengths``, ``sequence_ids`` and ``output_logits`` raise ValueError together with beams.
+        Constraints, applied on the device in front of the sampler (kx_constrain_logits; none of them by default):
+        ``no_repeat_ngram_size`` N: no N-gram of token ids occurs twice in prompt + output; ``bad_words_ids``: a list of
+        non-empty id lists that are never completed; ``min_new_tokens``: ``eos_token_id`` cannot be drawn before that many
+        tokens; ``stop_sequences`` (id lists, as ``bad_words_ids``): a row stops after generating one of them — the output
+        keeps it and is padded after it, as after an EOS.  All of them see the TEXT ids only (prompt, then output): the
+        spliced image rows contribute no ids, so an n-gram may span the splice point.  With beams: ``min_new_tokens`` and
+        single-id ``bad_words_ids`` only; the others need a per-beam history and raise ValueError."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1200,6 +1208,10 @@ class Kosmos(nn.Module):
             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
             prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
             output_trace=output_trace, beam_path=_beam_path)
+        generation.check_constraint_args(
+            self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
+            num_beams=num_beams if beams else None)
         _warn_train_mode(self)
         _require_cuda(text_tokens, "text_tokens")
         _require_cuda(images, "images")
@@ -1227,13 +1239,16 @@ class Kosmos(nn.Module):
                     self.decoder, prec, state, logits, max_new_tokens, num_beams=num_beams,
                     pos_shift=n_img if self.switches.u1_inplace_alias else 0, length_penalty=length_penalty,
                     early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
-                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace)
+                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace,
+                    bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens)
             return generation.generate_loop(
                 self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens,
                 pos_shift=n_img if self.switches.u1_inplace_alias else 0, do_sample=do_sample, temperature=temperature,
                 top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed, eos_token_id=eos_token_id,
                 pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll, output_logits=output_logits,
-                lengths=None if lens is None else [n_img + l for l in lens])
+                lengths=None if lens is None else [n_img + l for l in lens], text_lengths=lens,
+                no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
+                stop_sequences=stop_sequences)
 
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
@@ -1331,10 +1346,12 @@ class KosmosLanguage(nn.Module):
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
                  repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False):
+                 num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
+                 bad_words_ids=None, min_new_tokens=0, stop_sequences=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
-        arguments that go with it: beam search, as there)."""
+        arguments that go with it: beam search, as there; ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens`` and
+        ``stop_sequences``: the constraints, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1343,6 +1360,10 @@ class KosmosLanguage(nn.Module):
             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
             prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
             output_trace=output_trace, beam_path=_beam_path)
+        generation.check_constraint_args(
+            self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
+            num_beams=num_beams if beams else None)
         _warn_train_mode(self)
         _require_cuda(x, "x")
         if x.dim() != 2:
@@ -1368,12 +1389,14 @@ class KosmosLanguage(nn.Module):
                 return generation.beam_loop(
                     self.decoder, self.precision, state, logits, max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
                     early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
-                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace)
+                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace,
+                    bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens)
             return generation.generate_loop(
                 self.decoder, self.precision, state, logits, x.long(), max_new_tokens, do_sample=do_sample,
                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
                 eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-                output_logits=output_logits, lengths=lens)
+                output_logits=output_logits, lengths=lens, no_repeat_ngram_size=no_repeat_ngram_size,
+                bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences)
 
 
 class KosmosTokenizer:

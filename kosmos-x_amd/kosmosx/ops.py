@@ -420,6 +420,74 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     return (out, kept, mask) if return_debug else out
 
 
+class SequenceTable:
+    """A list of token-id sequences (``bad_words_ids`` / ``stop_sequences``) in the CSR form kx_constrain_logits reads: ``ids``
+    int64 and ``off`` int32 [n + 1] on the device, and the host copy of the offsets the library checks the limits on.  Built
+    once per generate() call (the one upload), passed to every ops.constrain_logits of the loop."""
+
+    def __init__(self, sequences, device):
+        seqs = [[int(t) for t in s] for s in sequences]
+        off = [0]
+        for s in seqs:
+            off.append(off[-1] + len(s))
+        self.n = len(seqs)
+        self.off_host = (C.c_int32 * len(off))(*off)
+        self.ids = torch.tensor([t for s in seqs for t in s] or [0], dtype=torch.int64, device=device)
+        self.off = torch.tensor(off, dtype=torch.int32, device=device)
+
+
+def constrain_logits(logits, *, history=None, hist_len=0, prompt_width=0, prompt_lens=None, new_tokens=0, no_repeat_ngram_size=0,
+                     bad_words=None, stop_sequences=None, min_new_tokens=0, eos_token_id=None, finished=None):
+    """Ban ids in every row of fp32 `logits` [B, V] (row stride >= V) IN PLACE, by one launch, before ops.sample_logits or
+    ops.beam_step reads them (kx_constrain_logits in include/kosmosx_hip.h): a banned id's logit becomes -inf, nothing else is
+    written.  No-repeat n-gram of size ``no_repeat_ngram_size``, ``bad_words`` and the minimum length (``eos_token_id`` is banned
+    while ``new_tokens`` < ``min_new_tokens``); a row whose sequence ends in one of ``stop_sequences`` after at least one new token
+    becomes finished and gets no bans.
+
+    history [B, > hist_len] int64: the buffer the sampler appends to, ``hist_len`` columns in use.  prompt_lens [B] int32 (device)
+    with ``prompt_width``: the ragged form — row b's sequence is columns [0, prompt_lens[b]) then [prompt_width, hist_len).
+    ``bad_words`` / ``stop_sequences``: SequenceTable.  finished [B] uint8 (in/out): finished rows are left untouched.  Returns None."""
+    for name, t in (("bad_words", bad_words), ("stop_sequences", stop_sequences)):
+        if t is not None and not isinstance(t, SequenceTable):
+            raise TypeError(f"constrain_logits: {name} must be an ops.SequenceTable (or None), got {type(t).__name__}")
+    bad_t = None if bad_words is None else (bad_words.ids, bad_words.off)
+    stop_t = None if stop_sequences is None else (stop_sequences.ids, stop_sequences.off)
+    _need_cuda(logits, history, prompt_lens, finished, *(bad_t or ()), *(stop_t or ()))
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("constrain_logits: logits must be fp32 [B, V] with unit column stride")
+    for name, t, dt in (("history", history, torch.int64), ("prompt_lens", prompt_lens, torch.int32), ("finished", finished, torch.uint8)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"constrain_logits: {name} must be a contiguous {dt} tensor")
+    B, V = logits.shape
+    for name, t in (("prompt_lens", prompt_lens), ("finished", finished)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"constrain_logits: {name} must have shape [{B}]")
+    if history is not None and (history.dim() != 2 or history.shape[0] != B):
+        raise ValueError(f"constrain_logits: history must be [{B}, n]")
+    if history is None and int(hist_len) != 0:
+        raise ValueError(f"constrain_logits: hist_len = {hist_len} needs a history")
+    if history is not None and not 0 <= int(hist_len) < history.shape[1]:
+        raise ValueError(f"constrain_logits: hist_len = {hist_len} outside [0, {history.shape[1]}): history has {history.shape[1]} "
+                         "columns and the sampler appends one after this launch")
+    if prompt_lens is not None and not 0 <= int(prompt_width) <= int(hist_len):
+        raise ValueError(f"constrain_logits: prompt_width = {prompt_width} outside [0, hist_len = {hist_len}]")
+    a = H.ConstrainArgs()
+    a.ngram = int(no_repeat_ngram_size)
+    a.logits, a.ld, a.B, a.V = logits.data_ptr(), (logits.stride(0) if B > 1 else max(logits.stride(0), V)), B, V
+    a.history, a.hist_ld, a.hist_len = H.ptr(history), (0 if history is None else history.shape[1]), int(hist_len)
+    a.prompt_width, a.prompt_lens = int(prompt_width), H.ptr(prompt_lens)
+    a.new_tokens, a.min_new = int(new_tokens), int(min_new_tokens)
+    a.eos_id = -1 if eos_token_id is None else int(eos_token_id)
+    if bad_words is not None and bad_words.n:
+        a.bad_ids, a.bad_off, a.n_bad = bad_words.ids.data_ptr(), bad_words.off.data_ptr(), bad_words.n
+        a.bad_off_host = C.cast(bad_words.off_host, C.c_void_p)
+    if stop_sequences is not None and stop_sequences.n:
+        a.stop_ids, a.stop_off, a.n_stop = stop_sequences.ids.data_ptr(), stop_sequences.off.data_ptr(), stop_sequences.n
+        a.stop_off_host = C.cast(stop_sequences.off_host, C.c_void_p)
+    a.finished = H.ptr(finished)
+    H.check(H.load().kx_constrain_logits(C.byref(a), _stream()), "kx_constrain_logits")
+
+
 def embed_step(tokens, embed, pos, pos_a, pos_b=-1):
     """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
     kx_embed_step: [B, d] fp32 rows embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b]) for int64 ``tokens`` [B] on the device."""

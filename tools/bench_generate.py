@@ -16,7 +16,13 @@ One JSON line per batch size.  --only a|b|c restricts the run to one variant (fo
 --num-beams W: the beam-search leg alone.  Per batch size B, alternating, best of --reps each:
   (w) generate(num_beams=W) at B rows: ms per token after the prefill (beam step + cache gather + decode step at B * W rows);
   (p) plain greedy generate() at B * W rows — the decode step of the same width without the search.
---only w|p restricts the run (for a kernel trace of one variant)."""
+--only w|p restricts the run (for a kernel trace of one variant).
+
+--no-repeat-ngram N and/or --bad-words K (K random entries, alternately one and two ids long): the constraints leg alone.  Per
+batch size, alternating, best of --reps each:
+  (a) generate() with every constraint at its default — no kx_constrain_logits launch;
+  (k) generate(no_repeat_ngram_size=N, bad_words_ids=[...]) — one kx_constrain_logits launch per token in front of the sampler.
+--only a|k restricts the run (for a kernel trace of one variant)."""
 import argparse, json, os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -36,9 +42,12 @@ ap.add_argument("--only", default=None)
 ap.add_argument("--ragged", action="store_true")
 ap.add_argument("--min-prefix", type=int, default=16)
 ap.add_argument("--num-beams", type=int, default=0)
+ap.add_argument("--no-repeat-ngram", type=int, default=0)
+ap.add_argument("--bad-words", type=int, default=0)
 a = ap.parse_args()
+constrained = bool(a.no_repeat_ngram or a.bad_words)
 if a.only is None:
-    a.only = "wp" if a.num_beams else "ars" if a.ragged else "abc"
+    a.only = "wp" if a.num_beams else "ak" if constrained else "ars" if a.ragged else "abc"
 dev = torch.device("cuda", 0)
 V = 32002
 m = KosmosLanguage(vocab_size=V, dim=2048, _seed=0).eval().to(dev)
@@ -142,9 +151,37 @@ def timed_once(fn, arg, warm=False):
     return dt
 
 
+def constraints_leg():
+    g = torch.Generator().manual_seed(2)
+    words = [torch.randint(0, V, (1 + k % 2,), generator=g).tolist() for k in range(a.bad_words)]
+    CONS = dict(no_repeat_ngram_size=a.no_repeat_ngram, bad_words_ids=words or None)
+    for B in (int(b) for b in a.batches.split(",")):
+        tok = torch.randint(0, V, (B, a.prefix), generator=torch.Generator().manual_seed(0)).to(dev)
+        pre = timed(lambda t: m(t, incremental_state={"max_len": a.prefix + a.new}), tok)
+        runs = {"a": lambda t: m.generate(t, a.new, **KW), "k": lambda t: m.generate(t, a.new, **KW, **CONS)}
+        best = {}
+        for rep in range(a.reps):                               # alternating, so that both see the same clocks
+            for k in a.only:
+                dt = timed_once(runs[k], tok, warm=rep == 0)
+                best[k] = min(best.get(k, dt), dt)
+        res = {"workload": f"KosmosLanguage generate with constraints, B={B}, prefix {a.prefix}, {a.new} new tokens, {a.precision}, "
+                           f"top_k=50 top_p=0.9 temperature=0.8, no_repeat_ngram_size={a.no_repeat_ngram}, {a.bad_words} bad words",
+               "prefill_ms": round(pre * 1e3, 3)}
+        for k, name in (("a", "a_defaults_ms_per_token"), ("k", "k_constrained_ms_per_token")):
+            if k in best:
+                res[name] = round((best[k] - pre) / (a.new - 1) * 1e3, 4)
+        if len(best) == 2:
+            res["k_minus_a_us_per_token"] = round((best["k"] - best["a"]) / (a.new - 1) * 1e6, 2)
+        print(json.dumps(res), flush=True)
+
+
 if a.num_beams:
     with torch.no_grad():
         beam_leg()
+    sys.exit(0)
+if constrained:
+    with torch.no_grad():
+        constraints_leg()
     sys.exit(0)
 
 with torch.no_grad():
