@@ -714,6 +714,83 @@ typedef struct {
 int kx_constrain_logits(const kx_constrain_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Speculative decoding by prompt lookup (added within ABI 7: one struct and three functions are appended; no existing layout moves
+ * and the kx_struct_id list is unchanged — kx_spec_args carries its own struct_bytes, which kx_spec_accept checks — so kx_version()
+ * stays 7).
+ *
+ * A verify step feeds K = D + 1 rows per sequence in one pass over the weights: row 0 is the last confirmed token, rows 1..D are
+ * guesses ("drafts") for the tokens after it, at consecutive positions base .. base + D.  Row j's greedy pick is the model's
+ * token after rows 0..j, so draft j + 1 is right exactly when it equals row j's pick; the picks up to and including the first
+ * wrong draft's row are what plain greedy decoding would emit, one token per pass.  Exact for greedy decoding.
+ *
+ * kx_attention_decode_block: kx_attention_decode_ragged over M = B * K rows of which row r = b * K + j belongs to cache sequence b
+ *   (caches [B, ...], not [M, ...]).  positions [B * K] int32 (device): row r sits at t = positions[r] and its sequence's base is
+ *   t0 = positions[b * K]; the row must have t == t0 + j.  It attends over cache keys 0 .. t0 - 1 of sequence b and over keys
+ *   t0 + i, i = 0..j, read from qkv row b * K + i, and appends its own k / v to cache row t of sequence b.  Same slots, key order
+ *   and arithmetic as kx_attention_decode_ragged: ONE launch gives, bit for bit, the outputs, stats_out and cache rows of K
+ *   successive kx_attention_decode_ragged launches on the sequence (launch j: the rows j of every sequence at positions t0 + j),
+ *   in every output form and under both cache layouts.  A row with t outside [0, Tmax), t0 < 0 or t != t0 + j writes nothing
+ *   (no output, no cache row) and ORs KX_RAGGED_ERR_CACHE into *error_word; the other rows are unaffected.  K in 2..16.
+ * kx_decoder_decode_step_block: kx_decoder_decode_step_ragged with M = B * K rows and B cache sequences: kx_step_prepare on the
+ *   B * K tokens and positions (pos_shift as there), the qkv launch with xpos_T = B * K, kx_attention_decode_block in place of the
+ *   ragged attention, everything else row-wise.  x [B * K, 1, dim] and xpos_rows [4, B * K, 32] scratch zeroed once by the caller;
+ *   caches [L, B, heads, Tmax, 64]; logits [B * K, vocab]; workspace = kx_decoder_workspace_bytes(w, B * K, 1, prec).
+ *
+ * kx_spec_accept — one launch per verify step, after kx_sample_logits (greedy, no history, no finished) has left picked [B * Kin]
+ * for the step's logits block; one 256-thread workgroup per sequence, integer work only (exact, order-free).  Kin = 1 at step 0
+ * (the block is the prefill's last row) and K afterwards.  Per sequence b, with fed = fed[b * Kin ..], picked = picked[b * Kin ..]:
+ *   Accept.  a = the largest value with fed[j] == picked[j - 1] for all 1 <= j <= a (a <= Kin - 1; a = 0 when Kin = 1, fed unused).
+ *     The candidates are picked[0..a].
+ *   Emit.  A row with finished[b] != 0 on entry emits nothing and moves nothing (emitted[b, step] = 0).  Otherwise
+ *     e = min(a + 1, max_new - n_out[b]) candidates, cut after the first eos_id (inclusive; eos_id < 0 = none), are appended to
+ *     out_tokens[b, n_out[b] ..] and history[b, hist_len[b] ..]; out_src[b, n_out[b] + j] = step * K + j (the logits row token j was
+ *     picked from, counted in [step][row of the sequence]) and emitted[b, step] = e when those are given.  n_out[b], hist_len[b]
+ *     and the K positions of the sequence advance by e; at Kin = 1 the positions are initialised instead: positions[b * K + j] =
+ *     prefill_len - 1 + e + j (the first emitted token is fed at position prefill_len).  The row becomes finished when it emitted
+ *     eos_id or n_out[b] reached max_new.  out_tokens is filled with pad_id by the caller, so slots after a cut stay pad_id.
+ *   Draft the next block into next_tokens[b * K ..].  A finished row gets pad_id in all K rows (it keeps stepping at its frozen
+ *     positions, rewriting its own spare cache rows).  Otherwise row 0 = the last emitted token `last`, and rows 1..K-1:
+ *     - draft_from [B, draft_ld] given: row m = draft_from[b, n_out[b] + m - 1] (the draft for output slot n_out[b] + m - 1, n_out
+ *       after the append), `last` where that slot is outside [0, draft_ld);
+ *     - else the lookup in s = history[b, 0:len], len = hist_len[b] after the append: for n = min(ngram_max, len - 1) down to 1 take
+ *       the LARGEST i <= len - n - 1 with s[i : i + n] == s[len - n : len] (the suffix never matches itself); the first n that has
+ *       one wins, and row m = s[i + n + ((m - 1) mod p)], p = len - (i + n): the continuation of the match, wrapping at the
+ *       sequence's end.  No n matches: every draft = `last`.  Any draft is correct — a wrong one is only rejected.
+ *   Guards.  Ids are compared and copied as values and never used as an index.  n_out[b] outside [0, max_new], hist_len[b] outside
+ *     [0, hist_ld - (max_new - n_out[b])] (no room for what may still be appended) or, at Kin = K, positions[b * K] < 0 make the row
+ *     finished with nothing emitted: memory safety does not depend on the device data.
+ * Host checks (KX_ERR_INVALID_ARG, nothing launched): null pointers, struct_bytes, K outside 2..16, Kin not in {1, K}, B < 1,
+ * ngram_max outside 1..64, out_ld < max_new, max_new < 1, fed missing with Kin = K.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_spec_args) of the caller ("stale binding" otherwise) */
+  int32_t ngram_max;                          /* 1..64: the longest suffix n-gram looked up */
+  int64_t B; int64_t K; int64_t Kin;
+  const int64_t* fed;                         /* [B * Kin]: the tokens the block's rows were fed (NULL when Kin = 1) */
+  const int64_t* picked;                      /* [B * Kin]: kx_sample_logits' greedy picks */
+  int32_t* positions;                         /* [B * K] in/out */
+  int64_t prefill_len;                        /* read when Kin = 1 */
+  int64_t* history; int64_t hist_ld; int32_t* hist_len;          /* [B, hist_ld], [B] in/out */
+  int64_t* out_tokens; int64_t out_ld; int32_t* n_out;           /* [B, out_ld], [B] in/out (zeroed before step 0) */
+  uint8_t* finished;                          /* [B] in/out (zeroed before step 0) */
+  int64_t max_new; int64_t eos_id; int64_t pad_id;               /* eos_id < 0 = none */
+  int64_t step;                               /* the verify step's index, 0 = the prefill's */
+  int32_t* out_src;                           /* [B, out_ld] or NULL */
+  int32_t* emitted; int64_t emitted_ld;       /* [B, emitted_ld] (step < emitted_ld) or NULL */
+  const int64_t* draft_from; int64_t draft_ld;                   /* [B, draft_ld] or NULL */
+  int64_t* next_tokens;                       /* [B * K] out: the next block's tokens */
+} kx_spec_args;
+int kx_spec_accept(const kx_spec_args* args, void* stream);
+int kx_attention_decode_block(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                              int64_t B, int64_t K, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
+                              int32_t* error_word, void* stream);
+int kx_decoder_decode_step_block(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                 int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t B, int64_t K,
+                                 const int32_t* positions, const float* xq_cs, const float* xq_ss, const float* xk_cs,
+                                 const float* xk_ss, float* xpos_rows, void* kcache, void* vcache, int64_t Tmax,
+                                 void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
+                                 int32_t* error_word, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before
  * Kosmos.forward, on the device.  Integer / byte work; results are bit-identical to the HF processor.
  * ------------------------------------------------------------------------------------------ */

@@ -1142,7 +1142,10 @@ struct DecodeParams {
 };
 // the ragged form: t = positions[b] instead of DecodeParams.t, checked against Tmax in the kernel (err: the sticky error word)
 struct RaggedParams { const int* positions; int* err; int Tmax; };
+// the block form (a second pack member after RaggedParams): K consecutive rows of the launch are ONE cache sequence
+struct BlockParams { int K; };
 template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
+template <typename A, typename B2, typename... Rest> __device__ __forceinline__ const B2& second_arg(const A&, const B2& b, const Rest&...) { return b; }
 
 template <typename T> struct Ld4;
 template <> struct Ld4<bf16_t> {
@@ -1171,17 +1174,41 @@ template <> struct Ld4<float> {
 // (no cache row, no output) and sets KX_RAGGED_ERR_CACHE in the sticky error word.
 // The ragged launch passes one more kernel argument (R = RaggedParams); the uniform launch has an empty pack, i.e. the signature
 // and kernel-argument layout it always had.
+// BLOCK (R = RaggedParams, BlockParams; kx_attention_decode_block): the launch's row r = b * K + j is the j-th of K rows that belong
+// to cache sequence b, at consecutive positions t0 + j (t0 = positions[b * K], the number of keys the cache holds for all of them).
+// Row r attends over cache keys 0 .. t0 - 1 and over keys t0 + i, i = 0 .. j, read from qkv row b * K + i — the generalisation of
+// "the new key comes from the qkv row": K sequential ragged launches would find exactly those bits in cache rows t0 .. t - 1, which
+// the earlier launches appended from the same qkv rows.  Same slots, key order and arithmetic on `t`, hence the same bits.  The two
+// positions are requested together (still one scalar round trip before the one vector round trip; the grid is (H, K, B), the
+// workgroups of (H, B * K) with the division done by the dispatcher); the append of row t is the side
+// store it always was: no workgroup of the launch reads a cache row >= t0.  A row whose position leaves [0, Tmax) or is not
+// t0 + j writes nothing and sets KX_RAGGED_ERR_CACHE.  Everything BLOCK adds sits under `if constexpr (BLOCK)`.
 template <typename T, typename... R>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, const R... r) {
   constexpr bool RAGGED = sizeof...(R) != 0;
+  constexpr bool BLOCK = sizeof...(R) == 2;
   __shared__ float sm_m[16], sm_l[16], sm_o[16][64];
   typedef typename Ld4<T>::raw raw;
   constexpr int UK = Ld4<T>::UK;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = lane >> 4, li = lane & 15;              // 16-lane group = one key at a time; lane = dims 4li..4li+3
-  const int h = blockIdx.x, b = blockIdx.y;
+  const int h = blockIdx.x;
+  int b = blockIdx.y;                                       // the launch's row (BLOCK: set below)
   int t = p.t;
-  if constexpr (RAGGED) {
+  int cb = b, t0 = 0;                                       // BLOCK: the cache sequence of row b and its first position
+  if constexpr (BLOCK) {                                    // grid (H, K, B): row b = sequence z's y-th; both positions are requested together
+    const RaggedParams& rp = first_arg(r...);
+    const int jr = blockIdx.y;
+    cb = blockIdx.z;
+    b = cb * second_arg(r...).K + jr;
+    t = rp.positions[b];
+    t0 = rp.positions[b - jr];
+    // (one condition on both words, bitwise: evaluated after BOTH loads are back — neither waits behind a branch on the other)
+    if ((t < 0) | (t >= rp.Tmax) | (t0 < 0) | (t0 > t) | ((unsigned)t - (unsigned)t0 != (unsigned)jr)) {   // (uniform over the workgroup)
+      if (tid == 0) atomicOr(rp.err, KX_RAGGED_ERR_CACHE);
+      return;
+    }
+  } else if constexpr (RAGGED) {
     const RaggedParams& rp = first_arg(r...);
     t = rp.positions[b];
     if (t < 0 || t >= rp.Tmax) {                            // (uniform over the workgroup: nobody reaches a barrier)
@@ -1191,8 +1218,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   }
   const long long es = sizeof(T);
   const char* qrow = p.qkv + ((long long)b * p.qkv_row + (long long)h * 64 + 4 * li) * es;
-  char* kc = p.kcache + ((long long)b * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
-  char* vc = p.vcache + ((long long)b * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
+  char* kc = p.kcache + ((long long)cb * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
+  char* vc = p.vcache + ((long long)cb * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
   const char* knew = qrow + (long long)p.D * es;          // the new token (key t): k | v of the qkv row
   const char* vnew = qrow + 2ll * p.D * es;
   const int nkeys = t + 1;
@@ -1202,8 +1229,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
 #pragma unroll
   for (int u = 0; u < UK; ++u) {                           // (slots past the end re-read the last key and drop it)
     const int j = min(slot + 16 * u, t);
-    kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
-    vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
+    if constexpr (BLOCK) {                                 // keys t0 .. t: qkv row j - t0 of the sequence = (t - j) rows before this one
+      const long long back = (long long)(t - j) * p.qkv_row * es;
+      kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * p.cache_row * es);
+      vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * p.cache_row * es);
+    } else {
+      kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
+      vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
+    }
   }
   if (wave == 0 && grp < 2) {                              // append row t: 64 k + 64 v elements per head
     const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
@@ -1217,8 +1250,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
 #pragma unroll
       for (int u = 0; u < UK; ++u) {
         const int j = min(j0 + 16 * u, t);
-        kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
-        vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
+        if constexpr (BLOCK) {
+          const long long back = (long long)(t - j) * p.qkv_row * es;
+          kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * p.cache_row * es);
+          vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * p.cache_row * es);
+        } else {
+          kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
+          vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
+        }
       }
     }
 #pragma unroll
@@ -1316,10 +1355,11 @@ int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t
   return KX_OK;
 }
 
-// positions == nullptr: the uniform launch at host position t; else the ragged launch (t unused)
+// positions == nullptr: the uniform launch at host position t; else the ragged launch (t unused).  K > 0: the block launch — B counts
+// the ROWS (sequences * K), the caches hold B / K sequences.
 static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, void* vcache, void* out, int32_t odt,
                                  float* stats_out, int64_t B, int64_t H, int64_t t, const int32_t* positions, int32_t* err,
-                                 int64_t Tmax, int32_t prec, void* stream) {
+                                 int64_t Tmax, int32_t prec, void* stream, int64_t K = 0) {
   KX_REQUIRE(qkv && kcache && vcache && out, "%s: null pointer", fn);
   KX_REQUIRE(B > 0 && H > 0 && t >= 0 && t < Tmax, "%s: position %lld outside the cache of %lld rows", fn,
              (long long)t, (long long)Tmax);
@@ -1343,7 +1383,12 @@ static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, 
   hipStream_t s = (hipStream_t)stream;
   KxProfScope prof(prec == KX_PREC_BF16 ? KX_K_ATTN_BF16 : KX_K_ATTN_F32, B * H, 1, positions ? Tmax : t + 1, s);
   const dim3 grid((unsigned)H, (unsigned)B);
-  if (positions) {
+  if (K > 0) {
+    const BlockParams bp{(int)K};
+    const dim3 gb((unsigned)H, (unsigned)K, (unsigned)(B / K));   // the workgroups of (H, B) with the row's (sequence, index) as coordinates
+    if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
+    else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
+  } else if (positions) {
     if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams>), grid, dim3(256), 0, s, p, r);
     else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams>), grid, dim3(256), 0, s, p, r);
   } else {
@@ -1367,4 +1412,16 @@ extern "C" int kx_attention_decode_ragged(const void* qkv, void* kcache, void* v
   KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll, "kx_attention_decode_ragged: Tmax=%lld outside the 32-bit positions", (long long)Tmax);
   return attention_decode_impl("kx_attention_decode_ragged", qkv, kcache, vcache, out, odt, stats_out, B, H, 0, positions, error_word,
                                Tmax, prec, stream);
+}
+
+extern "C" int kx_attention_decode_block(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                                         int64_t B, int64_t K, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
+                                         int32_t* error_word, void* stream) {
+  KX_REQUIRE(positions && error_word, "kx_attention_decode_block: null positions / error_word");
+  KX_REQUIRE(K >= 2 && K <= 16, "kx_attention_decode_block: K=%lld outside 2..16 rows per sequence", (long long)K);
+  KX_REQUIRE(B > 0 && B <= 65535 / K, "kx_attention_decode_block: B=%lld sequences of K=%lld rows exceed the grid limits", (long long)B,
+             (long long)K);
+  KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll, "kx_attention_decode_block: Tmax=%lld outside the 32-bit positions", (long long)Tmax);
+  return attention_decode_impl("kx_attention_decode_block", qkv, kcache, vcache, out, odt, stats_out, B * K, H, 0, positions, error_word,
+                               Tmax, prec, stream, K);
 }

@@ -169,6 +169,20 @@ class ConstrainArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class SpecArgs(C.Structure):
+    """kx_spec_args; struct_bytes is filled in at construction ("stale binding" check of kx_spec_accept — the struct has no
+    kx_struct_id: the list of ids is pinned, so its size is checked by the call itself)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("ngram_max", i32), ("B", i64), ("K", i64), ("Kin", i64), ("fed", vp), ("picked", vp),
+                ("positions", vp), ("prefill_len", i64), ("history", vp), ("hist_ld", i64), ("hist_len", vp),
+                ("out_tokens", vp), ("out_ld", i64), ("n_out", vp), ("finished", vp), ("max_new", i64), ("eos_id", i64),
+                ("pad_id", i64), ("step", i64), ("out_src", vp), ("emitted", vp), ("emitted_ld", i64), ("draft_from", vp),
+                ("draft_ld", i64), ("next_tokens", vp)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -213,6 +227,10 @@ SYMBOLS = {
     "kx_beam_finalize": (C.c_int, [vp] * 8 + [i64] * 5 + [f32, i64, i64, vp, i64, vp, vp]),
     "kx_kv_cache_gather": (C.c_int, [vp] * 4 + [i64] * 6 + [i32, vp, vp, vp]),
     "kx_constrain_logits": (C.c_int, [C.POINTER(ConstrainArgs), vp]),
+    "kx_spec_accept": (C.c_int, [C.POINTER(SpecArgs), vp]),
+    "kx_attention_decode_block": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp]),
+    "kx_decoder_decode_step_block": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),
     "kx_decoder_forward": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, i32, vp,
                                      C.c_size_t, i32, vp]),
     "kx_clip_preprocess_workspace_bytes": (C.c_size_t, [i64, i32, i32]),

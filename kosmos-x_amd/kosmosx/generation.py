@@ -18,8 +18,14 @@ in front of the sampler (or the beam step) sets the banned ids' logits to -inf i
 finished; the sampler and the beam step already never pick -inf.  It reads the history buffer the sampler appends to, so the token
 still never leaves the device.  With every constraint at its default the launch is not issued.
 
+Prompt-lookup speculative decoding (``prompt_lookup_num_tokens`` = D > 0, lookup_loop): every step runs K = D + 1 rows per sequence
+through one pass over the weights (kx_decoder_decode_step_block: the last confirmed token and D drafts at consecutive positions of
+the sequence's cache), kx_sample_logits picks greedily on all of them and kx_spec_accept keeps the picks the drafts led up to
+correctly, appends them, moves the positions and copies the next drafts from where the row's last n-gram occurred before.  Exact
+for greedy decoding; the host reads only the stop poll.
+
 Not offered: compaction of finished rows, replaying the step as a captured graph, padding masks in
-``Decoder.forward`` (``self_attn_padding_mask``); with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
+``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
 """
 from __future__ import annotations
@@ -282,15 +288,141 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
     return res[0] if len(res) == 1 else tuple(res)
 
 
-def check_budget(decoder, T: int, max_new_tokens: int):
-    """IndexError before any launch when prompt + new tokens overrun the position table / cache."""
+MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
+
+
+def check_lookup_args(batch: int, *, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, draft_from=None,
+                      do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, num_beams=1,
+                      prompt_lengths=None, sequence_ids=None, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+                      stop_sequences=None, eos_poll=8) -> int:
+    """ValueError (naming the argument) for what generate() refuses of prompt-lookup speculation, before anything is launched.
+    Returns D, the number of drafts per step (0: the call runs the loops it always ran)."""
+    D = prompt_lookup_num_tokens
+    if isinstance(D, bool) or not isinstance(D, int) or D < 0:
+        raise ValueError(f"prompt_lookup_num_tokens must be a non-negative integer, got {D!r}")
+    if D == 0:
+        if output_acceptance:
+            raise ValueError("output_acceptance is an output of prompt-lookup speculation: it needs prompt_lookup_num_tokens > 0")
+        if draft_from is not None:
+            raise ValueError("_draft_from needs prompt_lookup_num_tokens > 0")
+        return 0
+    n = max_matching_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_NGRAM:
+        raise ValueError(f"max_matching_ngram_size must be an integer in 1..{MAX_NGRAM}, got {n!r}")
+    for name, bad in (("do_sample", bool(do_sample)), ("temperature", float(temperature) != 1.0), ("top_k", int(top_k) != 0),
+                      ("top_p", float(top_p) != 1.0), ("repetition_penalty", float(repetition_penalty) != 1.0),
+                      ("num_beams", num_beams != 1), ("prompt_lengths", prompt_lengths is not None),
+                      ("sequence_ids", sequence_ids is not None), ("no_repeat_ngram_size", no_repeat_ngram_size != 0),
+                      ("bad_words_ids", bool(bad_words_ids)), ("min_new_tokens", min_new_tokens != 0),
+                      ("stop_sequences", bool(stop_sequences))):
+        if bad:
+            raise ValueError(f"{name} is not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = {D}): it is "
+                             "exact for plain greedy decoding only; see DESIGN.md §7b")
+    if batch * (D + 1) > MAX_STEP_ROWS:
+        raise ValueError(f"prompt_lookup_num_tokens = {D}: {batch} sequences x {D + 1} rows exceed the {MAX_STEP_ROWS} rows of a "
+                         "weight-streaming step (the drafts would cost a tile GEMM)")
+    if isinstance(eos_poll, bool) or not isinstance(eos_poll, int) or eos_poll <= 0:
+        raise ValueError(f"eos_poll must be a positive integer with prompt_lookup_num_tokens = {D} (the poll is how the loop ends), "
+                         f"got {eos_poll!r}")
+    return D
+
+
+def lookup_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
+                num_drafts: int, ngram_max: int = 2, pos_shift: int = 0, eos_token_id=None, pad_token_id=1, eos_poll=8,
+                output_logits=False, output_acceptance=False, draft_from=None):
+    """Greedy decoding with prompt-lookup speculation after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop
+    (state["max_len"] >= T + max_new_tokens + num_drafts), ``prompt_tokens`` [B, Tt] int64 the ids the lookup starts from (the
+    TEXT ids: spliced image rows contribute none).  Per verify step g: kx_sample_logits (greedy) on the step's [B * Kin, V] block
+    (Kin = 1: the prefill's last row; K = num_drafts + 1 afterwards), kx_spec_accept (the contract: include/kosmosx_hip.h,
+    "Speculative decoding by prompt lookup"), then kx_decoder_decode_step_block on the B * K rows it wrote.  Every buffer is
+    allocated before the first step; the host reads ``finished.all()`` with the step kernels' error word at the poll and once
+    after the loop (there with the longest row's length), nothing else.  At most max_new_tokens steps: an unfinished row emits
+    at least one token per step.  ``draft_from`` int64 [B, max_new_tokens] (tests, benchmark): the draft for output slot i is
+    draft_from[b, i] instead of the lookup's.
+    Returns tokens int64 [B, n]; then with ``output_logits`` the fp32 [B, n, V] rows the tokens were picked from (zeros after a
+    row's end); then with ``output_acceptance`` the int32 [B, steps] tokens emitted per step, for the steps in which some row still
+    emitted (the steps issued after the last row finished and before the poll noticed are not listed)."""
+    B, T, V = logits.shape
+    dev = logits.device
+    D, N = int(num_drafts), int(max_new_tokens)
+    K = D + 1
+    M = B * K
+    pad = int(pad_token_id)
+    Tt = prompt_tokens.shape[1]
+    if draft_from is not None:
+        if not isinstance(draft_from, torch.Tensor) or draft_from.dtype != torch.int64 or tuple(draft_from.shape) != (B, N):
+            raise ValueError(f"_draft_from must be an int64 [{B}, {N}] tensor")
+        draft_from = draft_from.to(dev).contiguous()
+    out = torch.full((B, N), pad, dtype=torch.int64, device=dev)
+    n_out = torch.zeros(B, dtype=torch.int32, device=dev)
+    history = torch.empty((B, Tt + N), dtype=torch.int64, device=dev)
+    history[:, :Tt] = prompt_tokens
+    hist_len = torch.full((B,), Tt, dtype=torch.int32, device=dev)
+    finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+    positions = torch.zeros(M, dtype=torch.int32, device=dev)              # kx_spec_accept initialises them at step 0
+    picked = torch.empty(M, dtype=torch.int64, device=dev)
+    cur, nxt = (torch.empty(M, dtype=torch.int64, device=dev) for _ in range(2))   # the block a step was fed / the next one
+    emitted = torch.zeros((B, N), dtype=torch.int32, device=dev)
+    kept = out_src = None
+    if output_logits:
+        kept = torch.zeros((N, M, V), dtype=torch.float32, device=dev)       # row [g, b * K + j]: step g's logits
+        out_src = torch.zeros((B, N), dtype=torch.int32, device=dev)
+    else:
+        block_buf = torch.empty((M, V), dtype=torch.float32, device=dev)
+    # the furthest row any step can touch, for the host-side table / cache check of the step (the budget covers it)
+    state.update(positions=positions, block=K, pos_max=T + N + D - 1)
+    decoder._ragged_scratch(state, dev, rows=M)                             # (before the first launch: no fill between steps)
+    err = state["error"]
+    block = logits[:, -1]                                                   # [B, V] view, row stride T * V
+    if kept is not None:
+        kept[0].view(B, K, V)[:, 0].copy_(block)
+    steps = 0
+    for g in range(N):
+        Kin = 1 if g == 0 else K
+        ops.sample_logits(block, do_sample=False, pad_token_id=pad, out=picked[:B * Kin])
+        ops.spec_accept(picked[:B * Kin], fed=cur if g else None, rows_per_sequence=K, positions=positions, prefill_len=T,
+                        history=history, hist_len=hist_len, out_tokens=out, n_out=n_out, finished=finished, next_tokens=nxt,
+                        max_new_tokens=N, step=g, ngram_max=ngram_max, eos_token_id=eos_token_id, pad_token_id=pad,
+                        out_src=out_src, emitted=emitted, draft_from=draft_from)
+        steps = g + 1
+        if steps == N:
+            break
+        if steps % eos_poll == 0:                                           # the loop's only device-to-host read
+            done, word = torch.stack([finished.min().to(torch.int32), err[0]]).tolist()
+            _raise_position_error(word, state)
+            if done:
+                break
+        block = decoder._forward_incremental(None, state, None, prec, next_token=nxt, pos_shift=pos_shift,
+                                             logits_out=kept[g + 1] if kept is not None else block_buf)[:, 0]
+        cur, nxt = nxt, cur
+    # (the steps that emitted something are a prefix of the steps issued: the poll's granularity does not show in the outputs)
+    done, word, n, used = torch.stack([finished.min().to(torch.int32), err[0], n_out.max(),
+                                       (emitted.max(0).values > 0).sum().to(torch.int32)]).tolist()
+    _raise_position_error(word, state)
+    if not done:                                                            # cannot happen: max_new_tokens steps finish every row
+        raise RuntimeError("prompt-lookup speculation ended with an unfinished row")
+    res = [out[:, :n]]
+    if output_logits:
+        flat = kept[:steps].view(steps * M, V)
+        src = out_src[:, :n].to(torch.int64)
+        idx = (src // K) * M + torch.arange(B, device=dev)[:, None] * K + src % K
+        live = torch.arange(n, device=dev)[None, :] < n_out[:, None]
+        res.append(torch.where(live[:, :, None], flat[idx], torch.zeros((), dtype=torch.float32, device=dev)))
+    if output_acceptance:
+        res.append(emitted[:, :used])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0):
+    """IndexError before any launch when prompt + new tokens (+ ``spare`` rows: the drafts of a lookup step) overrun the position
+    table / cache."""
     if not isinstance(max_new_tokens, int) or max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
     rows = decoder.embed_positions.weight.shape[0] - 2
     # (conservative by one token: the last generated token is never embedded, so it would not need a row of its own)
-    if T + max_new_tokens > rows:
-        raise IndexError(f"index out of range in self: {T} prompt positions + {max_new_tokens} new tokens exceed the "
-                         f"{rows}-row position table / cache")
+    if T + max_new_tokens + spare > rows:
+        raise IndexError(f"index out of range in self: {T} prompt positions + {max_new_tokens} new tokens"
+                         + (f" + {spare} draft rows" if spare else "") + f" exceed the {rows}-row position table / cache")
 
 
 def _raise_position_error(word: int, state: dict):

@@ -796,7 +796,7 @@ class Decoder(_PackedMixin, nn.Module):
 
     # -- incremental decoding ---------------------------------------------------
     def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None,
-                             pos_shift: int = 0) -> torch.Tensor:
+                             pos_shift: int = 0, logits_out=None) -> torch.Tensor:
         """torchscale's incremental_state protocol: the first call runs the whole prefix and fills the KV cache,
         every later call is given the token history (only its last token and its length are used, as upstream's
         `tokens[:, -1:]`) and appends one position.  ``state`` is an opaque dict owned by the caller.
@@ -807,7 +807,11 @@ class Decoder(_PackedMixin, nn.Module):
         cached tokens, and ``state["pos_max"]`` its host-side maximum (for the budget check and the error messages only).  A
         later step then takes ``next_token`` and runs kx_decoder_decode_step_ragged: every row at its own position, embedded
         with the position rows positions[b] (and positions[b] - ``pos_shift`` when that is not 0).  The step does not move
-        the device positions — the sampler that produced ``next_token`` did (kx_sample_logits_ragged)."""
+        the device positions — the sampler that produced ``next_token`` did (kx_sample_logits_ragged).
+        Block steps (generate(prompt_lookup_num_tokens=...)): ``state["block"]`` = K makes the ragged state step K rows per
+        sequence — ``next_token`` and ``state["positions"]`` are [B * K], rows b * K + j at consecutive positions of cache
+        sequence b (kx_decoder_decode_step_block); kx_spec_accept keeps both.  ``logits_out``: a caller-owned fp32 [B * K, V]
+        buffer for the step's logits.  Returns [B * K, 1, V]."""
         if self.args.activation_fn != "gelu":
             raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
                                       "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
@@ -860,6 +864,8 @@ class Decoder(_PackedMixin, nn.Module):
             if next_token is None or passed_x is not None:
                 raise ValueError("a ragged incremental state (state['positions']) is stepped with next_token only")
             t = state["pos_max"]                           # the furthest row: what the table / cache must still hold
+        block = int(state.get("block", 0)) if positions is not None else 0
+        rows = B * block if block else B                   # the rows of the step's GEMMs
         if state["prec"] != prec:
             raise RuntimeError("precision changed between incremental steps")
         if t >= Tmax or t + 2 >= pos.shape[0]:
@@ -876,13 +882,15 @@ class Decoder(_PackedMixin, nn.Module):
         # they would run plain fp32 GEMMs on rounded weights — accuracy lost, no byte saved, and a second fp32 pack held
         #  — so those steps keep the f16c tile GEMMs the prefill ran.  (KOSMOSX_DECODE_TILED=0 is the A/B switch
         # that runs the SAME compressed weights from their row-major fp32 operands: bit-identical to the planes, test-only.)
-        streams = B <= 16
+        streams = rows <= 16
         sprec = prec if (prec != "f16c" or exact == "0" or not (streams or exact == "fp32")) else (
             {"fp32": "fp32", "w24": "w24"}.get(exact, "w16"))
         if sprec != prec:
             w = self._pack(sprec)[0]
-        if sprec in ("bf16", "fp32", "w24", "w16") and B <= 16:
+        if sprec in ("bf16", "fp32", "w24", "w16") and rows <= 16:
             self._pack_decode_tiles(sprec)                 # first decode step: the streaming copy of the weights
+        if block:
+            return self._block_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, block, logits_out)
         if positions is not None:
             return self._ragged_step(state, w, sprec, emb, pos, next_token, positions, pos_shift)
         if passed_x is not None:
@@ -916,12 +924,12 @@ class Decoder(_PackedMixin, nn.Module):
         state["len"] = t + 1
         return logits
 
-    def _ragged_scratch(self, state: dict, dev):
+    def _ragged_scratch(self, state: dict, dev, rows=None):
         """What a ragged step needs beside the caches, kept with the state (same pointers every step): the kernels' sticky
         error word, the step's input rows and the gathered XPos rows.  Zeros, not empty: a row kx_step_prepare rejects is not
         written, and what it computes until the error word is read must be finite and the same every time.  generate() calls
         this before its first sampler launch, so that no fill lands between two steps."""
-        B, D = state["batch"], self.args.decoder_embed_dim
+        B, D = (state["batch"] if rows is None else rows), self.args.decoder_embed_dim      # (rows: the block step's B * K)
         if "error" not in state:
             state["error"] = torch.zeros(1, dtype=torch.int32, device=dev)
         if "x_step" not in state:
@@ -949,6 +957,32 @@ class Decoder(_PackedMixin, nn.Module):
             buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_ragged")
         state["pos_max"] += 1
         return logits
+
+    def _block_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K, logits_out=None) -> torch.Tensor:
+        """One decode step over K rows per sequence at consecutive device positions (see _forward_incremental)."""
+        lib = H.load()
+        _require_cuda(next_token, "next_token")
+        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
+        M = B * K
+        if next_token.shape[0] != M or positions.shape[0] != M:
+            raise ValueError("batch size changed between incremental steps")
+        dev = emb.device
+        self._ragged_scratch(state, dev, rows=M)
+        if logits_out is None:
+            logits_out = torch.empty((M, w.vocab), dtype=torch.float32, device=dev)
+        elif (tuple(logits_out.shape) != (M, w.vocab) or logits_out.dtype != torch.float32 or not logits_out.is_contiguous()
+              or logits_out.device != dev):
+            raise ValueError(f"logits_out must be a contiguous fp32 [{M}, {w.vocab}] tensor on the model's device")
+        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
+               else H.PACK_PRECS[sprec])
+        need = lib.kx_decoder_workspace_bytes(C.byref(w), M, 1, pid)
+        buf = self._ws.get(need, dev)
+        H.check(lib.kx_decoder_decode_step_block(
+            C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
+            state["x_step"].data_ptr(), B, K, positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
+            state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(),
+            buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_block")
+        return logits_out.view(M, 1, w.vocab)
 
     # -- torchscale-compatible surface ------------------------------------------------------------
     def forward_embedding(self, tokens, token_embedding=None, incremental_state=None):
@@ -1175,7 +1209,8 @@ class Kosmos(nn.Module):
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1,
                  sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0,
                  early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
-                 no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None):
+                 no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
+                 prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1199,7 +1234,15 @@ class Kosmos(nn.Module):
         tokens; ``stop_sequences`` (id lists, as ``bad_words_ids``): a row stops after generating one of them — the output
         keeps it and is padded after it, as after an EOS.  All of them see the TEXT ids only (prompt, then output): the
         spliced image rows contribute no ids, so an n-gram may span the splice point.  With beams: ``min_new_tokens`` and
-        single-id ``bad_words_ids`` only; the others need a per-beam history and raise ValueError."""
+        single-id ``bad_words_ids`` only; the others need a per-beam history and raise ValueError.
+        ``prompt_lookup_num_tokens`` D >= 1: speculative decoding by prompt lookup (kosmosx.generation.lookup_loop) — every
+        step feeds the last token and D drafts copied from where the row's last n-gram (at most ``max_matching_ngram_size``
+        ids) occurred before in its prompt + output, in one pass over the weights, and keeps the drafts the model confirms:
+        the output is what plain greedy decoding picks from the same logits, in fewer steps where the text repeats itself.
+        Greedy only, B * (D + 1) <= 16 rows, and the budget is T + max_new_tokens + D positions; sampling, the filters, the
+        penalty, beams, ``prompt_lengths``, ``sequence_ids`` and the constraints raise ValueError together with it.
+        ``output_acceptance``: also the int32 [B, steps] number of tokens every row emitted at every verify step (column 0:
+        the token taken from the prefill).  Returned after the logits when both are asked for."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1212,6 +1255,12 @@ class Kosmos(nn.Module):
             self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
             num_beams=num_beams if beams else None)
+        drafts = generation.check_lookup_args(
+            text_tokens.shape[0] if text_tokens.dim() else 0, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, draft_from=_draft_from,
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+            num_beams=num_beams, prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, no_repeat_ngram_size=no_repeat_ngram_size,
+            bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_poll=eos_poll)
         _warn_train_mode(self)
         _require_cuda(text_tokens, "text_tokens")
         _require_cuda(images, "images")
@@ -1223,7 +1272,7 @@ class Kosmos(nn.Module):
             lens = generation.resolve_prompt_lengths(prompt_lengths, text_tokens.shape[0], text_tokens.shape[1], min_len=2)
             text_tokens = text_tokens[:, :max(lens)]                         # columns no row uses
         T = text_tokens.shape[1] + n_img
-        generation.check_budget(self.decoder, T, max_new_tokens)
+        generation.check_budget(self.decoder, T, max_new_tokens, spare=drafts)
         prec = self.precision
         with torch.no_grad():
             if lens is not None:
@@ -1231,9 +1280,15 @@ class Kosmos(nn.Module):
             img = self.clip_model.run(images, prec, self._ws)
             img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
             x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
-            state = {"max_len": T + max_new_tokens}
+            state = {"max_len": T + max_new_tokens + drafts}                # (rejected drafts still occupy table and cache rows)
             # (ragged: the right-padded prefill needs no mask — the argument is spelled out in KosmosLanguage.generate)
             logits = self.decoder._forward_incremental(None, state, x, prec)
+            if drafts:
+                return generation.lookup_loop(
+                    self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens, num_drafts=drafts,
+                    ngram_max=max_matching_ngram_size, pos_shift=n_img if self.switches.u1_inplace_alias else 0,
+                    eos_token_id=eos_token_id, pad_token_id=pad_token_id, eos_poll=eos_poll, output_logits=output_logits,
+                    output_acceptance=output_acceptance, draft_from=_draft_from)
             if beams:
                 return generation.beam_loop(
                     self.decoder, prec, state, logits, max_new_tokens, num_beams=num_beams,
@@ -1347,11 +1402,13 @@ class KosmosLanguage(nn.Module):
                  repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
-                 bad_words_ids=None, min_new_tokens=0, stop_sequences=None):
+                 bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
+                 max_matching_ngram_size=2, output_acceptance=False, _draft_from=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
         arguments that go with it: beam search, as there; ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens`` and
-        ``stop_sequences``: the constraints, as there)."""
+        ``stop_sequences``: the constraints, as there; ``prompt_lookup_num_tokens``, ``max_matching_ngram_size`` and
+        ``output_acceptance``: speculative decoding by prompt lookup, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1364,6 +1421,12 @@ class KosmosLanguage(nn.Module):
             self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
             num_beams=num_beams if beams else None)
+        drafts = generation.check_lookup_args(
+            x.shape[0] if x.dim() else 0, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, draft_from=_draft_from,
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+            num_beams=num_beams, prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, no_repeat_ngram_size=no_repeat_ngram_size,
+            bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_poll=eos_poll)
         _warn_train_mode(self)
         _require_cuda(x, "x")
         if x.dim() != 2:
@@ -1373,11 +1436,11 @@ class KosmosLanguage(nn.Module):
             lens = generation.resolve_prompt_lengths(prompt_lengths, x.shape[0], x.shape[1], min_len=1)
             x = x[:, :max(lens)]                                             # columns no row uses
         T = x.shape[1]
-        generation.check_budget(self.decoder, T, max_new_tokens)
+        generation.check_budget(self.decoder, T, max_new_tokens, spare=drafts)
         with torch.no_grad():
             if lens is not None:
                 x = generation.mask_padding(x.long(), lens)
-            state = {"max_len": T + max_new_tokens}
+            state = {"max_len": T + max_new_tokens + drafts}                # (rejected drafts still occupy table and cache rows)
             # Ragged prompts go through the ordinary prefill, right-padded, with no padding mask and no new kernel: attention is
             # causal, so a real position (< len_b) never has a padded key (>= len_b) among the keys it sees, and every other
             # operation of the decoder works on a row alone.  The padded rows compute finite values (their ids are the row's first
@@ -1385,6 +1448,11 @@ class KosmosLanguage(nn.Module):
             # len_b + g of sequence b is overwritten by the row's own g-th generated token in the very launch whose query is the
             # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row).
             logits = self.decoder._forward_incremental(x, state, None, self.precision)
+            if drafts:
+                return generation.lookup_loop(
+                    self.decoder, self.precision, state, logits, x.long(), max_new_tokens, num_drafts=drafts,
+                    ngram_max=max_matching_ngram_size, eos_token_id=eos_token_id, pad_token_id=pad_token_id, eos_poll=eos_poll,
+                    output_logits=output_logits, output_acceptance=output_acceptance, draft_from=_draft_from)
             if beams:
                 return generation.beam_loop(
                     self.decoder, self.precision, state, logits, max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,

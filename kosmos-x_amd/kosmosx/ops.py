@@ -572,6 +572,93 @@ def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=
     return out
 
 
+def attention_decode_block(qkv, kcache, vcache, positions, error_word, *, rows_per_sequence, out_dtype="f32", stats_out=None,
+                           layout="head_major"):
+    """Kernel-level wrapper of kx_attention_decode_block (include/kosmosx_hip.h, "Speculative decoding by prompt lookup"): the
+    decode attention over B * K rows of which K = ``rows_per_sequence`` consecutive ones belong to one cache sequence, at
+    consecutive positions.  qkv [B * K, 3 * H * 64] fp32 or bf16; kcache / vcache [B, H, Tmax, 64] ([B, Tmax, H, 64] with
+    ``layout`` "row_major", as ops.attention_decode) of the same dtype, updated in place; positions [B * K] int32 on the device;
+    error_word int32 [1] (sticky: KX_RAGGED_ERR_CACHE for a row outside the cache or off its sequence's base + j).
+    One launch = K successive ops.attention_decode(positions=...) launches, bit for bit.  Returns the output rows [B * K, ...]."""
+    _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out)
+    if layout not in ("head_major", "row_major"):
+        raise ValueError("attention_decode_block: layout is 'head_major' or 'row_major'")
+    if layout == "row_major":
+        B, Tmax, Hh, hd = kcache.shape
+    else:
+        B, Hh, Tmax, hd = kcache.shape
+    K = int(rows_per_sequence)
+    M = B * K
+    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (M, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError("attention_decode_block: qkv [B*K, 3*H*64], caches [B, H, Tmax, 64] ([B, Tmax, H, 64] row-major), contiguous")
+    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("attention_decode_block: qkv and the caches share one dtype, fp32 or bf16")
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (M,) or not positions.is_contiguous():
+        raise TypeError(f"attention_decode_block: positions must be a contiguous int32 [{M}] tensor")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError("attention_decode_block: error_word is an int32 [1] tensor on the device (the kernel's sticky word)")
+    D = Hh * 64
+    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
+    if out_dtype == "f16c":
+        out = torch.zeros((M, 4 * D), dtype=torch.uint8, device=qkv.device)
+    else:
+        out = torch.zeros((M, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
+    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    H.check(H.load().kx_attention_decode_block(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                               H.ptr(stats_out), B, K, Hh, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
+                                               _stream()), "kx_attention_decode_block")
+    return out
+
+
+def spec_accept(picked, *, fed=None, rows_per_sequence, positions, prefill_len=0, history, hist_len, out_tokens, n_out, finished,
+                next_tokens, max_new_tokens, step, ngram_max=2, eos_token_id=None, pad_token_id=1, out_src=None, emitted=None,
+                draft_from=None):
+    """The accept-and-draft launch of a speculative verify step (kx_spec_accept in include/kosmosx_hip.h).  ``picked`` int64
+    [B * Kin]: the greedy picks of the step's logits block, Kin = 1 (the prefill's row; ``fed`` unused, ``prefill_len`` read) or
+    K = ``rows_per_sequence``; ``fed`` int64 [B * Kin]: what those rows were fed.  Per sequence it accepts the drafts the picks
+    confirm, appends the emitted tokens to ``out_tokens`` [B, >= max_new_tokens] / ``history`` [B, n] (int64) and advances
+    ``n_out`` / ``hist_len`` [B] and ``positions`` [B * K] (int32), keeps ``finished`` [B] uint8, and writes the next block's
+    tokens to ``next_tokens`` int64 [B * K]: the last emitted token, then drafts from ``draft_from`` int64 [B, n] (per output
+    slot) or from the lookup of the sequence's last n-gram (n <= ``ngram_max``) in its own history.  Optional ``out_src`` int32
+    [B, out_ld] and ``emitted`` int32 [B, >= step + 1].  Everything stays on the device.  Returns None."""
+    _need_cuda(picked, fed, positions, history, hist_len, out_tokens, n_out, finished, next_tokens, out_src, emitted, draft_from)
+    K = int(rows_per_sequence)
+    for name, t, dt in (("picked", picked, torch.int64), ("fed", fed, torch.int64), ("positions", positions, torch.int32),
+                        ("history", history, torch.int64), ("hist_len", hist_len, torch.int32), ("out_tokens", out_tokens, torch.int64),
+                        ("n_out", n_out, torch.int32), ("finished", finished, torch.uint8), ("next_tokens", next_tokens, torch.int64),
+                        ("out_src", out_src, torch.int32), ("emitted", emitted, torch.int32), ("draft_from", draft_from, torch.int64)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"spec_accept: {name} must be a contiguous {dt} tensor")
+    B = finished.shape[0]
+    Kin = picked.numel() // max(B, 1)
+    if picked.dim() != 1 or picked.numel() != B * Kin or Kin not in (1, K):
+        raise ValueError(f"spec_accept: picked must be [B] or [B * {K}] for B = {B}")
+    if Kin == K and (fed is None or tuple(fed.shape) != (B * K,)):
+        raise ValueError(f"spec_accept: fed must be [{B * K}] alongside picked [{B * K}]")
+    for name, t, shape in (("positions", positions, (B * K,)), ("next_tokens", next_tokens, (B * K,)), ("hist_len", hist_len, (B,)),
+                           ("n_out", n_out, (B,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"spec_accept: {name} must have shape {list(shape)}")
+    for name, t in (("history", history), ("out_tokens", out_tokens), ("out_src", out_src), ("emitted", emitted), ("draft_from", draft_from)):
+        if t is not None and (t.dim() != 2 or t.shape[0] != B):
+            raise ValueError(f"spec_accept: {name} must be [{B}, n]")
+    if out_src is not None and out_src.shape[1] != out_tokens.shape[1]:
+        raise ValueError("spec_accept: out_src has the shape of out_tokens")
+    a = H.SpecArgs()
+    a.ngram_max, a.B, a.K, a.Kin = int(ngram_max), B, K, Kin
+    a.fed, a.picked, a.positions, a.prefill_len = (H.ptr(fed) if Kin == K else None), picked.data_ptr(), positions.data_ptr(), int(prefill_len)
+    a.history, a.hist_ld, a.hist_len = history.data_ptr(), history.shape[1], hist_len.data_ptr()
+    a.out_tokens, a.out_ld, a.n_out = out_tokens.data_ptr(), out_tokens.shape[1], n_out.data_ptr()
+    a.finished = finished.data_ptr()
+    a.max_new, a.eos_id, a.pad_id = int(max_new_tokens), (-1 if eos_token_id is None else int(eos_token_id)), int(pad_token_id)
+    a.step = int(step)
+    a.out_src = H.ptr(out_src)
+    a.emitted, a.emitted_ld = H.ptr(emitted), (0 if emitted is None else emitted.shape[1])
+    a.draft_from, a.draft_ld = H.ptr(draft_from), (0 if draft_from is None else draft_from.shape[1])
+    a.next_tokens = next_tokens.data_ptr()
+    H.check(H.load().kx_spec_accept(C.byref(a), _stream()), "kx_spec_accept")
+
+
 def beam_step(logits, scores_in, *, num_beams, step, pool, done, scores_out, next_token, parent, src_row, scratch,
               length_penalty=1.0, early_stopping=False, eos_token_id=None, pad_token_id=1):
     """One beam-search step (kx_beam_step in include/kosmosx_hip.h) over fp32 `logits` [B * Win, V] (row stride >= V), Win = 1 at

@@ -22,7 +22,16 @@ One JSON line per batch size.  --only a|b|c restricts the run to one variant (fo
 batch size, alternating, best of --reps each:
   (a) generate() with every constraint at its default — no kx_constrain_logits launch;
   (k) generate(no_repeat_ngram_size=N, bad_words_ids=[...]) — one kx_constrain_logits launch per token in front of the sampler.
---only a|k restricts the run (for a kernel trace of one variant)."""
+--only a|k restricts the run (for a kernel trace of one variant).
+
+--prompt-lookup D: the prompt-lookup speculation leg alone (greedy; B * (D + 1) <= 16).  The prompt is a block of --prefix / 4
+random tokens four times over.  Per batch size, alternating, best of --reps each; every leg prints ms per EMITTED token after the
+prefill and the tokens emitted per verify step:
+  (g) plain greedy generate() — one token per step;
+  (l) generate(prompt_lookup_num_tokens=D) — the lookup proper, on whatever the (random-weight) model makes of the repeated prompt;
+  (u) _draft_from = the plain run's own output: every draft is right, the upper bound;
+  (x) _draft_from = that output with every id changed: every draft is wrong, the price of the K-row step when nothing is accepted.
+--only g|l|u|x restricts the run (for a kernel trace of one variant)."""
 import argparse, json, os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -44,10 +53,13 @@ ap.add_argument("--min-prefix", type=int, default=16)
 ap.add_argument("--num-beams", type=int, default=0)
 ap.add_argument("--no-repeat-ngram", type=int, default=0)
 ap.add_argument("--bad-words", type=int, default=0)
+ap.add_argument("--prompt-lookup", type=int, default=0)
+ap.add_argument("--ngram", type=int, default=2)
+ap.add_argument("--eos-poll", type=int, default=2)   # (the lookup leg: a row that finished keeps stepping until the poll notices)
 a = ap.parse_args()
 constrained = bool(a.no_repeat_ngram or a.bad_words)
 if a.only is None:
-    a.only = "wp" if a.num_beams else "ak" if constrained else "ars" if a.ragged else "abc"
+    a.only = "glux" if a.prompt_lookup else "wp" if a.num_beams else "ak" if constrained else "ars" if a.ragged else "abc"
 dev = torch.device("cuda", 0)
 V = 32002
 m = KosmosLanguage(vocab_size=V, dim=2048, _seed=0).eval().to(dev)
@@ -175,6 +187,48 @@ def constraints_leg():
         print(json.dumps(res), flush=True)
 
 
+def lookup_leg():
+    D = a.prompt_lookup
+    for B in (int(b) for b in a.batches.split(",")):
+        if B * (D + 1) > 16:
+            print(json.dumps({"skipped": f"B={B}: {B} x {D + 1} rows exceed the 16 rows of a weight-streaming step"}), flush=True)
+            continue
+        block = torch.randint(0, V, (B, max(a.prefix // 4, 1)), generator=torch.Generator().manual_seed(0))
+        tok = block.repeat(1, 4).to(dev)
+        T = tok.shape[1]
+        pre = timed(lambda t: m(t, incremental_state={"max_len": T + a.new + D}), tok)
+        plain = m.generate(tok, a.new)
+        wrong = (plain + 1) % V
+        LK = dict(prompt_lookup_num_tokens=D, max_matching_ngram_size=a.ngram, output_acceptance=True, eos_poll=a.eos_poll)
+        runs = {"g": lambda t: m.generate(t, a.new), "l": lambda t: m.generate(t, a.new, **LK),
+                "u": lambda t: m.generate(t, a.new, _draft_from=plain, **LK), "x": lambda t: m.generate(t, a.new, _draft_from=wrong, **LK)}
+        best, steps, same = {}, {"g": a.new}, {}
+        for k in a.only:
+            if k != "g":                                        # (also the warm-up of the K-row step's packs and workspaces)
+                out, acc = runs[k](tok)
+                steps[k], same[k] = acc.shape[1], bool(torch.equal(out, plain))
+        for rep in range(a.reps):                               # alternating, so that all see the same clocks
+            for k in a.only:
+                dt = timed_once(runs[k], tok, warm=rep == 0)
+                best[k] = min(best.get(k, dt), dt)
+        res = {"workload": f"KosmosLanguage prompt-lookup speculation, B={B}, D={D}, ngram {a.ngram}, prompt {T} (one block x 4), "
+                           f"{a.new} new tokens, {a.precision}, greedy", "prefill_ms": round(pre * 1e3, 3)}
+        names = {"g": "g_plain", "l": "l_lookup", "u": "u_all_right", "x": "x_all_wrong"}
+        for k in a.only:
+            # the first token comes from the prefill: new - 1 tokens over steps - 1 decode steps
+            res[names[k] + "_ms_per_token"] = round((best[k] - pre) / (a.new - 1) * 1e3, 4)
+            res[names[k] + "_tokens_per_step"] = round((a.new - 1) / max(steps[k] - 1, 1), 3)
+            issued = steps[k] if k == "g" else min(a.new, -(-steps[k] // a.eos_poll) * a.eos_poll)   # up to the poll that ended the loop
+            res[names[k] + "_ms_per_issued_step"] = round((best[k] - pre) / max(issued - 1, 1) * 1e3, 4)
+            if k in same:
+                res[names[k] + "_equals_plain"] = same[k]
+        print(json.dumps(res), flush=True)
+
+
+if a.prompt_lookup:
+    with torch.no_grad():
+        lookup_leg()
+    sys.exit(0)
 if a.num_beams:
     with torch.no_grad():
         beam_leg()
