@@ -888,7 +888,8 @@ int kx_add_rowvec(const float* x, const float* vec, float* out, int64_t rows, in
 /* The vision tower's embeddings as stand-alone steps for the op-by-op training forward (HF CLIPVisionEmbeddings):
  * kx_patchify: pixels [B,3,image,image] fp32 -> patch rows [B*(image/patch)^2, kpad] (fp32 for KX_PREC_F32, bf16 for
  * KX_PREC_BF16), columns (channel, dy, dx) as nn.Conv2d's weight.flatten(1), zero padded to kpad;
- * kx_vit_assemble: x[b] = cat(class_embedding, patch_out[b]) + position_embedding, [B, tokens, dim] fp32. */
+ * kx_vit_assemble: x[b] = cat(class_embedding, patch_out[b]) + position_embedding, [B, tokens, dim] fp32;
+ * dim % 4 == 0, 16-byte aligned buffers (rows move as 16-byte vectors). */
 int kx_patchify(const float* pixels, void* patches, int64_t B, int32_t image, int32_t patch, int32_t kpad, int32_t prec,
                 void* stream);
 int kx_vit_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int64_t B, int32_t tokens,

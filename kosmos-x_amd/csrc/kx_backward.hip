@@ -627,8 +627,9 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   s = (red[0] + red[1]) + (red[2] + red[3]);
-  const float lse = mx + logf(s);
-  if (threadIdx.x == 0) loss_rows[row] = ignore ? 0.f : (lse - lr[tg]);
+  // log(s) - (logit[target] - max), not (max + log(s)) - logit[target]: the latter rounds the sum to an ulp of |max| first
+  // (3e-4 on the loss with logits near 1e4)
+  if (threadIdx.x == 0) loss_rows[row] = ignore ? 0.f : (logf(s) - (lr[tg] - mx));
   if (dlogits) {
     float* dr = dlogits + row * ldd;
     const float inv = 1.0f / s;
@@ -1794,7 +1795,9 @@ extern "C" int kx_adamw(float* param, const float* grad, float* m, float* v, int
                         float eps, float weight_decay, int64_t step, const float* grad_norm_sq, float max_norm,
                         void* stream) {
   KX_REQUIRE(param && grad && m && v && n > 0 && step >= 1, "kx_adamw: bad arguments");
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  // bias corrections in double, rounded once: 1 - 0.999^t cancels to ~t * 1e-3 at small t and would keep a float powf's
+  // absolute error (5e-6 of the step at steps 2 to 5)
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   hipStream_t s = (hipStream_t)stream;
   KxProfScope prof(KX_K_MISC, n, 0, 26, s);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, param, grad, m, v, (long long)n, lr,

@@ -508,6 +508,8 @@ extern "C" int kx_patchify(const float* pixels, void* patches, int64_t B, int32_
 
 extern "C" int kx_vit_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int64_t B,
                                int32_t tokens, int32_t dim, void* stream) {
-  KX_REQUIRE(patch_out && cls && pos && x && B > 0 && tokens > 1 && dim > 0, "kx_vit_assemble: bad arguments");
+  KX_REQUIRE(patch_out && cls && pos && x && B > 0 && tokens > 1 && dim > 0 && dim % 4 == 0 &&
+                 (((uintptr_t)patch_out | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)x) & 15) == 0,
+             "kx_vit_assemble: null pointer, bad shape, dim %% 4 != 0 or unaligned buffers");
   return kx_launch_vit_assemble(patch_out, cls, pos, x, B, tokens, dim, (hipStream_t)stream);
 }

@@ -222,9 +222,16 @@ def xpos_backward_(dqkv, D, T, tables, qscale):
 
 
 def embed_backward(tokens, dx, vocab, max_pos, pos_offset=0, out_embed=None, out_pos=None):
-    """tokens [B,T] int64, dx [B,T,d] -> (dembed [vocab,d], dpos [max_pos,d]; rows of dpos outside [2, 2+T) are zero)."""
+    """tokens [B,T] int64, dx [B,T,d] -> (dembed [vocab,d], dpos [max_pos,d]; rows of dpos outside
+    [2+pos_offset, 2+pos_offset+T) are zero)."""
     _need_cuda(tokens, dx, out_embed, out_pos)
     B, T, d = dx.shape
+    if pos_offset < 0 or 2 + pos_offset + T > max_pos:       # the kernel writes dpos rows 2+pos_offset+t unchecked
+        raise ValueError(f"embed_backward: position rows [{2 + pos_offset}, {2 + pos_offset + T}) outside max_pos = {max_pos}")
+    if out_pos is not None and (out_pos.shape[0] < max_pos or out_pos.shape[1] != d):
+        raise ValueError(f"embed_backward: out_pos {tuple(out_pos.shape)} is smaller than [max_pos = {max_pos}, {d}]")
+    if out_embed is not None and (out_embed.shape[0] < vocab or out_embed.shape[1] != d):
+        raise ValueError(f"embed_backward: out_embed {tuple(out_embed.shape)} is smaller than [vocab = {vocab}, {d}]")
     de = out_embed if out_embed is not None else torch.empty((vocab, d), dtype=torch.float32, device=dx.device)
     dp = out_pos.zero_() if out_pos is not None else torch.zeros((max_pos, d), dtype=torch.float32, device=dx.device)
     H.check(H.load().kx_embed_backward(H.ptr(tokens), H.ptr(dx), B, T, d, vocab, pos_offset, H.ptr(de), H.ptr(dp), _stream()),
