@@ -791,6 +791,52 @@ int kx_decoder_decode_step_block(const kx_decoder_weights* w, const int64_t* tok
                                  int32_t* error_word, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scoring candidates over a shared prompt cache (added within ABI 7: three functions are appended; no struct, no existing layout
+ * moves and the kx_struct_id list is unchanged, so kx_version() stays 7).
+ *
+ * C candidate continuations of K fed rows each are scored in one pass over the weights against the KV cache a prefill of Bc
+ * prompts left: several candidates read the same cache sequence and nobody appends to it.
+ *
+ * kx_attention_decode_shared: kx_attention_decode_block's rows and addressing — M = C * K rows, row r = c * K + j the j-th row of
+ *   candidate c, positions [C * K] int32 (device) with t = positions[r], t0 = positions[c * K] and t == t0 + j required — with
+ *   candidate c reading cache sequence cache_seq[c] (cache_seq [C] int32, device; caches [Bc, ...]; any mapping: repeated,
+ *   unordered, unused sequences).  Row r attends over cache keys 0 .. t0 - 1 of that sequence and over keys t0 + i, i = 0..j, read
+ *   from qkv row c * K + i.  It APPENDS NOTHING: the caches are const and bitwise unchanged by the launch, rows >= t0 of a cache
+ *   sequence are never read.  Same slots, key order and arithmetic: one launch gives, bit for bit, the outputs and stats_out of
+ *   kx_attention_decode_block run on a cache replicated per candidate (sequence c of the replica = sequence cache_seq[c]), and for
+ *   K = 1 those of kx_attention_decode_ragged on that replica; every output form (KX_F32, KX_BF16, KX_F16C, KX_F16P), both cache
+ *   layouts (tuning key 9).  cache_seq[c] is requested together with the two position words: one scalar round trip before the
+ *   one vector round trip, as in the block form.  A row with cache_seq[c] outside [0, Bc), t outside [0, Tmax), t0 < 0 or
+ *   t != t0 + j writes nothing and ORs KX_RAGGED_ERR_CACHE into *error_word; the other rows are unaffected.  K in 1..16,
+ *   C * K <= 65535.
+ * kx_decoder_score_step: kx_decoder_decode_step_block with C candidates of K rows, Bc cache sequences and cache_seq: kx_step_prepare
+ *   on the C * K tokens and positions (pos_shift as there), the qkv launch with xpos_T = C * K, kx_attention_decode_shared in place
+ *   of the block attention — the caches [L, Bc, heads, Tmax, 64] are const and stay untouched — everything else row-wise.  Up to 16
+ *   rows the step streams the weights, above that it runs the tile GEMMs.  x [C * K, 1, dim] and xpos_rows [4, C * K, 32] scratch
+ *   zeroed once by the caller; logits [C * K, vocab]; workspace = kx_decoder_workspace_bytes(w, C * K, 1, prec).
+ * kx_token_logprob: one launch, one 256-thread workgroup per output row r = 0 .. rows - 1:
+ *     out[r] = x[target[r]] - logsumexp(x),  x = logits[row_index[r] * ld + 0 .. V)   (fp32; ld >= V elements between rows)
+ *   row_index [rows] int32 (device) may repeat and reorder rows of the [rows_available, ld] logits buffer — one logits row serves
+ *   many outputs without a copy; NULL means row_index[r] = r.  The arithmetic is kx_cross_entropy's (the same device code):
+ *   (x[target] - max) - log(sum exp(x - max)), one pass for the max and one for the sum, no softmax materialised; deterministic.
+ *   target[r] outside [0, V) or row_index[r] outside [0, rows_available): out[r] = 0.0 exactly, nothing is read through the bad
+ *   index.  A -inf logit at the target gives -inf (the row's maximum being finite); a NaN anywhere in the row gives NaN.
+ *   Host checks (KX_ERR_INVALID_ARG, nothing launched): null logits / target / out, rows < 1, rows_available < 1, V < 1, ld < V.
+ * None of the three allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int kx_attention_decode_shared(const void* qkv, const void* kcache, const void* vcache, void* out, int32_t odt, float* stats_out,
+                               int64_t C, int64_t K, int64_t H, const int32_t* positions, const int32_t* cache_seq, int64_t Bc,
+                               int64_t Tmax, int32_t prec, int32_t* error_word, void* stream);
+int kx_decoder_score_step(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                          int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t C, int64_t K,
+                          const int32_t* positions, const int32_t* cache_seq, int64_t Bc, const float* xq_cs, const float* xq_ss,
+                          const float* xk_cs, const float* xk_ss, float* xpos_rows, const void* kcache, const void* vcache,
+                          int64_t Tmax, void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
+                          int32_t* error_word, void* stream);
+int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int64_t ld, const int32_t* row_index,
+                     const int64_t* target, float* out, int64_t rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before
  * Kosmos.forward, on the device.  Integer / byte work; results are bit-identical to the HF processor.
  * ------------------------------------------------------------------------------------------ */

@@ -1144,8 +1144,11 @@ struct DecodeParams {
 struct RaggedParams { const int* positions; int* err; int Tmax; };
 // the block form (a second pack member after RaggedParams): K consecutive rows of the launch are ONE cache sequence
 struct BlockParams { int K; };
+// the shared form (a third pack member): candidate z of the launch reads cache sequence cache_seq[z] of Bc and appends nothing
+struct SharedParams { const int* cache_seq; int Bc; };
 template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
 template <typename A, typename B2, typename... Rest> __device__ __forceinline__ const B2& second_arg(const A&, const B2& b, const Rest&...) { return b; }
+template <typename A, typename B2, typename C2, typename... Rest> __device__ __forceinline__ const C2& third_arg(const A&, const B2&, const C2& c, const Rest&...) { return c; }
 
 template <typename T> struct Ld4;
 template <> struct Ld4<bf16_t> {
@@ -1183,10 +1186,16 @@ template <> struct Ld4<float> {
 // workgroups of (H, B * K) with the division done by the dispatcher); the append of row t is the side
 // store it always was: no workgroup of the launch reads a cache row >= t0.  A row whose position leaves [0, Tmax) or is not
 // t0 + j writes nothing and sets KX_RAGGED_ERR_CACHE.  Everything BLOCK adds sits under `if constexpr (BLOCK)`.
+// SHARED (R = RaggedParams, BlockParams, SharedParams; kx_attention_decode_shared): BLOCK's rows and addressing with the launch's
+// z-th group of K rows a CANDIDATE that reads cache sequence cache_seq[z] — several candidates may name the same one — and with no
+// append: the caches are read only, so candidates of one sequence never meet.  cache_seq[z] is requested with the two position words
+// (still one scalar round trip) and checked with them, bitwise; what BLOCK computes on `t`, `t0` and the cache base is untouched,
+// hence the bits of the block launch on a cache replicated per candidate.  Everything SHARED adds sits under `if constexpr (SHARED)`.
 template <typename T, typename... R>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, const R... r) {
   constexpr bool RAGGED = sizeof...(R) != 0;
-  constexpr bool BLOCK = sizeof...(R) == 2;
+  constexpr bool BLOCK = sizeof...(R) >= 2;
+  constexpr bool SHARED = sizeof...(R) == 3;
   __shared__ float sm_m[16], sm_l[16], sm_o[16][64];
   typedef typename Ld4<T>::raw raw;
   constexpr int UK = Ld4<T>::UK;
@@ -1203,8 +1212,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
     b = cb * second_arg(r...).K + jr;
     t = rp.positions[b];
     t0 = rp.positions[b - jr];
+    bool bad_seq = false;
+    if constexpr (SHARED) {                                 // the candidate's cache sequence: a third word of the same round trip
+      const SharedParams& sp = third_arg(r...);
+      cb = sp.cache_seq[blockIdx.z];
+      bad_seq = (cb < 0) | (cb >= sp.Bc);
+    }
     // (one condition on both words, bitwise: evaluated after BOTH loads are back — neither waits behind a branch on the other)
-    if ((t < 0) | (t >= rp.Tmax) | (t0 < 0) | (t0 > t) | ((unsigned)t - (unsigned)t0 != (unsigned)jr)) {   // (uniform over the workgroup)
+    if ((t < 0) | (t >= rp.Tmax) | (t0 < 0) | (t0 > t) | ((unsigned)t - (unsigned)t0 != (unsigned)jr) | bad_seq) {   // (uniform over the workgroup)
       if (tid == 0) atomicOr(rp.err, KX_RAGGED_ERR_CACHE);
       return;
     }
@@ -1238,9 +1253,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
       vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
     }
   }
-  if (wave == 0 && grp < 2) {                              // append row t: 64 k + 64 v elements per head
-    const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
-    *reinterpret_cast<raw*>((grp == 0 ? kc : vc) + (long long)t * p.cache_row * es) = nv;
+  if constexpr (!SHARED) {
+    if (wave == 0 && grp < 2) {                            // append row t: 64 k + 64 v elements per head
+      const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
+      *reinterpret_cast<raw*>((grp == 0 ? kc : vc) + (long long)t * p.cache_row * es) = nv;
+    }
   }
   float q[4];
   Ld4<T>::unpack(qr, q);
@@ -1356,10 +1373,11 @@ int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t
 }
 
 // positions == nullptr: the uniform launch at host position t; else the ragged launch (t unused).  K > 0: the block launch — B counts
-// the ROWS (sequences * K), the caches hold B / K sequences.
+// the ROWS (sequences * K), the caches hold B / K sequences.  cache_seq != nullptr: the shared launch — B / K candidates, Bc sequences.
 static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, void* vcache, void* out, int32_t odt,
                                  float* stats_out, int64_t B, int64_t H, int64_t t, const int32_t* positions, int32_t* err,
-                                 int64_t Tmax, int32_t prec, void* stream, int64_t K = 0) {
+                                 int64_t Tmax, int32_t prec, void* stream, int64_t K = 0,
+                                 const int32_t* cache_seq = nullptr, int64_t Bc = 0) {
   KX_REQUIRE(qkv && kcache && vcache && out, "%s: null pointer", fn);
   KX_REQUIRE(B > 0 && H > 0 && t >= 0 && t < Tmax, "%s: position %lld outside the cache of %lld rows", fn,
              (long long)t, (long long)Tmax);
@@ -1386,7 +1404,11 @@ static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, 
   if (K > 0) {
     const BlockParams bp{(int)K};
     const dim3 gb((unsigned)H, (unsigned)K, (unsigned)(B / K));   // the workgroups of (H, B) with the row's (sequence, index) as coordinates
-    if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
+    if (cache_seq) {
+      const SharedParams sp{cache_seq, (int)Bc};
+      if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams, SharedParams>), gb, dim3(256), 0, s, p, r, bp, sp);
+      else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, BlockParams, SharedParams>), gb, dim3(256), 0, s, p, r, bp, sp);
+    } else if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
     else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
   } else if (positions) {
     if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams>), grid, dim3(256), 0, s, p, r);
@@ -1424,4 +1446,19 @@ extern "C" int kx_attention_decode_block(const void* qkv, void* kcache, void* vc
   KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll, "kx_attention_decode_block: Tmax=%lld outside the 32-bit positions", (long long)Tmax);
   return attention_decode_impl("kx_attention_decode_block", qkv, kcache, vcache, out, odt, stats_out, B * K, H, 0, positions, error_word,
                                Tmax, prec, stream, K);
+}
+
+extern "C" int kx_attention_decode_shared(const void* qkv, const void* kcache, const void* vcache, void* out, int32_t odt,
+                                          float* stats_out, int64_t C, int64_t K, int64_t H, const int32_t* positions,
+                                          const int32_t* cache_seq, int64_t Bc, int64_t Tmax, int32_t prec, int32_t* error_word,
+                                          void* stream) {
+  KX_REQUIRE(positions && cache_seq && error_word, "kx_attention_decode_shared: null positions / cache_seq / error_word");
+  KX_REQUIRE(K >= 1 && K <= 16, "kx_attention_decode_shared: K=%lld outside 1..16 rows per candidate", (long long)K);
+  KX_REQUIRE(C > 0 && C <= 65535 / K, "kx_attention_decode_shared: C=%lld candidates of K=%lld rows exceed the grid limits", (long long)C,
+             (long long)K);
+  KX_REQUIRE(Bc > 0 && Bc <= 0x7fffffffll, "kx_attention_decode_shared: Bc=%lld cache sequences", (long long)Bc);
+  KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll, "kx_attention_decode_shared: Tmax=%lld outside the 32-bit positions", (long long)Tmax);
+  // (the kernel's shared form has no store to the caches: the append is compiled out)
+  return attention_decode_impl("kx_attention_decode_shared", qkv, const_cast<void*>(kcache), const_cast<void*>(vcache), out, odt, stats_out,
+                               C * K, H, 0, positions, error_word, Tmax, prec, stream, K, cache_seq, Bc);
 }

@@ -614,19 +614,8 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
   const float* lr = logits + row * ld;
   const long long tg = target[row];
   const bool ignore = tg < 0 || tg >= V;            // ignore_index rows: zero loss, zero gradient
-  float mx = -INFINITY;
-  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, lr[c]);
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float s = 0.f;
-  for (int c = threadIdx.x; c < V; c += 256) s += expf(lr[c] - mx);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  s = (red[0] + red[1]) + (red[2] + red[3]);
+  float mx, s;
+  block_max_sumexp(lr, V, red, mx, s);                // (kx_common.h: shared with kx_token_logprob)
   // log(s) - (logit[target] - max), not (max + log(s)) - logit[target]: the latter rounds the sum to an ulp of |max| first
   // (3e-4 on the loss with logits near 1e4)
   if (threadIdx.x == 0) loss_rows[row] = ignore ? 0.f : (logf(s) - (lr[tg] - mx));

@@ -289,6 +289,27 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// max and sum(exp(x - max)) of lr[0:V] over a 256-thread workgroup, left in every thread: one pass each, threads stride the row,
+// xor-butterfly per wave, the four waves' words through `red` (4 floats of LDS) in a fixed tree — deterministic.  What
+// kx_cross_entropy and kx_token_logprob take their log-sum-exp from: log-prob = (x[target] - max) - log(sum), not
+// x[target] - (max + log(sum)), which rounds the sum to an ulp of |max| first.  Ends on a barrier-free read of `red`: a caller
+// that reuses `red` synchronises first.
+__device__ __forceinline__ void block_max_sumexp(const float* __restrict__ lr, int V, float* red, float& mx, float& s) {
+  mx = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, lr[c]);
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  s = 0.f;
+  for (int c = threadIdx.x; c < V; c += 256) s += expf(lr[c] - mx);
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  s = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---- internal launchers shared between translation units ----
 int kx_launch_rows_bcast(const float* src, float* dst, int64_t B, int64_t rows, int64_t cols, hipStream_t s);
 int kx_launch_patchify(const float* pixels, void* patches, int64_t B, int image, int patch, int kpad, int prec,

@@ -691,10 +691,13 @@ extern "C" int kx_decoder_prefill(const kx_decoder_weights* w, float* x, int64_t
 // step: sequence b at positions[b] (device), xq_* / xk_* = [B, 32] tables holding each sequence's row (xpos_T = B).
 // K > 0 (the block step): B counts the ROWS, K consecutive rows are one cache sequence (kx_attention_decode_block); the caches
 // hold B / K sequences.  Everything but the attention is row-wise and does not know.
+// cache_seq != nullptr (the score step): the B / K groups of K rows are candidates, group c reads cache sequence cache_seq[c] of the
+// Bc the caches hold and nothing is appended (kx_attention_decode_shared).
 static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const int32_t* positions,
                             int32_t* error_word, const float* xq_cs, const float* xq_ss, const float* xk_cs,
                             const float* xk_ss, void* kcache, void* vcache, int64_t Tmax, void* logits, int32_t ldt,
-                            void* workspace, size_t workspace_bytes, int32_t prec, void* stream, int64_t K = 0) {
+                            void* workspace, size_t workspace_bytes, int32_t prec, void* stream, int64_t K = 0,
+                            const int32_t* cache_seq = nullptr, int64_t Bc = 0) {
   const int64_t xT = positions ? B : 1;
   const int tfmt = prec == KX_PREC_F32W24 ? 2 : prec == KX_PREC_F32W16 ? 3 : 1;   // what the streaming copies (w*_t) hold
   if (prec == KX_PREC_F32W24 || prec == KX_PREC_F32W16) prec = KX_PREC_F32;
@@ -717,7 +720,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
   KX_SPLITK_SCOPE(d.splitk, s);
   const int ct = cdt(prec);
   const size_t es = esz(prec);
-  const size_t layer_bytes = (size_t)(K > 0 ? B / K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
+  const size_t layer_bytes = (size_t)(cache_seq ? Bc : K > 0 ? B / K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
   // One token per sequence, up to 16 sequences: the step is 120 dependent launches of weight-streaming work, and launches
   // are what it costs (~6 us each) — tile 16 does each GEMM in one launch and takes the LayerNorm and
   // statistics-finalize kernels in as prologues: 5 launches per layer instead of 13.  bf16 operands, or fp32 operands on the
@@ -754,7 +757,11 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
       if (w->xpos) { q.xq_cs = xq_cs; q.xq_ss = xq_ss; q.xk_cs = xk_cs; q.xk_ss = xk_ss; q.xT = xT; q.xdim = D; }
       q.W_tiled = L.wqkv_t; q.tiled_fmt = tfmt; q.prec = prec;
       KX_TRY(gemv16(q, s));
-      if (K > 0)
+      if (cache_seq)
+        KX_TRY(kx_attention_decode_shared(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
+                                          pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B / K, K, w->heads, positions,
+                                          cache_seq, Bc, Tmax, prec, error_word, stream));
+      else if (K > 0)
         KX_TRY(kx_attention_decode_block(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
                                          pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, Tmax,
                                          prec, error_word, stream));
@@ -797,7 +804,11 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     KX_FAM(0);
     KX_TRY(gemm(d.h, D, L.wqkv, D, d.qkv, 3 * D, qdt(prec), M, 3 * D, L.bqkv, nullptr, 0, 0.125f, D, prec, s,
                 w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? xT : 0, w->xpos ? D : 0));
-    if (K > 0)
+    if (cache_seq)
+      KX_TRY(kx_attention_decode_shared(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
+                                        w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, cache_seq, Bc, Tmax, prec,
+                                        error_word, stream));
+    else if (K > 0)
       KX_TRY(kx_attention_decode_block(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
                                        w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, Tmax, prec, error_word, stream));
     else if (positions)
@@ -886,4 +897,28 @@ extern "C" int kx_decoder_decode_step_block(const kx_decoder_weights* w, const i
   return decode_step_impl("kx_decoder_decode_step_block", w, x, M, 0, positions, error_word, r, r ? r + M * 32 : nullptr,
                           r ? r + 2 * M * 32 : nullptr, r ? r + 3 * M * 32 : nullptr, kcache, vcache, Tmax, logits, ldt, workspace,
                           workspace_bytes, prec, stream, K);
+}
+
+extern "C" int kx_decoder_score_step(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                     int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t C, int64_t K,
+                                     const int32_t* positions, const int32_t* cache_seq, int64_t Bc, const float* xq_cs,
+                                     const float* xq_ss, const float* xk_cs, const float* xk_ss, float* xpos_rows,
+                                     const void* kcache, const void* vcache, int64_t Tmax, void* logits, int32_t ldt,
+                                     void* workspace, size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
+  KX_REQUIRE(w && positions && cache_seq && error_word, "kx_decoder_score_step: null pointer");
+  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_score_step");
+  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
+             "kx_decoder_score_step: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
+  KX_REQUIRE(K >= 1 && K <= 16, "kx_decoder_score_step: K=%lld outside 1..16 rows per candidate", (long long)K);
+  KX_REQUIRE(C > 0 && C <= 65535 / K && Bc > 0 && Tmax > 0, "kx_decoder_score_step: empty batch / cache");
+  const bool xp = w->xpos != 0;
+  const int64_t M = C * K;
+  KX_TRY(kx_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
+                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, M, w->dim, vocab, max_pos, pos_shift, Tmax,
+                         error_word, stream));
+  const float* r = xp ? xpos_rows : nullptr;
+  // (the shared attention has no store to the caches)
+  return decode_step_impl("kx_decoder_score_step", w, x, M, 0, positions, error_word, r, r ? r + M * 32 : nullptr,
+                          r ? r + 2 * M * 32 : nullptr, r ? r + 3 * M * 32 : nullptr, const_cast<void*>(kcache),
+                          const_cast<void*>(vcache), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream, K, cache_seq, Bc);
 }

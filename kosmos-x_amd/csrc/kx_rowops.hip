@@ -334,7 +334,41 @@ __global__ __launch_bounds__(256) void rows_bcast_kernel(const float* __restrict
   for (int c = threadIdx.x; c < (cols >> 2); c += 256) o[c] = s[c];
 }
 
+// out[r] = log softmax(logits[row_index[r], 0:V])[target[r]]: one workgroup per output row, kx_cross_entropy's arithmetic
+// (block_max_sumexp, kx_common.h) without the softmax ever written.  A target or a row index out of range: 0.0, nothing read
+// through it (uniform over the workgroup: nobody reaches a barrier).
+__global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restrict__ logits, long long ld, int V,
+                                                            long long rows_available, const int* __restrict__ row_index,
+                                                            const long long* __restrict__ target, float* __restrict__ out) {
+  __shared__ float red[4];
+  const long long r = blockIdx.x;
+  const long long row = row_index ? (long long)row_index[r] : r;
+  const long long tg = target[r];
+  if ((tg < 0) | (tg >= V) | (row < 0) | (row >= rows_available)) {
+    if (threadIdx.x == 0) out[r] = 0.f;
+    return;
+  }
+  const float* lr = logits + row * ld;
+  float mx, s;
+  block_max_sumexp(lr, V, red, mx, s);
+  if (threadIdx.x == 0) out[r] = (lr[tg] - mx) - logf(s);
+}
+
 }  // namespace
+
+extern "C" int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int64_t ld, const int32_t* row_index,
+                                const int64_t* target, float* out, int64_t rows, void* stream) {
+  KX_REQUIRE(logits && target && out, "kx_token_logprob: null pointer");
+  KX_REQUIRE(rows > 0 && rows <= 0x7fffffffll && rows_available > 0, "kx_token_logprob: rows=%lld of rows_available=%lld",
+             (long long)rows, (long long)rows_available);
+  KX_REQUIRE(V >= 1 && V <= 0x7fffffffll && ld >= V, "kx_token_logprob: V=%lld, ld=%lld (V >= 1, ld >= V)", (long long)V, (long long)ld);
+  hipStream_t s = (hipStream_t)stream;
+  KxProfScope prof(KX_K_MISC, rows, V, 32, s);
+  hipLaunchKernelGGL(token_logprob_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, (long long)ld, (int)V,
+                     (long long)rows_available, row_index, (const long long*)target, out);
+  KX_CHECK_LAUNCH("kx_token_logprob");
+  return KX_OK;
+}
 
 extern "C" int kx_layernorm(const float* x, const float* pre_add, const float* gamma, const float* beta, void* y,
                             kx_dtype ydt, int64_t rows, int64_t cols, float eps, int64_t rows_per_group,

@@ -24,6 +24,10 @@ the sequence's cache), kx_sample_logits picks greedily on all of them and kx_spe
 correctly, appends them, moves the positions and copies the next drafts from where the row's last n-gram occurred before.  Exact
 for greedy decoding; the host reads only the stop poll.
 
+Scoring (``score()``, score_loop): the log-likelihood of C candidate continuations over B prefilled prompts — column 0 from the
+prefill's rows, every later column from ONE step of C * (L - 1) rows in which the candidates read their prompt's cache rows and
+nobody appends (kx_decoder_score_step), the log-probs taken row by row without a softmax (kx_token_logprob).
+
 Not offered: compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
@@ -411,6 +415,114 @@ def lookup_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_to
     if output_acceptance:
         res.append(emitted[:, :used])
     return res[0] if len(res) == 1 else tuple(res)
+
+
+MAX_SCORE_LEN = 16                      # kx_decoder_score_step's K rows per candidate: a continuation feeds L - 1 <= 16 of them
+
+
+def check_score_args(batch: int, continuations, continuation_lengths=None, prompt_index=None):
+    """ValueError (naming the argument) for what score() refuses, before the device check and any launch.  Returns the host lists
+    (continuation lengths [C], prompt of every candidate [C])."""
+    if not isinstance(continuations, torch.Tensor) or continuations.dtype != torch.int64 or continuations.dim() != 2:
+        what = (f"a {continuations.dtype} tensor of shape {tuple(continuations.shape)}" if isinstance(continuations, torch.Tensor)
+                else repr(type(continuations)))
+        raise ValueError(f"continuations must be an int64 [candidates, length] tensor, got {what}")
+    C, L = continuations.shape
+    if not 1 <= L <= MAX_SCORE_LEN:
+        raise ValueError(f"continuations holds {L} tokens per candidate: 1..{MAX_SCORE_LEN} are offered, the limit of the K-row decode "
+                         "step that scores them in one pass over the weights")
+    if C < 1:
+        raise ValueError("continuations holds no candidate")
+    if continuation_lengths is None:
+        lens = [L] * C
+    else:
+        if isinstance(continuation_lengths, torch.Tensor):
+            cl = continuation_lengths
+            if cl.is_floating_point() or cl.is_complex() or cl.dtype == torch.bool or cl.dim() != 1:
+                raise ValueError(f"continuation_lengths must be {C} integers, got a {cl.dtype} tensor of shape {tuple(cl.shape)}")
+            lens = cl.tolist()                             # (the one read of a device tensor)
+        else:
+            try:
+                lens = [operator.index(l) for l in continuation_lengths]
+            except TypeError:
+                raise ValueError(f"continuation_lengths must be a sequence of {C} integers or an integer tensor, got "
+                                 f"{continuation_lengths!r}") from None
+        if len(lens) != C:
+            raise ValueError(f"continuation_lengths must have {C} entries (one per candidate), got {len(lens)}")
+        for c, l in enumerate(lens):
+            if not 1 <= l <= L:
+                raise ValueError(f"continuation_lengths[{c}] = {l} is outside 1..{L}")
+    if prompt_index is None:
+        if batch < 1 or C % batch:
+            raise ValueError(f"continuations holds {C} candidates for {batch} prompts: without a prompt_index the candidates are "
+                             "split evenly, so their number must be a multiple of the prompts'")
+        pidx = [c // (C // batch) for c in range(C)]
+    else:
+        if isinstance(prompt_index, torch.Tensor):
+            raise ValueError("prompt_index must be host integers (a list), not a tensor: the cache map is built on the host")
+        try:
+            pidx = [operator.index(b) for b in prompt_index]
+        except TypeError:
+            raise ValueError(f"prompt_index must be a sequence of {C} integers, got {prompt_index!r}") from None
+        if len(pidx) != C:
+            raise ValueError(f"prompt_index must have {C} entries (one per candidate), got {len(pidx)}")
+        for c, b in enumerate(pidx):
+            if not 0 <= b < batch:
+                raise ValueError(f"prompt_index[{c}] = {b} is outside the {batch} prompts")
+    return lens, pidx
+
+
+def score_loop(decoder, prec: str, state: dict, logits: torch.Tensor, continuations: torch.Tensor, clens: list, pidx: list,
+               plens: list, *, pos_shift: int = 0, output_logits=False):
+    """The log-probs of C candidates after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (state["max_len"] >=
+    T + L - 1), ``continuations`` int64 [C, L] on the device, ``clens`` / ``pidx`` the host lists check_score_args returned and
+    ``plens`` [B] the prompts' positions (spliced rows included).  Column 0: kx_token_logprob on the prefill's rows, addressed
+    through a row index (row len_b - 1 of the candidate's prompt; no [C, V] copy).  Columns 1..L-1: ONE kx_decoder_score_step with
+    M = C * (L - 1) rows — candidate c's row j is fed continuations[c, j] at position len_b + j, its last token is never fed — and one
+    kx_token_logprob on its rows.  L = 1 launches no step.  The positions [M] and the candidate -> cache sequence map [C] are built
+    on the host and uploaded once; the host reads the deferred id check and the step kernels' error word at the end, nothing else.
+    Returns token_logprobs fp32 [C, L] (0.0 at padded slots), and with ``output_logits`` the fp32 [C, L, V] rows."""
+    from .model import _begin_token_id_check
+    B, T, V = logits.shape
+    dev = logits.device
+    C, L = continuations.shape
+    K = L - 1
+    col = torch.arange(L, device=dev)[None, :]
+    live = col < torch.tensor(clens, dtype=torch.int64, device=dev)[:, None]                     # [C, L]
+    # padding -> the candidate's own first id: whatever it held is never range-checked or embedded (as mask_padding)
+    tokens = torch.where(live, continuations, continuations[:, :1]).contiguous()
+    check = None
+    if getattr(decoder, "validate_token_ids", True):
+        check = _begin_token_id_check(tokens, decoder.embed_tokens.weight.shape[0])              # finished after the launches
+    target = torch.where(live, tokens, torch.full((), -1, dtype=torch.int64, device=dev))       # -1: kx_token_logprob leaves 0.0
+    rows0 = torch.tensor([pidx[c] * T + plens[pidx[c]] - 1 for c in range(C)], dtype=torch.int32, device=dev)
+    flat = logits.view(B * T, V)
+    out = torch.empty((C, L), dtype=torch.float32, device=dev)
+    lp0 = ops.token_logprob(flat, target[:, 0].contiguous(), row_index=rows0)
+    out[:, 0] = lp0
+    kept = None
+    if output_logits:
+        kept = torch.zeros((C, L, V), dtype=torch.float32, device=dev)
+        kept[:, 0] = flat[rows0.long()]
+    if K > 0:
+        M = C * K
+        positions = torch.tensor([plens[pidx[c]] + j for c in range(C) for j in range(K)], dtype=torch.int32, device=dev)
+        cache_seq = torch.tensor(pidx, dtype=torch.int32, device=dev)
+        # the furthest position fed, for the host-side table / cache check of the step (the budget covers it)
+        state.update(positions=positions, score=(K, cache_seq), pos_max=max(plens[b] for b in pidx) + K - 1)
+        decoder._ragged_scratch(state, dev, rows=M)
+        fed = tokens[:, :K].reshape(M).contiguous()                                              # (K = 1: reshape alone is a strided view)
+        step = decoder._forward_incremental(None, state, None, prec, next_token=fed, pos_shift=pos_shift)[:, 0]   # [M, V]
+        out[:, 1:] = ops.token_logprob(step, target[:, 1:].reshape(M).contiguous()).view(C, K)
+        if kept is not None:
+            kept[:, 1:] = torch.where(live[:, 1:, None], step.view(C, K, V), torch.zeros((), dtype=torch.float32, device=dev))
+    if check is not None:
+        check()                                                                                  # IndexError: an id outside the vocabulary
+    if K > 0:
+        _raise_position_error(int(state["error"].item()), state)
+    if kept is not None:
+        return out, kept
+    return out
 
 
 def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0):

@@ -811,7 +811,10 @@ class Decoder(_PackedMixin, nn.Module):
         Block steps (generate(prompt_lookup_num_tokens=...)): ``state["block"]`` = K makes the ragged state step K rows per
         sequence — ``next_token`` and ``state["positions"]`` are [B * K], rows b * K + j at consecutive positions of cache
         sequence b (kx_decoder_decode_step_block); kx_spec_accept keeps both.  ``logits_out``: a caller-owned fp32 [B * K, V]
-        buffer for the step's logits.  Returns [B * K, 1, V]."""
+        buffer for the step's logits.  Returns [B * K, 1, V].
+        Score steps (score()): ``state["score"]`` = (K, cache_seq) with ``cache_seq`` an int32 [C] device tensor makes the step C
+        candidates of K rows over the B cache sequences, candidate c reading sequence cache_seq[c] and nobody appending
+        (kx_decoder_score_step); ``next_token`` and ``state["positions"]`` are [C * K].  Returns [C * K, 1, V]."""
         if self.args.activation_fn != "gelu":
             raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
                                       "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
@@ -865,7 +868,10 @@ class Decoder(_PackedMixin, nn.Module):
                 raise ValueError("a ragged incremental state (state['positions']) is stepped with next_token only")
             t = state["pos_max"]                           # the furthest row: what the table / cache must still hold
         block = int(state.get("block", 0)) if positions is not None else 0
+        score = state.get("score") if positions is not None else None
         rows = B * block if block else B                   # the rows of the step's GEMMs
+        if score is not None:
+            rows = score[1].shape[0] * score[0]
         if state["prec"] != prec:
             raise RuntimeError("precision changed between incremental steps")
         if t >= Tmax or t + 2 >= pos.shape[0]:
@@ -889,6 +895,8 @@ class Decoder(_PackedMixin, nn.Module):
             w = self._pack(sprec)[0]
         if sprec in ("bf16", "fp32", "w24", "w16") and rows <= 16:
             self._pack_decode_tiles(sprec)                 # first decode step: the streaming copy of the weights
+        if score is not None:
+            return self._score_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, score[0], score[1], logits_out)
         if block:
             return self._block_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, block, logits_out)
         if positions is not None:
@@ -982,6 +990,34 @@ class Decoder(_PackedMixin, nn.Module):
             state["x_step"].data_ptr(), B, K, positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
             state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(),
             buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_block")
+        return logits_out.view(M, 1, w.vocab)
+
+    def _score_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K, cache_seq, logits_out=None) -> torch.Tensor:
+        """One step over C candidates of K rows at consecutive device positions, candidate c on top of cache sequence cache_seq[c];
+        the caches are read only (see _forward_incremental)."""
+        lib = H.load()
+        _require_cuda(next_token, "next_token")
+        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
+        M = cache_seq.shape[0] * K
+        if next_token.shape[0] != M or positions.shape[0] != M:
+            raise ValueError("the score step's tokens and positions are [candidates * rows per candidate]")
+        dev = emb.device
+        self._ragged_scratch(state, dev, rows=M)
+        if logits_out is None:
+            logits_out = torch.empty((M, w.vocab), dtype=torch.float32, device=dev)
+        elif (tuple(logits_out.shape) != (M, w.vocab) or logits_out.dtype != torch.float32 or not logits_out.is_contiguous()
+              or logits_out.device != dev):
+            raise ValueError(f"logits_out must be a contiguous fp32 [{M}, {w.vocab}] tensor on the model's device")
+        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
+               else H.PACK_PRECS[sprec])
+        need = lib.kx_decoder_workspace_bytes(C.byref(w), M, 1, pid)
+        buf = self._ws.get(need, dev)
+        H.check(lib.kx_decoder_score_step(
+            C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
+            state["x_step"].data_ptr(), M // K, K, positions.data_ptr(), cache_seq.data_ptr(), B,
+            *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]), state["kcache"].data_ptr(), state["vcache"].data_ptr(),
+            Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(), buf.numel(), pid, state["error"].data_ptr(), _stream()),
+            "kx_decoder_score_step")
         return logits_out.view(M, 1, w.vocab)
 
     # -- torchscale-compatible surface ------------------------------------------------------------
@@ -1305,6 +1341,54 @@ class Kosmos(nn.Module):
                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
                 stop_sequences=stop_sequences)
 
+    def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
+              prompt_index=None, prompt_lengths=None, output_logits=False):
+        """Log-likelihood of candidate continuations of the prompts -> ``token_logprobs`` fp32 [C, L] on the device: entry [c, j] is
+        log P(continuations[c, j] | prompt, continuations[c, :j]), and exactly 0.0 at padded slots.  A candidate's sequence score
+        is ``token_logprobs.sum(1)``; divide by the lengths for a per-token score.  With ``output_logits`` also the fp32 [C, L, V]
+        logits rows the log-probs were taken from (zeros at padded slots).
+        ``continuations`` int64 [C, L], 1 <= L <= 16 (the K-row decode step's limit); ``continuation_lengths`` [C] ints or an
+        integer tensor, each in 1..L (default L): the slots at and after a candidate's length are padding and are ignored
+        whatever they hold.  ``prompt_index`` [C] host ints in [0, B): the prompt every candidate continues — any mapping;
+        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` as in generate().
+        The prompts are prefilled once, exactly as generate() prefills them; column 0 is read from the prefill's row at the prompt's
+        end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
+        prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
+        is T + L - 1 positions.  Ids outside the vocabulary raise IndexError, as in forward()."""
+        from . import generation
+        if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
+            raise TypeError("text_tokens and images must be instances of torch.Tensor")
+        B = text_tokens.shape[0] if text_tokens.dim() else 0
+        clens, pidx = generation.check_score_args(B, continuations, continuation_lengths, prompt_index)
+        _warn_train_mode(self)
+        _require_cuda(text_tokens, "text_tokens")
+        _require_cuda(images, "images")
+        _require_cuda(continuations, "continuations")
+        if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
+            raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
+        n_img = self.cfg.perceiver.latents
+        lens = None
+        if prompt_lengths is not None:
+            lens = generation.resolve_prompt_lengths(prompt_lengths, text_tokens.shape[0], text_tokens.shape[1], min_len=2)
+            text_tokens = text_tokens[:, :max(lens)]                         # columns no row uses
+        T = text_tokens.shape[1] + n_img
+        L = continuations.shape[1]
+        if L > 1:
+            generation.check_budget(self.decoder, T, L - 1)
+        prec = self.precision
+        with torch.no_grad():
+            if lens is not None:
+                text_tokens = generation.mask_padding(text_tokens.long(), lens)
+            img = self.clip_model.run(images, prec, self._ws)
+            img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
+            x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
+            state = {"max_len": T + L - 1}
+            logits = self.decoder._forward_incremental(None, state, x, prec)
+            return generation.score_loop(
+                self.decoder, prec, state, logits, continuations, clens, pidx,
+                [T] * B if lens is None else [n_img + l for l in lens],
+                pos_shift=n_img if self.switches.u1_inplace_alias else 0, output_logits=output_logits)
+
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
         synchronises, so the whole launch sequence is capturable).  Worth it when the forward is launch-bound
@@ -1465,6 +1549,47 @@ class KosmosLanguage(nn.Module):
                 eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
                 output_logits=output_logits, lengths=lens, no_repeat_ngram_size=no_repeat_ngram_size,
                 bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences)
+
+    def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
+              prompt_lengths=None, output_logits=False):
+        """Log-likelihood of candidate continuations of the prompts -> ``token_logprobs`` fp32 [C, L] on the device: entry [c, j] is
+        log P(continuations[c, j] | prompt, continuations[c, :j]), and exactly 0.0 at padded slots.  A candidate's sequence score
+        is ``token_logprobs.sum(1)``; divide by the lengths for a per-token score.  With ``output_logits`` also the fp32 [C, L, V]
+        logits rows the log-probs were taken from (zeros at padded slots).
+        ``continuations`` int64 [C, L], 1 <= L <= 16 (the K-row decode step's limit); ``continuation_lengths`` [C] ints or an
+        integer tensor, each in 1..L (default L): the slots at and after a candidate's length are padding and are ignored
+        whatever they hold.  ``prompt_index`` [C] host ints in [0, B): the prompt every candidate continues — any mapping;
+        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` as in generate().
+        The prompts are prefilled once, exactly as generate() prefills them; column 0 is read from the prefill's row at the prompt's
+        end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
+        prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
+        is T + L - 1 positions.  Ids outside the vocabulary raise IndexError, as in forward()."""
+        from . import generation
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("x must be an instance of torch.Tensor")
+        B = x.shape[0] if x.dim() else 0
+        clens, pidx = generation.check_score_args(B, continuations, continuation_lengths, prompt_index)
+        _warn_train_mode(self)
+        _require_cuda(x, "x")
+        _require_cuda(continuations, "continuations")
+        if x.dim() != 2:
+            raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
+        lens = None
+        if prompt_lengths is not None:
+            lens = generation.resolve_prompt_lengths(prompt_lengths, x.shape[0], x.shape[1], min_len=1)
+            x = x[:, :max(lens)]                                             # columns no row uses
+        T = x.shape[1]
+        L = continuations.shape[1]
+        if L > 1:
+            generation.check_budget(self.decoder, T, L - 1)
+        with torch.no_grad():
+            if lens is not None:
+                x = generation.mask_padding(x.long(), lens)
+            state = {"max_len": T + L - 1}
+            # (ragged prompts: the right-padded prefill needs no mask, see generate(); a candidate reads cache rows < len_b only)
+            logits = self.decoder._forward_incremental(x, state, None, self.precision)
+            return generation.score_loop(self.decoder, self.precision, state, logits, continuations, clens, pidx,
+                                         [T] * B if lens is None else lens, output_logits=output_logits)
 
 
 class KosmosTokenizer:

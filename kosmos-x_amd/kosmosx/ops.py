@@ -610,6 +610,73 @@ def attention_decode_block(qkv, kcache, vcache, positions, error_word, *, rows_p
     return out
 
 
+def attention_decode_shared(qkv, kcache, vcache, positions, cache_seq, error_word, *, rows_per_candidate, out_dtype="f32",
+                            stats_out=None, layout="head_major"):
+    """Kernel-level wrapper of kx_attention_decode_shared (include/kosmosx_hip.h, "Scoring candidates over a shared prompt cache"):
+    ops.attention_decode_block's rows with C candidates of K = ``rows_per_candidate`` rows, candidate c reading cache sequence
+    cache_seq[c] and nobody appending.  qkv [C * K, 3 * H * 64] fp32 or bf16; kcache / vcache [Bc, H, Tmax, 64] ([Bc, Tmax, H, 64]
+    with ``layout`` "row_major", as ops.attention_decode) of the same dtype, left untouched; positions [C * K] and cache_seq [C] int32
+    on the device; error_word int32 [1] (sticky: KX_RAGGED_ERR_CACHE for a row outside the cache, off its candidate's base + j or
+    with a cache sequence outside [0, Bc)).  The bits of the block launch on a cache replicated per candidate.  Returns the output
+    rows [C * K, ...]."""
+    _need_cuda(qkv, kcache, vcache, positions, cache_seq, error_word, stats_out)
+    if layout not in ("head_major", "row_major"):
+        raise ValueError("attention_decode_shared: layout is 'head_major' or 'row_major'")
+    if layout == "row_major":
+        Bc, Tmax, Hh, hd = kcache.shape
+    else:
+        Bc, Hh, Tmax, hd = kcache.shape
+    K = int(rows_per_candidate)
+    if cache_seq.dtype != torch.int32 or cache_seq.dim() != 1 or not cache_seq.is_contiguous():
+        raise TypeError("attention_decode_shared: cache_seq must be a contiguous int32 [C] tensor")
+    M = cache_seq.shape[0] * K
+    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (M, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError("attention_decode_shared: qkv [C*K, 3*H*64], caches [Bc, H, Tmax, 64] ([Bc, Tmax, H, 64] row-major), contiguous")
+    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("attention_decode_shared: qkv and the caches share one dtype, fp32 or bf16")
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (M,) or not positions.is_contiguous():
+        raise TypeError(f"attention_decode_shared: positions must be a contiguous int32 [{M}] tensor")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError("attention_decode_shared: error_word is an int32 [1] tensor on the device (the kernel's sticky word)")
+    D = Hh * 64
+    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
+    if out_dtype == "f16c":
+        out = torch.zeros((M, 4 * D), dtype=torch.uint8, device=qkv.device)
+    else:
+        out = torch.zeros((M, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
+    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    H.check(H.load().kx_attention_decode_shared(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                                H.ptr(stats_out), M // K, K, Hh, positions.data_ptr(), cache_seq.data_ptr(), Bc, Tmax,
+                                                prec, error_word.data_ptr(), _stream()), "kx_attention_decode_shared")
+    return out
+
+
+def token_logprob(logits, target, *, row_index=None, vocab=None, out=None):
+    """Kernel-level wrapper of kx_token_logprob (include/kosmosx_hip.h, "Scoring candidates over a shared prompt cache"):
+    out[r] = log softmax(logits[row_index[r], :V])[target[r]] in one launch, no softmax written.  logits fp32 [rows_available, ld]
+    with unit column stride (a row pitch ld >= V; ``vocab`` = V, default the row's width); target int64 [R]; ``row_index`` int32 [R]
+    or None (row r).  A target outside [0, V) or a row index outside the buffer gives exactly 0.0.  Returns fp32 [R]."""
+    _need_cuda(logits, target, row_index, out)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("token_logprob: logits is an fp32 [rows, ld] tensor with unit column stride")
+    V = logits.shape[1] if vocab is None else int(vocab)
+    if target.dtype != torch.int64 or target.dim() != 1 or not target.is_contiguous():
+        raise TypeError("token_logprob: target is a contiguous int64 [R] tensor")
+    R = target.shape[0]
+    if row_index is None:
+        if R != logits.shape[0]:
+            raise ValueError(f"token_logprob: {R} targets for {logits.shape[0]} rows need a row_index")
+    elif row_index.dtype != torch.int32 or tuple(row_index.shape) != (R,) or not row_index.is_contiguous():
+        raise TypeError(f"token_logprob: row_index is a contiguous int32 [{R}] tensor")
+    if out is None:
+        out = torch.empty(R, dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (R,) or not out.is_contiguous():
+        raise TypeError(f"token_logprob: out is a contiguous fp32 [{R}] tensor")
+    H.check(H.load().kx_token_logprob(logits.data_ptr(), logits.shape[0], V, logits.stride(0), H.ptr(row_index), target.data_ptr(),
+                                      out.data_ptr(), R, _stream()), "kx_token_logprob")
+    return out
+
+
 def spec_accept(picked, *, fed=None, rows_per_sequence, positions, prefill_len=0, history, hist_len, out_tokens, n_out, finished,
                 next_tokens, max_new_tokens, step, ngram_max=2, eos_token_id=None, pad_token_id=1, out_src=None, emitted=None,
                 draft_from=None):
