@@ -1165,6 +1165,28 @@ template <> struct Ld4<float> {
   static __device__ __forceinline__ void unpack(const raw v, float (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
 };
 
+// One round of a slot's keys and values, j0 + 16u for u < UK, into kr / vr (slots past the end re-read the last key and drop it).
+// Key t is the new token's, read from the qkv row (knew / vnew) and not back through the cache.
+template <typename T, bool BLOCK>
+__device__ __forceinline__ void load_kv_round(typename Ld4<T>::raw (&kr)[Ld4<T>::UK], typename Ld4<T>::raw (&vr)[Ld4<T>::UK], const int j0,
+                                              const int t, const int t0, const char* knew, const char* vnew, const char* kc,
+                                              const char* vc, const long long qkv_row, const long long cache_row) {
+  typedef typename Ld4<T>::raw raw;
+  const long long es = sizeof(T);
+#pragma unroll
+  for (int u = 0; u < Ld4<T>::UK; ++u) {
+    const int j = min(j0 + 16 * u, t);
+    if constexpr (BLOCK) {                                 // keys t0 .. t: qkv row j - t0 of the sequence = (t - j) rows before this one
+      const long long back = (long long)(t - j) * qkv_row * es;
+      kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * cache_row * es);
+      vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * cache_row * es);
+    } else {
+      kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * cache_row * es);
+      vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * cache_row * es);
+    }
+  }
+}
+
 // One query per (head, sequence) against the cache.  At batch 1 this is 32 workgroups and pure latency, so the kernel is
 // ONE round trip: q, the first 256 (bf16) cached keys / values of the 16 slots and the new token's k / v — read from the
 // qkv row itself, not back through the cache — are all requested before anything is waited for; the cache append is a
@@ -1241,18 +1263,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   const int slot = wave * 4 + grp;
   const raw qr = *reinterpret_cast<const raw*>(qrow);
   raw kr[UK], vr[UK];
-#pragma unroll
-  for (int u = 0; u < UK; ++u) {                           // (slots past the end re-read the last key and drop it)
-    const int j = min(slot + 16 * u, t);
-    if constexpr (BLOCK) {                                 // keys t0 .. t: qkv row j - t0 of the sequence = (t - j) rows before this one
-      const long long back = (long long)(t - j) * p.qkv_row * es;
-      kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * p.cache_row * es);
-      vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * p.cache_row * es);
-    } else {
-      kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
-      vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
-    }
-  }
+  load_kv_round<T, BLOCK>(kr, vr, slot, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);
   if constexpr (!SHARED) {
     if (wave == 0 && grp < 2) {                            // append row t: 64 k + 64 v elements per head
       const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
@@ -1263,20 +1274,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   Ld4<T>::unpack(qr, q);
   float m = -INFINITY, l = 0.f, o[4] = {0.f, 0.f, 0.f, 0.f};
   for (int j0 = slot; j0 < nkeys; j0 += 16 * UK) {
-    if (j0 != slot) {                                      // contexts beyond the first round: one more round trip each
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const int j = min(j0 + 16 * u, t);
-        if constexpr (BLOCK) {
-          const long long back = (long long)(t - j) * p.qkv_row * es;
-          kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * p.cache_row * es);
-          vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * p.cache_row * es);
-        } else {
-          kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * p.cache_row * es);
-          vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * p.cache_row * es);
-        }
-      }
-    }
+    if (j0 != slot) load_kv_round<T, BLOCK>(kr, vr, j0, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);   // contexts beyond the first round: one more round trip each
 #pragma unroll
     for (int u = 0; u < UK; ++u) {
       if (j0 + 16 * u < nkeys) {
@@ -1372,6 +1370,20 @@ int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t
   return KX_OK;
 }
 
+// one decode launch on a cache of T: the form picks the pack and the grid (see attention_decode_impl)
+template <typename T>
+static void launch_decode(const DecodeParams& p, const RaggedParams& r, int64_t B, int64_t H, int64_t K, const int32_t* cache_seq,
+                          int64_t Bc, hipStream_t s) {
+  if (K > 0) {
+    const BlockParams bp{(int)K};
+    const dim3 gb((unsigned)H, (unsigned)K, (unsigned)(B / K));   // the workgroups of (H, B) with the row's (sequence, index) as coordinates
+    if (cache_seq) hipLaunchKernelGGL((attn_decode_kernel<T, RaggedParams, BlockParams, SharedParams>), gb, dim3(256), 0, s, p, r, bp,
+                                      SharedParams{cache_seq, (int)Bc});
+    else hipLaunchKernelGGL((attn_decode_kernel<T, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
+  } else if (r.positions) hipLaunchKernelGGL((attn_decode_kernel<T, RaggedParams>), dim3((unsigned)H, (unsigned)B), dim3(256), 0, s, p, r);
+  else hipLaunchKernelGGL(attn_decode_kernel<T>, dim3((unsigned)H, (unsigned)B), dim3(256), 0, s, p);
+}
+
 // positions == nullptr: the uniform launch at host position t; else the ragged launch (t unused).  K > 0: the block launch — B counts
 // the ROWS (sequences * K), the caches hold B / K sequences.  cache_seq != nullptr: the shared launch — B / K candidates, Bc sequences.
 static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, void* vcache, void* out, int32_t odt,
@@ -1400,23 +1412,8 @@ static int attention_decode_impl(const char* fn, const void* qkv, void* kcache, 
   const RaggedParams r{positions, err, (int)Tmax};
   hipStream_t s = (hipStream_t)stream;
   KxProfScope prof(prec == KX_PREC_BF16 ? KX_K_ATTN_BF16 : KX_K_ATTN_F32, B * H, 1, positions ? Tmax : t + 1, s);
-  const dim3 grid((unsigned)H, (unsigned)B);
-  if (K > 0) {
-    const BlockParams bp{(int)K};
-    const dim3 gb((unsigned)H, (unsigned)K, (unsigned)(B / K));   // the workgroups of (H, B) with the row's (sequence, index) as coordinates
-    if (cache_seq) {
-      const SharedParams sp{cache_seq, (int)Bc};
-      if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams, SharedParams>), gb, dim3(256), 0, s, p, r, bp, sp);
-      else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, BlockParams, SharedParams>), gb, dim3(256), 0, s, p, r, bp, sp);
-    } else if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
-    else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, BlockParams>), gb, dim3(256), 0, s, p, r, bp);
-  } else if (positions) {
-    if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams>), grid, dim3(256), 0, s, p, r);
-    else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams>), grid, dim3(256), 0, s, p, r);
-  } else {
-    if (prec == KX_PREC_BF16) hipLaunchKernelGGL(attn_decode_kernel<bf16_t>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(attn_decode_kernel<float>, grid, dim3(256), 0, s, p);
-  }
+  if (prec == KX_PREC_BF16) launch_decode<bf16_t>(p, r, B, H, K, cache_seq, Bc, s);
+  else launch_decode<float>(p, r, B, H, K, cache_seq, Bc, s);
   KX_CHECK_LAUNCH(fn);
   return KX_OK;
 }

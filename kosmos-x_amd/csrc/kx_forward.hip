@@ -283,9 +283,9 @@ int ln(const float* x, const float* pre, const float* g, const float* b, void* y
 // Binding guard (header, "Binding safety"): the caller's sizeof() of the weights struct and of its per-layer struct
 #define KX_CHECK_BINDING(w, WT, LT, fn)                                                                                   \
   KX_REQUIRE((w)->struct_bytes == sizeof(WT) && (w)->layer_bytes == sizeof(LT),                                           \
-             fn ": stale binding — caller declares " #WT " as %u bytes with %u-byte " #LT " elements, this library (ABI %d) " \
+             "%s: stale binding — caller declares " #WT " as %u bytes with %u-byte " #LT " elements, this library (ABI %d) " \
              "has %zu / %zu; regenerate the binding from include/kosmosx_hip.h",                                          \
-             (unsigned)(w)->struct_bytes, (unsigned)(w)->layer_bytes, KX_ABI_VERSION, sizeof(WT), sizeof(LT))
+             fn, (unsigned)(w)->struct_bytes, (unsigned)(w)->layer_bytes, KX_ABI_VERSION, sizeof(WT), sizeof(LT))
 template <class WT, class LT> static bool binding_ok(const WT* w) {
   return w && w->struct_bytes == sizeof(WT) && w->layer_bytes == sizeof(LT);
 }
@@ -687,18 +687,34 @@ extern "C" int kx_decoder_prefill(const kx_decoder_weights* w, float* x, int64_t
                               stream, kcache, vcache, Tmax);
 }
 
+// How the step's rows map to cache rows.
 // positions == nullptr: every sequence at host position t, xq_* / xk_* = row t of the tables (xpos_T = 1).  Else the ragged
 // step: sequence b at positions[b] (device), xq_* / xk_* = [B, 32] tables holding each sequence's row (xpos_T = B).
 // K > 0 (the block step): B counts the ROWS, K consecutive rows are one cache sequence (kx_attention_decode_block); the caches
 // hold B / K sequences.  Everything but the attention is row-wise and does not know.
 // cache_seq != nullptr (the score step): the B / K groups of K rows are candidates, group c reads cache sequence cache_seq[c] of the
 // Bc the caches hold and nothing is appended (kx_attention_decode_shared).
-static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const int32_t* positions,
-                            int32_t* error_word, const float* xq_cs, const float* xq_ss, const float* xk_cs,
-                            const float* xk_ss, void* kcache, void* vcache, int64_t Tmax, void* logits, int32_t ldt,
-                            void* workspace, size_t workspace_bytes, int32_t prec, void* stream, int64_t K = 0,
-                            const int32_t* cache_seq = nullptr, int64_t Bc = 0) {
-  const int64_t xT = positions ? B : 1;
+struct StepRows {
+  int64_t t; const int32_t* positions; int32_t* error_word; int64_t K; const int32_t* cache_seq; int64_t Bc;
+};
+
+// the step's attention over one layer's caches: the public entry point of the form `r` describes (B rows)
+static int step_attention(const StepRows& r, const void* qkv, void* kc, void* vc, void* out, int32_t odt, float* stats_out, int64_t B,
+                          int64_t H, int64_t Tmax, int32_t prec, void* stream) {
+  if (r.cache_seq)
+    return kx_attention_decode_shared(qkv, kc, vc, out, odt, stats_out, B / r.K, r.K, H, r.positions, r.cache_seq, r.Bc, Tmax, prec,
+                                      r.error_word, stream);
+  if (r.K > 0)
+    return kx_attention_decode_block(qkv, kc, vc, out, odt, stats_out, B / r.K, r.K, H, r.positions, Tmax, prec, r.error_word, stream);
+  if (r.positions) return kx_attention_decode_ragged(qkv, kc, vc, out, odt, stats_out, B, H, r.positions, Tmax, prec, r.error_word, stream);
+  return kx_attention_decode(qkv, kc, vc, out, odt, stats_out, B, H, r.t, Tmax, prec, stream);
+}
+
+static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* x, int64_t B, const StepRows& r, const float* xq_cs,
+                            const float* xq_ss, const float* xk_cs, const float* xk_ss, void* kcache, void* vcache, int64_t Tmax,
+                            void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec, void* stream) {
+  const int64_t t = r.t;
+  const int64_t xT = r.positions ? B : 1;
   const int tfmt = prec == KX_PREC_F32W24 ? 2 : prec == KX_PREC_F32W16 ? 3 : 1;   // what the streaming copies (w*_t) hold
   if (prec == KX_PREC_F32W24 || prec == KX_PREC_F32W16) prec = KX_PREC_F32;
   KX_REQUIRE(w && x && logits && workspace && kcache && vcache, "%s: null pointer", fn);
@@ -720,7 +736,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
   KX_SPLITK_SCOPE(d.splitk, s);
   const int ct = cdt(prec);
   const size_t es = esz(prec);
-  const size_t layer_bytes = (size_t)(cache_seq ? Bc : K > 0 ? B / K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
+  const size_t layer_bytes = (size_t)(r.cache_seq ? r.Bc : r.K > 0 ? B / r.K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
   // One token per sequence, up to 16 sequences: the step is 120 dependent launches of weight-streaming work, and launches
   // are what it costs (~6 us each) — tile 16 does each GEMM in one launch and takes the LayerNorm and
   // statistics-finalize kernels in as prologues: 5 launches per layer instead of 13.  bf16 operands, or fp32 operands on the
@@ -757,21 +773,8 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
       if (w->xpos) { q.xq_cs = xq_cs; q.xq_ss = xq_ss; q.xk_cs = xk_cs; q.xk_ss = xk_ss; q.xT = xT; q.xdim = D; }
       q.W_tiled = L.wqkv_t; q.tiled_fmt = tfmt; q.prec = prec;
       KX_TRY(gemv16(q, s));
-      if (cache_seq)
-        KX_TRY(kx_attention_decode_shared(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
-                                          pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B / K, K, w->heads, positions,
-                                          cache_seq, Bc, Tmax, prec, error_word, stream));
-      else if (K > 0)
-        KX_TRY(kx_attention_decode_block(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
-                                         pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, Tmax,
-                                         prec, error_word, stream));
-      else if (positions)
-        KX_TRY(kx_attention_decode_ragged(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att,
-                                          pieces ? KX_F16P : ct, w->subln ? d.partials : nullptr, B, w->heads, positions, Tmax, prec,
-                                          error_word, stream));
-      else
-        KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, pieces ? KX_F16P : ct,
-                                   w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
+      KX_TRY(step_attention(r, d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, pieces ? KX_F16P : ct,
+                            w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream));
       float *qa = pair ? d.ya : pa, *qb = pair ? d.yb : nullptr;   // what out_proj writes
       Gemv16 o{d.att, D, L.wo, D, qa, D, KX_F32, M, D};
       o.bias = L.bo; o.residual = pa; o.residual2 = pb; o.eps = w->eps;
@@ -804,19 +807,8 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     KX_FAM(0);
     KX_TRY(gemm(d.h, D, L.wqkv, D, d.qkv, 3 * D, qdt(prec), M, 3 * D, L.bqkv, nullptr, 0, 0.125f, D, prec, s,
                 w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? xT : 0, w->xpos ? D : 0));
-    if (cache_seq)
-      KX_TRY(kx_attention_decode_shared(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                                        w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, cache_seq, Bc, Tmax, prec,
-                                        error_word, stream));
-    else if (K > 0)
-      KX_TRY(kx_attention_decode_block(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                                       w->subln ? d.partials : nullptr, B / K, K, w->heads, positions, Tmax, prec, error_word, stream));
-    else if (positions)
-      KX_TRY(kx_attention_decode_ragged(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                                        w->subln ? d.partials : nullptr, B, w->heads, positions, Tmax, prec, error_word, stream));
-    else
-      KX_TRY(kx_attention_decode(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                                 w->subln ? d.partials : nullptr, B, w->heads, t, Tmax, prec, stream));
+    KX_TRY(step_attention(r, d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
+                          w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream));
     if (w->subln) {
       KX_TRY(kx_row_stats_finalize(d.partials, M, w->heads, 64, w->eps, d.stats, stream));
       KX_FAM(1);
@@ -852,8 +844,32 @@ extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int
                                       const float* xq_ss, const float* xk_cs, const float* xk_ss, void* kcache,
                                       void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
                                       size_t workspace_bytes, int32_t prec, void* stream) {
-  return decode_step_impl("kx_decoder_decode_step", w, x, B, t, nullptr, nullptr, xq_cs, xq_ss, xk_cs, xk_ss, kcache, vcache, Tmax, logits, ldt, workspace,
-                          workspace_bytes, prec, stream);
+  return decode_step_impl("kx_decoder_decode_step", w, x, B, StepRows{t, nullptr, nullptr, 0, nullptr, 0}, xq_cs, xq_ss, xk_cs, xk_ss,
+                          kcache, vcache, Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
+}
+
+// The device-position steps (B sequences, or B groups of r.K rows; M rows at r.positions): the checks they share, kx_step_prepare
+// and the step on the [M, 32] XPos rows that gathered.  own_ptrs: the entry point's further pointers are there; `range`: its own
+// range checks, run where each entry point always ran them — after the pointer checks, before any launch.
+template <class Range>
+static int device_step(const char* fn, bool own_ptrs, Range range, const kx_decoder_weights* w, const int64_t* tokens, const float* embed,
+                       const float* pos, int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t B, const StepRows& r,
+                       const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* xpos_rows, void* kcache,
+                       void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
+                       void* stream) {
+  KX_REQUIRE(w && r.positions && r.error_word && own_ptrs, "%s: null pointer", fn);
+  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, fn);
+  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
+             "%s: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing", fn);
+  KX_TRY(range());
+  const bool xp = w->xpos != 0;
+  const int64_t M = r.K > 0 ? B * r.K : B;
+  KX_TRY(kx_step_prepare(tokens, embed, pos, r.positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
+                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, M, w->dim, vocab, max_pos, pos_shift, Tmax,
+                         r.error_word, stream));
+  const float* xr = xp ? xpos_rows : nullptr;
+  return decode_step_impl(fn, w, x, M, r, xr, xr ? xr + M * 32 : nullptr, xr ? xr + 2 * M * 32 : nullptr, xr ? xr + 3 * M * 32 : nullptr,
+                          kcache, vcache, Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
 }
 
 extern "C" int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const int64_t* tokens, const float* embed,
@@ -862,18 +878,13 @@ extern "C" int kx_decoder_decode_step_ragged(const kx_decoder_weights* w, const 
                                              const float* xk_cs, const float* xk_ss, float* xpos_rows, void* kcache,
                                              void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
                                              size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
-  KX_REQUIRE(w && positions && error_word, "kx_decoder_decode_step_ragged: null pointer");
-  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_decode_step_ragged");
-  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
-             "kx_decoder_decode_step_ragged: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
-  KX_REQUIRE(B > 0 && Tmax > 0, "kx_decoder_decode_step_ragged: empty batch / cache");
-  const bool xp = w->xpos != 0;
-  KX_TRY(kx_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
-                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, B, w->dim, vocab, max_pos, pos_shift, Tmax,
-                         error_word, stream));
-  const float* r = xp ? xpos_rows : nullptr;
-  return decode_step_impl("kx_decoder_decode_step_ragged", w, x, B, 0, positions, error_word, r, r ? r + B * 32 : nullptr, r ? r + 2 * B * 32 : nullptr,
-                          r ? r + 3 * B * 32 : nullptr, kcache, vcache, Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
+  auto range = [&] {
+    KX_REQUIRE(B > 0 && Tmax > 0, "kx_decoder_decode_step_ragged: empty batch / cache");
+    return KX_OK;
+  };
+  return device_step("kx_decoder_decode_step_ragged", true, range, w, tokens, embed, pos, vocab, max_pos, pos_shift, x, B,
+                     StepRows{0, positions, error_word, 0, nullptr, 0}, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows, kcache, vcache, Tmax,
+                     logits, ldt, workspace, workspace_bytes, prec, stream);
 }
 
 extern "C" int kx_decoder_decode_step_block(const kx_decoder_weights* w, const int64_t* tokens, const float* embed,
@@ -882,21 +893,14 @@ extern "C" int kx_decoder_decode_step_block(const kx_decoder_weights* w, const i
                                             const float* xk_cs, const float* xk_ss, float* xpos_rows, void* kcache,
                                             void* vcache, int64_t Tmax, void* logits, int32_t ldt, void* workspace,
                                             size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
-  KX_REQUIRE(w && positions && error_word, "kx_decoder_decode_step_block: null pointer");
-  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_decode_step_block");
-  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
-             "kx_decoder_decode_step_block: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
-  KX_REQUIRE(K >= 2 && K <= 16, "kx_decoder_decode_step_block: K=%lld outside 2..16 rows per sequence", (long long)K);
-  KX_REQUIRE(B > 0 && B <= 65535 / K && Tmax > 0, "kx_decoder_decode_step_block: empty batch / cache");
-  const bool xp = w->xpos != 0;
-  const int64_t M = B * K;
-  KX_TRY(kx_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
-                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, M, w->dim, vocab, max_pos, pos_shift, Tmax,
-                         error_word, stream));
-  const float* r = xp ? xpos_rows : nullptr;
-  return decode_step_impl("kx_decoder_decode_step_block", w, x, M, 0, positions, error_word, r, r ? r + M * 32 : nullptr,
-                          r ? r + 2 * M * 32 : nullptr, r ? r + 3 * M * 32 : nullptr, kcache, vcache, Tmax, logits, ldt, workspace,
-                          workspace_bytes, prec, stream, K);
+  auto range = [&] {
+    KX_REQUIRE(K >= 2 && K <= 16, "kx_decoder_decode_step_block: K=%lld outside 2..16 rows per sequence", (long long)K);
+    KX_REQUIRE(B > 0 && B <= 65535 / K && Tmax > 0, "kx_decoder_decode_step_block: empty batch / cache");
+    return KX_OK;
+  };
+  return device_step("kx_decoder_decode_step_block", true, range, w, tokens, embed, pos, vocab, max_pos, pos_shift, x, B,
+                     StepRows{0, positions, error_word, K, nullptr, 0}, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows, kcache, vcache, Tmax,
+                     logits, ldt, workspace, workspace_bytes, prec, stream);
 }
 
 extern "C" int kx_decoder_score_step(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
@@ -905,20 +909,13 @@ extern "C" int kx_decoder_score_step(const kx_decoder_weights* w, const int64_t*
                                      const float* xq_ss, const float* xk_cs, const float* xk_ss, float* xpos_rows,
                                      const void* kcache, const void* vcache, int64_t Tmax, void* logits, int32_t ldt,
                                      void* workspace, size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
-  KX_REQUIRE(w && positions && cache_seq && error_word, "kx_decoder_score_step: null pointer");
-  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_score_step");
-  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
-             "kx_decoder_score_step: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
-  KX_REQUIRE(K >= 1 && K <= 16, "kx_decoder_score_step: K=%lld outside 1..16 rows per candidate", (long long)K);
-  KX_REQUIRE(C > 0 && C <= 65535 / K && Bc > 0 && Tmax > 0, "kx_decoder_score_step: empty batch / cache");
-  const bool xp = w->xpos != 0;
-  const int64_t M = C * K;
-  KX_TRY(kx_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
-                         xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, M, w->dim, vocab, max_pos, pos_shift, Tmax,
-                         error_word, stream));
-  const float* r = xp ? xpos_rows : nullptr;
+  auto range = [&] {
+    KX_REQUIRE(K >= 1 && K <= 16, "kx_decoder_score_step: K=%lld outside 1..16 rows per candidate", (long long)K);
+    KX_REQUIRE(C > 0 && C <= 65535 / K && Bc > 0 && Tmax > 0, "kx_decoder_score_step: empty batch / cache");
+    return KX_OK;
+  };
   // (the shared attention has no store to the caches)
-  return decode_step_impl("kx_decoder_score_step", w, x, M, 0, positions, error_word, r, r ? r + M * 32 : nullptr,
-                          r ? r + 2 * M * 32 : nullptr, r ? r + 3 * M * 32 : nullptr, const_cast<void*>(kcache),
-                          const_cast<void*>(vcache), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream, K, cache_seq, Bc);
+  return device_step("kx_decoder_score_step", cache_seq != nullptr, range, w, tokens, embed, pos, vocab, max_pos, pos_shift, x, C,
+                     StepRows{0, positions, error_word, K, cache_seq, Bc}, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows,
+                     const_cast<void*>(kcache), const_cast<void*>(vcache), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
 }

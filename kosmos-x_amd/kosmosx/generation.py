@@ -525,6 +525,81 @@ def score_loop(decoder, prec: str, state: dict, logits: torch.Tensor, continuati
     return out
 
 
+def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True):
+    """The prompt's prefill, under torch.no_grad(): ``prompt`` as run_generate takes it, ``new_rows`` (+ ``spare``) the positions the
+    caller will add, checked against the tables when ``budget``.  Returns the tokens as prefilled (trimmed to the longest prompt, the
+    padding masked), the host lengths (None: a uniform batch), T (prefix rows included), the state and the prefill's logits."""
+    tokens, lens = prompt["tokens"], None
+    if prompt_lengths is not None:
+        lens = resolve_prompt_lengths(prompt_lengths, tokens.shape[0], tokens.shape[1], min_len=prompt["min_len"])
+        tokens = tokens[:, :max(lens)]                                      # columns no row uses
+    T = tokens.shape[1] + prompt["prefix_rows"]
+    if budget:
+        check_budget(model.decoder, T, new_rows, spare=spare)
+    if lens is not None:
+        tokens = mask_padding(tokens.long(), lens)
+    # Ragged prompts go through the ordinary prefill, right-padded, with no padding mask and no new kernel: attention is
+    # causal, so a real position (< len_b) never has a padded key (>= len_b) among the keys it sees, and every other
+    # operation of the decoder works on a row alone.  The padded rows compute finite values (their ids are the row's first
+    # token, mask_padding) that nobody uses: the first token is drawn from logits[b, len_b - 1], and cache row
+    # len_b + g of sequence b is overwritten by the row's own g-th generated token in the very launch whose query is the
+    # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row);
+    # a score() candidate reads cache rows < len_b only.
+    passed_x = prompt["passed_x"](tokens)                                   # (the prompt's ids are range-checked here or in the prefill, once)
+    state = {"max_len": T + new_rows + spare}                               # (rejected drafts still occupy table and cache rows)
+    logits = model.decoder._forward_incremental(tokens if passed_x is None else None, state, passed_x, model.precision)
+    return tokens, lens, T, state, logits
+
+
+def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
+    """What Kosmos.generate and KosmosLanguage.generate share, ``kw`` being their keyword arguments by name.  ``prompt`` describes
+    the model's prompt: ``tokens`` (the [B, Tt] ids), ``check`` (a callable: the model's device and shape checks, run after the
+    argument checks), ``passed_x`` (a callable: the tokens as prefilled -> the [B, T, D] rows the prefill takes, or None for the
+    tokens alone), ``min_len`` (the shortest ragged prompt), ``prefix_rows`` (the rows passed_x adds to the tokens') and
+    ``pos_shift`` (as in generate_loop)."""
+    def pick(*names):
+        return {n: kw[n] for n in names}
+    decoder, prec, vocab, tokens = model.decoder, model.precision, model.embed.weight.shape[0], prompt["tokens"]
+    sampling = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
+    constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
+    beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
+        "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
+        "output_scores", "output_trace"))
+    check_constraint_args(vocab, num_beams=kw["num_beams"] if beams else None, **pick(*constraints, "eos_token_id"))
+    drafts = check_lookup_args(tokens.shape[0] if tokens.dim() else 0, draft_from=kw["_draft_from"], **pick(
+        "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
+        "sequence_ids", *constraints, "eos_poll"))
+    prompt["check"]()
+    with torch.no_grad():
+        tokens, lens, _, state, logits = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts)
+        common = dict(pos_shift=prompt["pos_shift"], **pick("eos_token_id", "pad_token_id", "eos_poll"))
+        if drafts:
+            return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
+                               ngram_max=kw["max_matching_ngram_size"], draft_from=kw["_draft_from"], **common,
+                               **pick("output_logits", "output_acceptance"))
+        if beams:
+            return beam_loop(decoder, prec, state, logits, max_new_tokens, **common, **pick(
+                "num_beams", "length_penalty", "early_stopping", "num_return_sequences", "output_scores", "output_trace",
+                "bad_words_ids", "min_new_tokens"))
+        return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
+                             lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
+                             **pick(*sampling, "seed", "sequence_ids", "output_logits", *constraints))
+
+
+def run_score(model, prompt: dict, continuations, kw: dict):
+    """What Kosmos.score and KosmosLanguage.score share: ``prompt`` as in run_generate, ``kw`` their keyword arguments by name."""
+    tokens = prompt["tokens"]
+    B = tokens.shape[0] if tokens.dim() else 0
+    clens, pidx = check_score_args(B, continuations, kw["continuation_lengths"], kw["prompt_index"])
+    prompt["check"](continuations=continuations)
+    L = continuations.shape[1]
+    with torch.no_grad():
+        _, lens, T, state, logits = _prefill(model, prompt, kw["prompt_lengths"], L - 1, budget=L > 1)
+        return score_loop(model.decoder, model.precision, state, logits, continuations, clens, pidx,
+                          [T] * B if lens is None else [prompt["prefix_rows"] + l for l in lens], pos_shift=prompt["pos_shift"],
+                          output_logits=kw["output_logits"])
+
+
 def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0):
     """IndexError before any launch when prompt + new tokens (+ ``spare`` rows: the drafts of a lookup step) overrun the position
     table / cache."""

@@ -133,6 +133,14 @@ def _default_precision() -> str:
     return p
 
 
+def _step_prec_id(w, sprec: str) -> int:
+    """The kx_precision of a decode step on pack ``w``: the compressed planes where the pack holds their streaming copies
+    (w24 / w16 without them — KOSMOSX_DECODE_TILED=0, more than 16 rows — is plain fp32 on the rounded operands)."""
+    if sprec in ("w24", "w16") and bool(w.wout_t):
+        return {"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec]
+    return H.PACK_PRECS[sprec]
+
+
 def _require_cuda(t: torch.Tensor, what: str):
     if not t.is_cuda:
         msg = (f"{what} is on {t.device}: the Kosmos-X MI355X path runs on HIP devices only "
@@ -895,12 +903,9 @@ class Decoder(_PackedMixin, nn.Module):
             w = self._pack(sprec)[0]
         if sprec in ("bf16", "fp32", "w24", "w16") and rows <= 16:
             self._pack_decode_tiles(sprec)                 # first decode step: the streaming copy of the weights
-        if score is not None:
-            return self._score_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, score[0], score[1], logits_out)
-        if block:
-            return self._block_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, block, logits_out)
         if positions is not None:
-            return self._ragged_step(state, w, sprec, emb, pos, next_token, positions, pos_shift)
+            return self._device_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, block if score is None else score[0],
+                                     None if score is None else score[1], logits_out)
         if passed_x is not None:
             _require_cuda(passed_x, "passed_x")
             x = passed_x[:, -1:].to(torch.float32).clone(memory_format=torch.contiguous_format)
@@ -919,9 +924,7 @@ class Decoder(_PackedMixin, nn.Module):
             raise ValueError("batch size changed between incremental steps")
         rows = tuple(None if tb is None else tb[t] for tb in state["xpos"])   # views: row t of each [Tmax, 32] table
         logits = torch.empty((B, 1, w.vocab), dtype=torch.float32, device=x.device)
-        # (w24 without streaming copies — KOSMOSX_DECODE_TILED=0, more than 16 sequences — is plain fp32 on the rounded operands)
-        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
-               else H.PACK_PRECS[sprec])
+        pid = _step_prec_id(w, sprec)
         need = lib.kx_decoder_workspace_bytes(C.byref(w), B, 1, pid)
         buf = self._ws.get(need, x.device)
         H.check(lib.kx_decoder_decode_step(C.byref(w), x.data_ptr(), B, t, *(H.ptr(r) for r in rows),
@@ -944,36 +947,17 @@ class Decoder(_PackedMixin, nn.Module):
             state["x_step"] = torch.zeros((B, 1, D), dtype=torch.float32, device=dev)
             state["xpos_rows"] = None if state["xpos"][0] is None else torch.zeros((4, B, 32), dtype=torch.float32, device=dev)
 
-    def _ragged_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift) -> torch.Tensor:
-        """One decode step with every row at its own device-resident position (see _forward_incremental)."""
+    def _device_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K=0, cache_seq=None, logits_out=None) -> torch.Tensor:
+        """One decode step with every row at its own device-resident position (see _forward_incremental).  K = 0: the ragged step,
+        one row per sequence.  K > 0: the block step, K rows per sequence at consecutive positions.  ``cache_seq`` [C]: the score
+        step, C candidates of K rows, candidate c on top of cache sequence cache_seq[c]; the caches are read only."""
         lib = H.load()
         _require_cuda(next_token, "next_token")
-        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
-        if next_token.shape[0] != B or positions.shape[0] != B:
-            raise ValueError("batch size changed between incremental steps")
-        dev = emb.device
-        self._ragged_scratch(state, dev)
-        logits = torch.empty((B, 1, w.vocab), dtype=torch.float32, device=dev)
-        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
-               else H.PACK_PRECS[sprec])
-        need = lib.kx_decoder_workspace_bytes(C.byref(w), B, 1, pid)
-        buf = self._ws.get(need, dev)
-        H.check(lib.kx_decoder_decode_step_ragged(
-            C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
-            state["x_step"].data_ptr(), B, positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
-            state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits.data_ptr(), H.KX_F32, buf.data_ptr(),
-            buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_ragged")
-        state["pos_max"] += 1
-        return logits
-
-    def _block_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K, logits_out=None) -> torch.Tensor:
-        """One decode step over K rows per sequence at consecutive device positions (see _forward_incremental)."""
-        lib = H.load()
-        _require_cuda(next_token, "next_token")
-        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
-        M = B * K
+        B, Tmax = state["batch"], state["max_len"]
+        M = (B if cache_seq is None else cache_seq.shape[0]) * max(K, 1)
         if next_token.shape[0] != M or positions.shape[0] != M:
-            raise ValueError("batch size changed between incremental steps")
+            raise ValueError("batch size changed between incremental steps" if cache_seq is None else
+                             "the score step's tokens and positions are [candidates * rows per candidate]")
         dev = emb.device
         self._ragged_scratch(state, dev, rows=M)
         if logits_out is None:
@@ -981,43 +965,22 @@ class Decoder(_PackedMixin, nn.Module):
         elif (tuple(logits_out.shape) != (M, w.vocab) or logits_out.dtype != torch.float32 or not logits_out.is_contiguous()
               or logits_out.device != dev):
             raise ValueError(f"logits_out must be a contiguous fp32 [{M}, {w.vocab}] tensor on the model's device")
-        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
-               else H.PACK_PRECS[sprec])
+        pid = _step_prec_id(w, sprec)
         need = lib.kx_decoder_workspace_bytes(C.byref(w), M, 1, pid)
         buf = self._ws.get(need, dev)
-        H.check(lib.kx_decoder_decode_step_block(
+        if cache_seq is not None:
+            fn, rows = "kx_decoder_score_step", (M // K, K, positions.data_ptr(), cache_seq.data_ptr(), B)
+        elif K:
+            fn, rows = "kx_decoder_decode_step_block", (B, K, positions.data_ptr())
+        else:
+            fn, rows = "kx_decoder_decode_step_ragged", (B, positions.data_ptr())
+        H.check(getattr(lib, fn)(
             C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
-            state["x_step"].data_ptr(), B, K, positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
+            state["x_step"].data_ptr(), *rows, *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
             state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(),
-            buf.numel(), pid, state["error"].data_ptr(), _stream()), "kx_decoder_decode_step_block")
-        return logits_out.view(M, 1, w.vocab)
-
-    def _score_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K, cache_seq, logits_out=None) -> torch.Tensor:
-        """One step over C candidates of K rows at consecutive device positions, candidate c on top of cache sequence cache_seq[c];
-        the caches are read only (see _forward_incremental)."""
-        lib = H.load()
-        _require_cuda(next_token, "next_token")
-        B, Tmax, D = state["batch"], state["max_len"], self.args.decoder_embed_dim
-        M = cache_seq.shape[0] * K
-        if next_token.shape[0] != M or positions.shape[0] != M:
-            raise ValueError("the score step's tokens and positions are [candidates * rows per candidate]")
-        dev = emb.device
-        self._ragged_scratch(state, dev, rows=M)
-        if logits_out is None:
-            logits_out = torch.empty((M, w.vocab), dtype=torch.float32, device=dev)
-        elif (tuple(logits_out.shape) != (M, w.vocab) or logits_out.dtype != torch.float32 or not logits_out.is_contiguous()
-              or logits_out.device != dev):
-            raise ValueError(f"logits_out must be a contiguous fp32 [{M}, {w.vocab}] tensor on the model's device")
-        pid = ({"w24": H.KX_PREC_F32W24, "w16": H.KX_PREC_F32W16}[sprec] if (sprec in ("w24", "w16") and bool(w.wout_t))
-               else H.PACK_PRECS[sprec])
-        need = lib.kx_decoder_workspace_bytes(C.byref(w), M, 1, pid)
-        buf = self._ws.get(need, dev)
-        H.check(lib.kx_decoder_score_step(
-            C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
-            state["x_step"].data_ptr(), M // K, K, positions.data_ptr(), cache_seq.data_ptr(), B,
-            *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]), state["kcache"].data_ptr(), state["vcache"].data_ptr(),
-            Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(), buf.numel(), pid, state["error"].data_ptr(), _stream()),
-            "kx_decoder_score_step")
+            buf.numel(), pid, state["error"].data_ptr(), _stream()), fn)
+        if not K:
+            state["pos_max"] += 1
         return logits_out.view(M, 1, w.vocab)
 
     # -- torchscale-compatible surface ------------------------------------------------------------
@@ -1282,64 +1245,14 @@ class Kosmos(nn.Module):
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
-        beams = generation.check_beam_args(
-            self.embed.weight.shape[0], num_beams=num_beams, length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-            prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
-            output_trace=output_trace, beam_path=_beam_path)
-        generation.check_constraint_args(
-            self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
-            num_beams=num_beams if beams else None)
-        drafts = generation.check_lookup_args(
-            text_tokens.shape[0] if text_tokens.dim() else 0, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, draft_from=_draft_from,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-            num_beams=num_beams, prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, no_repeat_ngram_size=no_repeat_ngram_size,
-            bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_poll=eos_poll)
-        _warn_train_mode(self)
-        _require_cuda(text_tokens, "text_tokens")
-        _require_cuda(images, "images")
-        if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
-            raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
-        n_img = self.cfg.perceiver.latents
-        lens = None
-        if prompt_lengths is not None:
-            lens = generation.resolve_prompt_lengths(prompt_lengths, text_tokens.shape[0], text_tokens.shape[1], min_len=2)
-            text_tokens = text_tokens[:, :max(lens)]                         # columns no row uses
-        T = text_tokens.shape[1] + n_img
-        generation.check_budget(self.decoder, T, max_new_tokens, spare=drafts)
-        prec = self.precision
-        with torch.no_grad():
-            if lens is not None:
-                text_tokens = generation.mask_padding(text_tokens.long(), lens)
-            img = self.clip_model.run(images, prec, self._ws)
-            img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
-            x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
-            state = {"max_len": T + max_new_tokens + drafts}                # (rejected drafts still occupy table and cache rows)
-            # (ragged: the right-padded prefill needs no mask — the argument is spelled out in KosmosLanguage.generate)
-            logits = self.decoder._forward_incremental(None, state, x, prec)
-            if drafts:
-                return generation.lookup_loop(
-                    self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens, num_drafts=drafts,
-                    ngram_max=max_matching_ngram_size, pos_shift=n_img if self.switches.u1_inplace_alias else 0,
-                    eos_token_id=eos_token_id, pad_token_id=pad_token_id, eos_poll=eos_poll, output_logits=output_logits,
-                    output_acceptance=output_acceptance, draft_from=_draft_from)
-            if beams:
-                return generation.beam_loop(
-                    self.decoder, prec, state, logits, max_new_tokens, num_beams=num_beams,
-                    pos_shift=n_img if self.switches.u1_inplace_alias else 0, length_penalty=length_penalty,
-                    early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
-                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace,
-                    bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens)
-            return generation.generate_loop(
-                self.decoder, prec, state, logits, text_tokens.long(), max_new_tokens,
-                pos_shift=n_img if self.switches.u1_inplace_alias else 0, do_sample=do_sample, temperature=temperature,
-                top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed, eos_token_id=eos_token_id,
-                pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll, output_logits=output_logits,
-                lengths=None if lens is None else [n_img + l for l in lens], text_lengths=lens,
-                no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
-                stop_sequences=stop_sequences)
+        return generation.run_generate(self, self._prompt(text_tokens, images), max_new_tokens, dict(
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
+            eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
+            output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
+            early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
+            output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False):
@@ -1358,36 +1271,28 @@ class Kosmos(nn.Module):
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
-        B = text_tokens.shape[0] if text_tokens.dim() else 0
-        clens, pidx = generation.check_score_args(B, continuations, continuation_lengths, prompt_index)
-        _warn_train_mode(self)
-        _require_cuda(text_tokens, "text_tokens")
-        _require_cuda(images, "images")
-        _require_cuda(continuations, "continuations")
-        if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
-            raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
+        return generation.run_score(self, self._prompt(text_tokens, images), continuations, dict(
+            continuation_lengths=continuation_lengths, prompt_index=prompt_index, prompt_lengths=prompt_lengths,
+            output_logits=output_logits))
+
+    def _prompt(self, text_tokens, images) -> dict:
+        """The multimodal prompt as generation.run_generate / run_score take it: tower -> resampler -> splice, as in forward()."""
         n_img = self.cfg.perceiver.latents
-        lens = None
-        if prompt_lengths is not None:
-            lens = generation.resolve_prompt_lengths(prompt_lengths, text_tokens.shape[0], text_tokens.shape[1], min_len=2)
-            text_tokens = text_tokens[:, :max(lens)]                         # columns no row uses
-        T = text_tokens.shape[1] + n_img
-        L = continuations.shape[1]
-        if L > 1:
-            generation.check_budget(self.decoder, T, L - 1)
-        prec = self.precision
-        with torch.no_grad():
-            if lens is not None:
-                text_tokens = generation.mask_padding(text_tokens.long(), lens)
-            img = self.clip_model.run(images, prec, self._ws)
-            img, _ = self.perceive.run(img, prec, self._ws, self.image_proj.weight)
-            x = self.decoder.embed(text_tokens, prec, img=img)              # the prompt's ids are range-checked here, once
-            state = {"max_len": T + L - 1}
-            logits = self.decoder._forward_incremental(None, state, x, prec)
-            return generation.score_loop(
-                self.decoder, prec, state, logits, continuations, clens, pidx,
-                [T] * B if lens is None else [n_img + l for l in lens],
-                pos_shift=n_img if self.switches.u1_inplace_alias else 0, output_logits=output_logits)
+
+        def check(**more):
+            _warn_train_mode(self)
+            for name, t in dict(text_tokens=text_tokens, images=images, **more).items():
+                _require_cuda(t, name)
+            if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
+                raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
+
+        def passed_x(tokens):
+            img = self.clip_model.run(images, self.precision, self._ws)
+            img, _ = self.perceive.run(img, self.precision, self._ws, self.image_proj.weight)
+            return self.decoder.embed(tokens, self.precision, img=img)      # the prompt's ids are range-checked here, once
+
+        return dict(tokens=text_tokens, check=check, passed_x=passed_x, min_len=2, prefix_rows=n_img,   # (the image is spliced after two tokens)
+                    pos_shift=n_img if self.switches.u1_inplace_alias else 0)
 
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
@@ -1496,59 +1401,14 @@ class KosmosLanguage(nn.Module):
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
-        beams = generation.check_beam_args(
-            self.embed.weight.shape[0], num_beams=num_beams, length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-            prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, output_logits=output_logits, output_scores=output_scores,
-            output_trace=output_trace, beam_path=_beam_path)
-        generation.check_constraint_args(
-            self.embed.weight.shape[0], no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id,
-            num_beams=num_beams if beams else None)
-        drafts = generation.check_lookup_args(
-            x.shape[0] if x.dim() else 0, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, draft_from=_draft_from,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-            num_beams=num_beams, prompt_lengths=prompt_lengths, sequence_ids=sequence_ids, no_repeat_ngram_size=no_repeat_ngram_size,
-            bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_poll=eos_poll)
-        _warn_train_mode(self)
-        _require_cuda(x, "x")
-        if x.dim() != 2:
-            raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
-        lens = None
-        if prompt_lengths is not None:
-            lens = generation.resolve_prompt_lengths(prompt_lengths, x.shape[0], x.shape[1], min_len=1)
-            x = x[:, :max(lens)]                                             # columns no row uses
-        T = x.shape[1]
-        generation.check_budget(self.decoder, T, max_new_tokens, spare=drafts)
-        with torch.no_grad():
-            if lens is not None:
-                x = generation.mask_padding(x.long(), lens)
-            state = {"max_len": T + max_new_tokens + drafts}                # (rejected drafts still occupy table and cache rows)
-            # Ragged prompts go through the ordinary prefill, right-padded, with no padding mask and no new kernel: attention is
-            # causal, so a real position (< len_b) never has a padded key (>= len_b) among the keys it sees, and every other
-            # operation of the decoder works on a row alone.  The padded rows compute finite values (their ids are the row's first
-            # token, mask_padding) that nobody uses: the first token is drawn from logits[b, len_b - 1], and cache row
-            # len_b + g of sequence b is overwritten by the row's own g-th generated token in the very launch whose query is the
-            # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row).
-            logits = self.decoder._forward_incremental(x, state, None, self.precision)
-            if drafts:
-                return generation.lookup_loop(
-                    self.decoder, self.precision, state, logits, x.long(), max_new_tokens, num_drafts=drafts,
-                    ngram_max=max_matching_ngram_size, eos_token_id=eos_token_id, pad_token_id=pad_token_id, eos_poll=eos_poll,
-                    output_logits=output_logits, output_acceptance=output_acceptance, draft_from=_draft_from)
-            if beams:
-                return generation.beam_loop(
-                    self.decoder, self.precision, state, logits, max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
-                    early_stopping=early_stopping, num_return_sequences=num_return_sequences, eos_token_id=eos_token_id,
-                    pad_token_id=pad_token_id, eos_poll=eos_poll, output_scores=output_scores, output_trace=output_trace,
-                    bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens)
-            return generation.generate_loop(
-                self.decoder, self.precision, state, logits, x.long(), max_new_tokens, do_sample=do_sample,
-                temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
-                eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-                output_logits=output_logits, lengths=lens, no_repeat_ngram_size=no_repeat_ngram_size,
-                bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, stop_sequences=stop_sequences)
+        return generation.run_generate(self, self._prompt(x), max_new_tokens, dict(
+            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
+            eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
+            output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
+            early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
+            output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False):
@@ -1567,29 +1427,20 @@ class KosmosLanguage(nn.Module):
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
-        B = x.shape[0] if x.dim() else 0
-        clens, pidx = generation.check_score_args(B, continuations, continuation_lengths, prompt_index)
-        _warn_train_mode(self)
-        _require_cuda(x, "x")
-        _require_cuda(continuations, "continuations")
-        if x.dim() != 2:
-            raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
-        lens = None
-        if prompt_lengths is not None:
-            lens = generation.resolve_prompt_lengths(prompt_lengths, x.shape[0], x.shape[1], min_len=1)
-            x = x[:, :max(lens)]                                             # columns no row uses
-        T = x.shape[1]
-        L = continuations.shape[1]
-        if L > 1:
-            generation.check_budget(self.decoder, T, L - 1)
-        with torch.no_grad():
-            if lens is not None:
-                x = generation.mask_padding(x.long(), lens)
-            state = {"max_len": T + L - 1}
-            # (ragged prompts: the right-padded prefill needs no mask, see generate(); a candidate reads cache rows < len_b only)
-            logits = self.decoder._forward_incremental(x, state, None, self.precision)
-            return generation.score_loop(self.decoder, self.precision, state, logits, continuations, clens, pidx,
-                                         [T] * B if lens is None else lens, output_logits=output_logits)
+        return generation.run_score(self, self._prompt(x), continuations, dict(
+            continuation_lengths=continuation_lengths, prompt_index=prompt_index, prompt_lengths=prompt_lengths,
+            output_logits=output_logits))
+
+    def _prompt(self, x) -> dict:
+        """The text prompt as generation.run_generate / run_score take it."""
+        def check(**more):
+            _warn_train_mode(self)
+            for name, t in dict(x=x, **more).items():
+                _require_cuda(t, name)
+            if x.dim() != 2:
+                raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
+
+        return dict(tokens=x, check=check, passed_x=lambda tokens: None, min_len=1, prefix_rows=0, pos_shift=0)
 
 
 class KosmosTokenizer:

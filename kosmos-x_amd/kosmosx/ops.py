@@ -527,6 +527,40 @@ def step_prepare(tokens, embed, pos, positions, tables=None, pos_shift=0, error_
     return out, (xpos_rows if tables is not None else None), error_word
 
 
+def _decode_attention_args(fn, qkv, kcache, vcache, layout, out_dtype, positions, error_word, K=None, cache_seq=None):
+    """What the three decode-attention wrappers share: the caches' layout, the shape / dtype checks (``fn`` names the wrapper in
+    every message), the output rows and the kernel's precision.  K None: one row per cache sequence; else K rows per sequence, or
+    per candidate of ``cache_seq``.  Returns (cache sequences, H, Tmax, rows, odt, out, prec)."""
+    if layout not in ("head_major", "row_major"):
+        raise ValueError(f"{fn}: layout is 'head_major' or 'row_major'")
+    if layout == "row_major":
+        B, Tmax, Hh, hd = kcache.shape
+    else:
+        B, Hh, Tmax, hd = kcache.shape
+    if cache_seq is not None and (cache_seq.dtype != torch.int32 or cache_seq.dim() != 1 or not cache_seq.is_contiguous()):
+        raise TypeError(f"{fn}: cache_seq must be a contiguous int32 [C] tensor")
+    M = B if K is None else (B if cache_seq is None else cache_seq.shape[0]) * K
+    rows, seqs = ("B" if K is None else "B*K", "B") if cache_seq is None else ("C*K", "Bc")
+    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (M, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"{fn}: qkv [{rows}, 3*H*64], caches [{seqs}, H, Tmax, 64] ([{seqs}, Tmax, H, 64] row-major), contiguous")
+    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{fn}: qkv and the caches share one dtype, fp32 or bf16")
+    if positions is not None:
+        if positions.dtype != torch.int32 or tuple(positions.shape) != (M,) or not positions.is_contiguous():
+            raise TypeError(f"{fn}: positions must be a contiguous int32 [{M}] tensor")
+        if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+            raise TypeError(f"{fn}: {'positions need error_word, an' if K is None else 'error_word is an'} int32 [1] tensor on the "
+                            "device (the kernel's sticky word)")
+    D = Hh * 64
+    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
+    if out_dtype == "f16c":
+        out = torch.zeros((M, 4 * D), dtype=torch.uint8, device=qkv.device)
+    else:
+        out = torch.zeros((M, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
+    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    return B, Hh, Tmax, M, odt, out, prec
+
+
 def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=None, out_dtype="f32", stats_out=None,
                      layout="head_major"):
     """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
@@ -538,23 +572,7 @@ def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=
     ``layout`` "row_major": the caches are [B, Tmax, H, 64], the layout the library reads under tuning key 9 = 1.  The argument
     only names the shape that is checked; the caller sets the key (kx_set_tuning(9, 1)) around the call."""
     _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out)
-    if layout not in ("head_major", "row_major"):
-        raise ValueError("attention_decode: layout is 'head_major' or 'row_major'")
-    if layout == "row_major":
-        B, Tmax, Hh, hd = kcache.shape
-    else:
-        B, Hh, Tmax, hd = kcache.shape
-    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (B, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
-        raise ValueError("attention_decode: qkv [B, 3*H*64], caches [B, H, Tmax, 64] ([B, Tmax, H, 64] row-major), contiguous")
-    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("attention_decode: qkv and the caches share one dtype, fp32 or bf16")
-    D = Hh * 64
-    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
-    if out_dtype == "f16c":
-        out = torch.zeros((B, 4 * D), dtype=torch.uint8, device=qkv.device)
-    else:
-        out = torch.zeros((B, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
-    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    B, Hh, Tmax, _, odt, out, prec = _decode_attention_args("attention_decode", qkv, kcache, vcache, layout, out_dtype, positions, error_word)
     lib = H.load()
     if positions is None:
         if t is None:
@@ -562,10 +580,6 @@ def attention_decode(qkv, kcache, vcache, t=None, *, positions=None, error_word=
         H.check(lib.kx_attention_decode(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
                                         H.ptr(stats_out), B, Hh, int(t), Tmax, prec, _stream()), "kx_attention_decode")
         return out
-    if positions.dtype != torch.int32 or tuple(positions.shape) != (B,) or not positions.is_contiguous():
-        raise TypeError(f"attention_decode: positions must be a contiguous int32 [{B}] tensor")
-    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
-        raise TypeError("attention_decode: positions need error_word, an int32 [1] tensor on the device (the kernel's sticky word)")
     H.check(lib.kx_attention_decode_ragged(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
                                            H.ptr(stats_out), B, Hh, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
                                            _stream()), "kx_attention_decode_ragged")
@@ -581,29 +595,9 @@ def attention_decode_block(qkv, kcache, vcache, positions, error_word, *, rows_p
     error_word int32 [1] (sticky: KX_RAGGED_ERR_CACHE for a row outside the cache or off its sequence's base + j).
     One launch = K successive ops.attention_decode(positions=...) launches, bit for bit.  Returns the output rows [B * K, ...]."""
     _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out)
-    if layout not in ("head_major", "row_major"):
-        raise ValueError("attention_decode_block: layout is 'head_major' or 'row_major'")
-    if layout == "row_major":
-        B, Tmax, Hh, hd = kcache.shape
-    else:
-        B, Hh, Tmax, hd = kcache.shape
     K = int(rows_per_sequence)
-    M = B * K
-    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (M, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
-        raise ValueError("attention_decode_block: qkv [B*K, 3*H*64], caches [B, H, Tmax, 64] ([B, Tmax, H, 64] row-major), contiguous")
-    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("attention_decode_block: qkv and the caches share one dtype, fp32 or bf16")
-    if positions.dtype != torch.int32 or tuple(positions.shape) != (M,) or not positions.is_contiguous():
-        raise TypeError(f"attention_decode_block: positions must be a contiguous int32 [{M}] tensor")
-    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
-        raise TypeError("attention_decode_block: error_word is an int32 [1] tensor on the device (the kernel's sticky word)")
-    D = Hh * 64
-    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
-    if out_dtype == "f16c":
-        out = torch.zeros((M, 4 * D), dtype=torch.uint8, device=qkv.device)
-    else:
-        out = torch.zeros((M, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
-    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    B, Hh, Tmax, _, odt, out, prec = _decode_attention_args("attention_decode_block", qkv, kcache, vcache, layout, out_dtype, positions,
+                                                            error_word, K)
     H.check(H.load().kx_attention_decode_block(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
                                                H.ptr(stats_out), B, K, Hh, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
                                                _stream()), "kx_attention_decode_block")
@@ -620,31 +614,9 @@ def attention_decode_shared(qkv, kcache, vcache, positions, cache_seq, error_wor
     with a cache sequence outside [0, Bc)).  The bits of the block launch on a cache replicated per candidate.  Returns the output
     rows [C * K, ...]."""
     _need_cuda(qkv, kcache, vcache, positions, cache_seq, error_word, stats_out)
-    if layout not in ("head_major", "row_major"):
-        raise ValueError("attention_decode_shared: layout is 'head_major' or 'row_major'")
-    if layout == "row_major":
-        Bc, Tmax, Hh, hd = kcache.shape
-    else:
-        Bc, Hh, Tmax, hd = kcache.shape
     K = int(rows_per_candidate)
-    if cache_seq.dtype != torch.int32 or cache_seq.dim() != 1 or not cache_seq.is_contiguous():
-        raise TypeError("attention_decode_shared: cache_seq must be a contiguous int32 [C] tensor")
-    M = cache_seq.shape[0] * K
-    if hd != 64 or vcache.shape != kcache.shape or tuple(qkv.shape) != (M, 3 * Hh * 64) or not (qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()):
-        raise ValueError("attention_decode_shared: qkv [C*K, 3*H*64], caches [Bc, H, Tmax, 64] ([Bc, Tmax, H, 64] row-major), contiguous")
-    if qkv.dtype != kcache.dtype or kcache.dtype != vcache.dtype or qkv.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("attention_decode_shared: qkv and the caches share one dtype, fp32 or bf16")
-    if positions.dtype != torch.int32 or tuple(positions.shape) != (M,) or not positions.is_contiguous():
-        raise TypeError(f"attention_decode_shared: positions must be a contiguous int32 [{M}] tensor")
-    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
-        raise TypeError("attention_decode_shared: error_word is an int32 [1] tensor on the device (the kernel's sticky word)")
-    D = Hh * 64
-    odt = {"f32": H.KX_F32, "bf16": H.KX_BF16, "f16c": H.KX_F16C, "f16p": H.KX_F16P}[out_dtype]
-    if out_dtype == "f16c":
-        out = torch.zeros((M, 4 * D), dtype=torch.uint8, device=qkv.device)
-    else:
-        out = torch.zeros((M, D), dtype=torch.bfloat16 if out_dtype == "bf16" else torch.float32, device=qkv.device)
-    prec = H.KX_PREC_BF16 if qkv.dtype == torch.bfloat16 else (H.KX_PREC_F16C if out_dtype == "f16c" else H.KX_PREC_F32)
+    Bc, Hh, Tmax, M, odt, out, prec = _decode_attention_args("attention_decode_shared", qkv, kcache, vcache, layout, out_dtype, positions,
+                                                             error_word, K, cache_seq)
     H.check(H.load().kx_attention_decode_shared(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
                                                 H.ptr(stats_out), M // K, K, Hh, positions.data_ptr(), cache_seq.data_ptr(), Bc, Tmax,
                                                 prec, error_word.data_ptr(), _stream()), "kx_attention_decode_shared")

@@ -112,8 +112,8 @@ def test_one_token_continuations_launch_no_step(monkeypatch):
     lm = lm0.to("cuda")
     lm.precision = "fp32"
     calls = []
-    real = Decoder._score_step
-    monkeypatch.setattr(Decoder, "_score_step", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
+    real = Decoder._device_step
+    monkeypatch.setattr(Decoder, "_device_step", lambda self, *a, **k: (calls.append(1), real(self, *a, **k))[1])
     g = torch.Generator().manual_seed(8)
     tok = torch.randint(0, 502, (2, 9), generator=g)
     cont = torch.randint(0, 502, (6, 1), generator=g)
