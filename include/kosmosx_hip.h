@@ -837,6 +837,40 @@ int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int
                      const int64_t* target, float* out, int64_t rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Chunked prefill: append MANY rows to filled caches in one pass over the forward's tile GEMMs and flash attention (added
+ * within ABI 7: functions only).  P is a host scalar, the number of rows every sequence already has in the caches; P = 0 is allowed.
+ *
+ * kx_attention_extend: qkv [B * Tn, 3 * H * 64], row b * Tn + i = sequence b's i-th new token, q pre-scaled and XPos-rotated
+ *   and k rotated as the qkv GEMM's epilogue writes them.  Cache dtype and layout as kx_attention_decode: bf16 for KX_PREC_BF16,
+ *   fp32 for KX_PREC_F32 and KX_PREC_F16C; per sequence [H][Tmax][64], or [Tmax][H * 64] under tuning key 9 = 1.
+ *   Appends the rows' k and v to cache rows P .. P + Tn - 1 (a launch of its own), then query i attends cache rows 0 .. P + i
+ *   — the causal mask with its diagonal shifted by P — reading keys from the caches only: rows at and after P + Tn are never
+ *   read, whatever they hold.  nan_to_num as kx_attention applies it to causal launches (the fp32 kernel: every score; the
+ *   16-bit kernels: not reachable, plain bf16 the documented divergence).  out [B * Tn, H * 64] as kx_attention writes it for the
+ *   precision: fp32, or bf16 (KX_PREC_BF16, KX_PREC_F32) / KX_F16C rows (KX_PREC_F16C); stats_out [B * Tn, H, 2] optional, as
+ *   kx_attn_args.stats_out.  Per query the key tiles, their order and every sum are those of kx_attention's causal launch over the
+ *   P + Tn rows: rows P .. P + Tn - 1 of that launch, bit for bit with KX_PREC_F32 and KX_PREC_F16C.  KX_PREC_BF16 may differ in the
+ *   last bit: that kernel's rescale factor for an unchanged running maximum is exp2 of a rounding residue (1 +- 1 ulp), applied
+ *   once more to a query whose wave still has work in a tile the query itself has none in — and which queries share a wave
+ *   depends on P.
+ *   KX_ERR_INVALID_ARG and nothing launched: null pointers, Tn < 1, P < 0, P + Tn > Tmax, a precision or output form outside the
+ *   above, pointers not 16-byte aligned, KX_PREC_F32 under tuning key 2 = 1 (the first-version kernel has no cache form).
+ *   The launch has H x ceil(ceil(Tn / 128) / 2) x B workgroups (KX_PREC_F32: ceil(Tn / 64) x H x B), each walking the whole key
+ *   stream below its diagonal: with P much larger than Tn that is few workgroups on long streams; there is no split over keys.
+ * kx_decoder_extend: kx_decoder_prefill with the T rows at positions P .. P + T - 1 of caches that hold P rows.  xq_*, xk_*
+ *   are the FULL [Tmax, 32] tables of the caches' one centring (as the ragged step takes them); the qkv GEMM reads them from row
+ *   P.  x [B, T, dim] fp32 (consumed).  P = 0 is kx_decoder_prefill, launch for launch.  logits [B, T, vocab], or NULL: the call then
+ *   ends after the last layer — no decoder.layer_norm, no output projection — and only the caches were its purpose.
+ *   Workspace: kx_decoder_workspace_bytes(w, B, T, prec).  Precisions: those of the prefill with a cache (bf16, fp32, f16c).
+ * ------------------------------------------------------------------------------------------ */
+int kx_attention_extend(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                        int64_t B, int64_t H, int64_t Tn, int64_t P, int64_t Tmax, int32_t prec, void* stream);
+int kx_decoder_extend(const kx_decoder_weights* w, float* x, int64_t B, int64_t T, int64_t P,
+                      const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss,
+                      void* logits, int32_t ldt, void* kcache, void* vcache, int64_t Tmax,
+                      void* workspace, size_t workspace_bytes, int32_t prec, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before
  * Kosmos.forward, on the device.  Integer / byte work; results are bit-identical to the HF processor.
  * ------------------------------------------------------------------------------------------ */

@@ -40,7 +40,22 @@ struct AttnParams {
   float* lse_out;     // [B, H, Tq] log-sum-exp of the scores (fp32 matrix-core kernel; for the backward pass), or null
   float drop_inv_keep; unsigned drop_thresh; unsigned long long drop_seed; unsigned drop_site;   // attention dropout (training)
   int interleave;     // causal split-fp16 launches: a wave's two 16-query blocks sit 64 rows apart (attn_f16s_kernel, IL); tuning key 2 = 8: off
+  // the EXT instantiations only (kx_attention_extend; appended, so the other kernels' argument offsets stay): k / v are a KV cache
+  // whose head h starts khs elements after the sequence's base (the others: h * 64), and query i is the sequence's row P + i
+  long long khs; int P;
 };
+
+// EXT (kx_attention_extend): the causal kernels over a KV cache that already holds P rows.  Tq new queries, Tk = P + Tq keys read
+// from the cache (head stride p.khs); query i sits at sequence position P + i, so P enters the causal tile count, the per-wave /
+// per-block "tile has work" tests and the mask compare.  Without EXT both fold to h * 64 and 0: the same instructions as before.
+template <bool EXT> __device__ __forceinline__ long long kv_head_off(const AttnParams& p, int h) {
+  if constexpr (EXT) return (long long)h * p.khs;
+  else return (long long)h * 64;
+}
+template <bool EXT> __device__ __forceinline__ int q_shift(const AttnParams& p) {
+  if constexpr (EXT) return p.P;
+  else return 0;
+}
 
 constexpr int KSTR = 72;  // LDS row stride (elements) for the 64-wide K / Vᵀ tiles: 144 B, 16-B aligned rows
 
@@ -221,10 +236,12 @@ __device__ __forceinline__ unsigned pack16x2(float lo, float hi) { return F16 ? 
 // unchanged), O^T += V^T P^T takes the kept ones, 1 / (1 - p) goes into the final 1 / l; mask bits from kx_dropout.h, one
 // Philox block per (query, four keys) = per accumulator register quadruple (two when Tk % 4 != 0: the rows of the mask then
 // do not start on block boundaries).
-template <bool CAUSAL, bool F16 = false, bool FOLD = false, bool DROP = false>
+template <bool CAUSAL, bool F16 = false, bool FOLD = false, bool DROP = false, bool EXT = false>
 __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const AttnParams p) {
   static_assert(!(CAUSAL && FOLD), "the tail fold is for unmasked launches (causal blocks are paired instead)");
+  static_assert(!EXT || (CAUSAL && !F16 && !FOLD && !DROP), "EXT: the causal bf16 forward kernel over a KV cache");
   static_assert(!(DROP && (F16 || FOLD)), "attention dropout: the bf16 training kernel");
+  const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2][64 * 64];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2][64 * VSTR];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -246,8 +263,8 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
   const int qw0 = qblk0 + wave * 32;                        // first query of this wave
   const bool wave_live = qw0 < p.Tq && (!FOLD || wave < 4 || blockIdx.y + 1 == gridDim.y);   // (FOLD: wave 4 = the tail, last block only)
   const bf16_t* qp = reinterpret_cast<const bf16_t*>(p.q) + (long long)b * p.qbs + (long long)h * 64;
-  const bf16_t* kp = reinterpret_cast<const bf16_t*>(p.k) + (long long)b * p.kbs + (long long)h * 64;
-  const bf16_t* vp = reinterpret_cast<const bf16_t*>(p.v) + (long long)b * p.kbs + (long long)h * 64;
+  const bf16_t* kp = reinterpret_cast<const bf16_t*>(p.k) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
+  const bf16_t* vp = reinterpret_cast<const bf16_t*>(p.v) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
 
   u32x4_t qf[2][2];
 #pragma unroll
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
   }
 
   int ntiles = (p.Tk + 63) >> 6;
-  if (CAUSAL) ntiles = min(ntiles, (min(qblk0 + 127, p.Tq - 1) >> 6) + 1);
+  if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 127, p.Tq - 1) + P) >> 6) + 1);
 
   // cooperative tile loads: thread owns chunks c = tid, tid+256 -> (row c>>3, 16-B part c&7)
   u32x4_t kreg[2], vreg[2];
@@ -297,7 +314,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
   for (int t = 0; t < ntiles; ++t) {
     const int buf = t & 1, kv0 = t * 64;
     if (t + 1 < ntiles) gload(t + 1);
-    const bool work = wave_live && (!CAUSAL || kv0 <= min(qw0 + 31, p.Tq - 1));
+    const bool work = wave_live && (!CAUSAL || kv0 <= min(qw0 + 31, p.Tq - 1) + P);
     if (work) {
       // ---- S^T = K Q^T : one K fragment feeds both query blocks ----
       f32x4_t st[2][4];
@@ -317,7 +334,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
       }
       // ---- online softmax per query block (query = lane&15; its keys sit in 4 lanes x 16 registers) ----
       // Masking is needed only on the tile that holds the sequence end or crosses this wave's diagonal (wave-uniform).
-      const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qw0);
+      const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qw0 + P);
       // Tile 0 holds key 0, which no mask removes (causal: key 0 <= every query), so the running maximum is finite
       // from the first tile on and exp2(-inf - finite) = 0 covers the start: no -inf guard in the chain.
       u32x4_t pf[2][2];
@@ -326,7 +343,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
         if (need_mask) {
-          const int qi = qw0 + qb * 16 + li;
+          const int qi = qw0 + qb * 16 + li + P;
 #pragma unroll
           for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -514,8 +531,10 @@ __device__ __forceinline__ f32x4_t mma_f16(u32x4_t a, u32x4_t b, f32x4_t c) {
 // one and a half tiles of the block's last two instead of waves 0-1 one and waves 2-3 two (T = 114: 6 wave-tiles in 1.5 tile
 // times instead of 2).  Per query nothing changes — same tiles in the same order, a skipped tile is one whose every score was
 // masked (alpha = 1, p = 0 exactly): bit-identical to the consecutive mapping.
-template <bool CAUSAL, int PVS, bool HL = false>
+template <bool CAUSAL, int PVS, bool HL = false, bool EXT = false>
 __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
+  static_assert(!EXT || (CAUSAL && PVS == 1 && !HL), "EXT: the causal split-fp16 kernel on fp32 rows over a KV cache");
+  const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
   __shared__ __attribute__((aligned(16))) unsigned short Kh[2][64 * 64], Kl[2][64 * 64];
   __shared__ __attribute__((aligned(16))) unsigned short Vh[2][64 * VSTR], Vl[2][64 * VSTR];
   constexpr float SC = 256.0f;                               // operand pre-scale (see above)
@@ -533,8 +552,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
   const int qrow[2] = {il ? qblk0 + wave * 16 : qw0, il ? qblk0 + 64 + wave * 16 : qw0 + 16};   // first query of block qb
   const bool wave_live = qrow[0] < p.Tq;
   const float* qp = reinterpret_cast<const float*>(p.q) + (long long)b * p.qbs + (long long)h * 64;
-  const float* kp = reinterpret_cast<const float*>(p.k) + (long long)b * p.kbs + (long long)h * 64;
-  const float* vp = reinterpret_cast<const float*>(p.v) + (long long)b * p.kbs + (long long)h * 64;
+  const float* kp = reinterpret_cast<const float*>(p.k) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
+  const float* vp = reinterpret_cast<const float*>(p.v) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
 
   u32x4_t qh[2][2], ql[2][2];
 #pragma unroll
@@ -562,7 +581,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
     for (int d = 0; d < 4; ++d) ot[qb][d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   }
   int ntiles = (p.Tk + 63) >> 6;
-  if (CAUSAL) ntiles = min(ntiles, (min(qblk0 + 127, p.Tq - 1) >> 6) + 1);
+  if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 127, p.Tq - 1) + P) >> 6) + 1);
 
   // cooperative tile loads: thread owns (row c>>3, 8-value part c&7) for c = tid, tid + 256: two float4 each of K and V
   float4 kreg[2][2], vreg[2][2];
@@ -623,8 +642,8 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
     if (t + 1 < ntiles) gload(t + 1);
     // block qb of this wave has work in this tile when the tile starts at or below its last query (causal); block 1 holds the
     // later rows, so block 0 working implies block 1 working — two forms of the tile body: both blocks, or block 1 alone
-    const bool work1 = wave_live && (!CAUSAL || kv0 <= min(qrow[1] + 15, p.Tq - 1));
-    const bool work0 = wave_live && (!CAUSAL || kv0 <= min(qrow[0] + 15, p.Tq - 1));
+    const bool work1 = wave_live && (!CAUSAL || kv0 <= min(qrow[1] + 15, p.Tq - 1) + P);
+    const bool work0 = wave_live && (!CAUSAL || kv0 <= min(qrow[0] + 15, p.Tq - 1) + P);
     auto tile_body = [&](auto q0_c) __attribute__((always_inline)) {
       constexpr int Q0 = decltype(q0_c)::value;
       // ---- S'^T = K' Q'^T, three products per (key block, k-step, query block) ----
@@ -652,9 +671,9 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
       constexpr float L2S = 1.44269504088896340736f / (SC * SC);     // exp(S) = exp2(S' * log2e / 2^16)
 #pragma unroll
       for (int qb = Q0; qb < 2; ++qb) {
-        const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qrow[qb]);
+        const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qrow[qb] + P);
         if (need_mask) {
-          const int qi = qrow[qb] + li;
+          const int qi = qrow[qb] + li + P;
 #pragma unroll
           for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -860,8 +879,10 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
 // 16 queries per wave, 64 per workgroup.  k-slice map of S^T = K Q^T: slice g <-> head dims 16g + s (s = MFMA step),
 // so a lane's 16 operand values are contiguous: 4 x 16-byte reads of its key row / query row.
 // Replaces the wave-per-query VALU kernel below as the default (36 -> a few ms of a 150 ms fp32-mode step).
-template <bool CAUSAL>
+template <bool CAUSAL, bool EXT = false>
 __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) {
+  static_assert(!EXT || CAUSAL, "EXT: the causal kernel over a KV cache");
+  const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
   constexpr int PITCH = 68;                                  // floats per LDS row (272 B: 16-byte aligned, bank-skewed)
   __shared__ __attribute__((aligned(16))) float Ks[64 * PITCH];
   __shared__ __attribute__((aligned(16))) float Vs[64 * PITCH];
@@ -874,8 +895,8 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
   const int qw0 = qblk0 + wave * 16, qi = qw0 + li;
   const bool wave_live = qw0 < p.Tq;
   const float* qp = reinterpret_cast<const float*>(p.q) + (long long)b * p.qbs + (long long)h * 64;
-  const float* kp = reinterpret_cast<const float*>(p.k) + (long long)b * p.kbs + (long long)h * 64;
-  const float* vp = reinterpret_cast<const float*>(p.v) + (long long)b * p.kbs + (long long)h * 64;
+  const float* kp = reinterpret_cast<const float*>(p.k) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
+  const float* vp = reinterpret_cast<const float*>(p.v) + (long long)b * p.kbs + kv_head_off<EXT>(p, h);
 
   float qf[16];
   {
@@ -888,7 +909,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
   for (int d = 0; d < 4; ++d) ot[d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
   int ntiles = (p.Tk + 63) >> 6;
-  if (CAUSAL) ntiles = min(ntiles, (min(qblk0 + 63, p.Tq - 1) >> 6) + 1);
+  if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 63, p.Tq - 1) + P) >> 6) + 1);
 
   for (int t = 0; t < ntiles; ++t) {
     const int kv0 = t * 64;
@@ -906,7 +927,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
       *reinterpret_cast<float4*>(&Vs[row * PITCH + part * 4]) = vv;
     }
     __syncthreads();
-    if (!wave_live || (CAUSAL && kv0 > min(qw0 + 15, p.Tq - 1))) continue;   // wave-uniform; barriers stay aligned
+    if (!wave_live || (CAUSAL && kv0 > min(qw0 + 15, p.Tq - 1) + P)) continue;   // wave-uniform; barriers stay aligned
 
     // ---- S^T = K Q^T ----
     f32x4_t st[4];
@@ -927,7 +948,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kv0 + kb * 16 + 4 * g + r;
-        const bool ok = key < p.Tk && (!CAUSAL || key <= qi);
+        const bool ok = key < p.Tk && (!CAUSAL || key <= qi + P);
         st[kb][r] = ok ? (CAUSAL ? score_nan_to_num(st[kb][r]) : st[kb][r]) : -INFINITY;
         mloc = fmaxf(mloc, st[kb][r]);
       }
@@ -1335,13 +1356,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   }
 }
 
-// prefill: copy the k and v column blocks of the fused qkv rows [B*T, 3D] into the caches [B, Tmax, D]
+// prefill: copy the k and v column blocks of the fused qkv rows [B*T, 3D] into rows [row0, row0 + T) of the caches [B, Tmax, D]
 template <typename T>
 __global__ __launch_bounds__(256) void kv_prefill_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                          int Tlen, int D, long long cache_batch, long long cache_head,
-                                                         long long cache_row) {
-  const long long row = blockIdx.x;                       // b*T + t
-  const long long b = row / Tlen, t = row % Tlen;
+                                                         long long cache_row, int row0) {
+  const long long row = blockIdx.x;                       // b*T + i
+  const long long b = row / Tlen, t = row0 + row % Tlen;
   const uint4* src = reinterpret_cast<const uint4*>(qkv + row * 3 * D);
   constexpr int EPV = 16 / sizeof(T);
   const int nv = D / EPV;
@@ -1356,17 +1377,56 @@ __global__ __launch_bounds__(256) void kv_prefill_kernel(const T* __restrict__ q
 }  // namespace
 
 int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t T, int64_t D, int64_t Tmax, int prec,
-                         hipStream_t s) {
+                         hipStream_t s, int64_t row0) {
   KxProfScope prof(KX_K_MISC, B * T, D, 4, s);
   const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;
   const long long ch = head_major ? Tmax * 64 : 64, cr = head_major ? 64 : D;
   if (prec == KX_PREC_BF16)
     hipLaunchKernelGGL(kv_prefill_kernel<bf16_t>, dim3((unsigned)(B * T)), dim3(256), 0, s, (const bf16_t*)qkv,
-                       (bf16_t*)kc, (bf16_t*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr);
+                       (bf16_t*)kc, (bf16_t*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr, (int)row0);
   else
     hipLaunchKernelGGL(kv_prefill_kernel<float>, dim3((unsigned)(B * T)), dim3(256), 0, s, (const float*)qkv, (float*)kc,
-                       (float*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr);
+                       (float*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr, (int)row0);
   KX_CHECK_LAUNCH("kv_prefill");
+  return KX_OK;
+}
+
+// Attention of Tn new rows per sequence over a cache that holds P: the append (its own launch, so every key — the new rows' too —
+// is then read from the cache alone), and the EXT instantiation of the precision's causal flash kernel: the prefill's grid
+// (query-block pairs (x, nx-1-x) over the Tn queries), key tiles from 0, the mask's diagonal at key P + i.
+extern "C" int kx_attention_extend(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out, int64_t B,
+                                   int64_t H, int64_t Tn, int64_t P, int64_t Tmax, int32_t prec, void* stream) {
+  KX_REQUIRE(qkv && kcache && vcache && out, "kx_attention_extend: null pointer");
+  KX_REQUIRE(B > 0 && H > 0 && B < 65536 && H < 65536, "kx_attention_extend: B/H empty or beyond the grid limits");
+  KX_REQUIRE(Tn >= 1 && P >= 0 && P + Tn <= Tmax && Tmax <= 0x7fffffffll,
+             "kx_attention_extend: rows %lld .. %lld outside the cache of %lld rows", (long long)P, (long long)(P + Tn - 1), (long long)Tmax);
+  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "kx_attention_extend: bad precision");
+  KX_REQUIRE(odt == KX_F32 || (prec == KX_PREC_F16C ? odt == KX_F16C : odt == KX_BF16),
+             "kx_attention_extend: the output is fp32, or bf16 (KX_PREC_BF16, KX_PREC_F32) / KX_F16C rows (KX_PREC_F16C)");
+  KX_REQUIRE(prec != KX_PREC_F32 || kx_tuning_get(KX_TUNE_ATTN_VARIANT) != 1, "kx_attention_extend: the first-version fp32 kernel (tuning key 2 = 1) has no cache form");
+  KX_REQUIRE((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out) & 15) == 0, "kx_attention_extend: pointers must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t D = H * 64;
+  KX_TRY(kx_launch_kv_prefill(qkv, kcache, vcache, B, Tn, D, Tmax, prec, s, P));
+  const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;   // per sequence [H][Tmax][64]; tuning key 9 = 1: [Tmax][H*64]
+  AttnParams p;
+  memset(&p, 0, sizeof(p));
+  p.q = (const char*)qkv; p.qbs = Tn * 3 * D; p.qrs = 3 * D;
+  p.k = (const char*)kcache; p.v = (const char*)vcache; p.kbs = Tmax * D;
+  p.khs = head_major ? Tmax * 64 : 64; p.krs = head_major ? 64 : D;
+  const int64_t ors = odt == KX_F16C ? 2 * D : D;                     // (KX_F16C rows: strides count 2-byte units)
+  p.out = out; p.obs = Tn * ors; p.ors = ors; p.o_bf16 = odt == KX_BF16; p.o_f16c = odt == KX_F16C;
+  p.B = (int)B; p.H = (int)H; p.Tq = (int)Tn; p.Tk = (int)(P + Tn); p.P = (int)P;
+  p.stats_out = stats_out;
+  p.drop_inv_keep = 1.0f;
+  p.interleave = kx_tuning_get(KX_TUNE_ATTN_VARIANT) != 8;
+  KxProfScope prof(prec == KX_PREC_F32 ? KX_K_ATTN_F32 : prec == KX_PREC_F16C ? KX_K_ATTN_F16S : KX_K_ATTN_BF16, B * H, Tn, P + Tn, s);
+  const unsigned nx = (unsigned)((Tn + 127) / 128);
+  const dim3 gc((unsigned)H, (nx + 1) / 2, (unsigned)B);
+  if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_bf16_v2_kernel<true, false, false, false, true>), gc, dim3(256), 0, s, p);
+  else if (prec == KX_PREC_F16C) hipLaunchKernelGGL((attn_f16s_kernel<true, 1, false, true>), gc, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_f32_mfma_kernel<true, true>), dim3((unsigned)((Tn + 63) / 64), (unsigned)H, (unsigned)B), dim3(256), 0, s, p);
+  KX_CHECK_LAUNCH("kx_attention_extend");
   return KX_OK;
 }
 

@@ -315,6 +315,6 @@ int kx_launch_rows_bcast(const float* src, float* dst, int64_t B, int64_t rows, 
 int kx_launch_patchify(const float* pixels, void* patches, int64_t B, int image, int patch, int kpad, int prec,
                        hipStream_t s);
 int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t T, int64_t D, int64_t Tmax, int prec,
-                         hipStream_t s);
+                         hipStream_t s, int64_t row0 = 0);   // the rows go to cache rows [row0, row0 + T)
 int kx_launch_vit_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int64_t B,
                            int tokens, int dim, hipStream_t s);

@@ -522,14 +522,17 @@ extern "C" size_t kx_decoder_workspace_bytes(const kx_decoder_weights* w, int64_
 static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B, int64_t T, const float* xq_cs,
                                 const float* xq_ss, const float* xk_cs, const float* xk_ss, void* logits, int32_t ldt,
                                 void* workspace, size_t workspace_bytes, int32_t prec, void* stream, void* kcache,
-                                void* vcache, int64_t Tmax) {
-  KX_REQUIRE(w && x && logits && workspace, "kx_decoder_forward: null pointer");
+                                void* vcache, int64_t Tmax, int64_t P = 0, bool need_logits = true) {
+  // P > 0 (kx_decoder_extend): the caches already hold P rows per sequence and the T rows are positions P .. P + T - 1 — the XPos
+  // tables are read from row P, the append goes to row P and the attention reads its keys from the cache (kx_attention_extend).
+  // !need_logits (kx_decoder_extend with logits == NULL): the call ends after the last layer.
+  KX_REQUIRE(w && x && (logits || !need_logits) && workspace, "kx_decoder_forward: null pointer");
   KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_forward");
   KX_REQUIRE(prec >= KX_PREC_BF16 && prec <= KX_PREC_F16, "kx_decoder_forward: bad precision %d (KX_PREC_F32W24 / W16 are decode-step formats)", prec);
   KX_REQUIRE(!kcache == !vcache, "kx_decoder_prefill: kcache and vcache must be given together");
   KX_REQUIRE(!kcache || (prec != KX_PREC_BF16X3 && prec != KX_PREC_F16),
              "kx_decoder_prefill: incremental decoding is offered in bf16, fp32 and f16c (fp32 cache)");
-  KX_REQUIRE(!kcache || T <= Tmax, "kx_decoder_prefill: %lld tokens do not fit a %lld-row cache", (long long)T,
+  KX_REQUIRE(!kcache || (P >= 0 && P + T <= Tmax), "kx_decoder_prefill: %lld tokens do not fit a %lld-row cache", (long long)(P + T),
              (long long)Tmax);
   KX_REQUIRE(B > 0 && T > 0, "kx_decoder_forward: empty input");
   KX_REQUIRE(w->dim == w->heads * 64, "kx_decoder_forward: head_dim must be 64 (dim=%d heads=%d)", w->dim, w->heads);
@@ -573,6 +576,7 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
                       !(kx_tuning_get(KX_TUNE_GEMM_RULES) & 4) && kx_tuning_get(KX_TUNE_GEMM_EPILOGUE) != 1 &&
                       kx_tuning_get(KX_TUNE_GEMM_TILE) == 0 && kx_tuning_get(KX_TUNE_ATTN_VARIANT) == 0;
   bool h_ready = false;                                   // d.h already holds the LayerNorm this layer starts with
+  const int64_t xo = w->xpos ? P * 32 : 0;                // the XPos tables' first row ([*, 32] floats each)
   for (int i = 0; i < w->layers; ++i) {
     const kx_decoder_layer& L = w->layer[i];
     // x = x + out_proj(inner_attn_ln(attn(xpos(q), xpos(k), v)))   on self_attn_layer_norm(x)
@@ -582,9 +586,9 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     KX_FAM(0);
     KX_TRY(gemm(d.h, D, fold ? L.wqkv_f : L.wqkv, D, d.qkv, 3 * D, (qkv_hl && !st1) ? KX_F16HL : qdt(prec), M, 3 * D,
                 fold ? L.bqkv_f : L.bqkv, nullptr, 0,
-                0.125f, D, prec, s, w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? T : 0, w->xpos ? D : 0,
-                st1 ? d.stats2 : nullptr, st1 ? L.wqkv_colsum : nullptr));
-    if (kcache) {   // incremental decoding: keep this layer's (XPos-rotated) keys and values
+                0.125f, D, prec, s, w->xpos ? xq_cs + xo : nullptr, xq_ss + xo, xk_cs + xo, xk_ss + xo, w->xpos ? T : 0,
+                w->xpos ? D : 0, st1 ? d.stats2 : nullptr, st1 ? L.wqkv_colsum : nullptr));   // ([*, 32] tables: row m % T of those from row P)
+    if (kcache && P == 0) {   // incremental decoding: keep this layer's (XPos-rotated) keys and values
       const size_t layer_bytes = (size_t)B * Tmax * D * qes(prec);
       KX_TRY(kx_launch_kv_prefill(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, B, T, D, Tmax,
                                   prec, s));
@@ -596,13 +600,20 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     a.kv_batch_stride = T * 3 * D; a.kv_row_stride = 3 * D;
     a.B = B; a.H = w->heads; a.Tq = T; a.Tk = T; a.mask = KX_ATTN_CAUSAL; a.prec = (qkv_hl && !st1) ? KX_PREC_F16CHL : aprec(prec);
     a.out = d.att; a.out_batch_stride = T * D * kmul(prec); a.out_row_stride = D * kmul(prec); a.odt = ct;
+    // the layer's attention: the prefill's causal launch, or over the P cached rows (which appends the new keys and values itself)
+    auto attend = [&]() -> int {
+      if (P == 0) return kx_attention(&a, stream);
+      const size_t layer_bytes = (size_t)B * Tmax * D * qes(prec);
+      return kx_attention_extend(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct, a.stats_out, B,
+                                 w->heads, T, P, Tmax, aprec(prec), stream);
+    };
     RowFusion ro, r2;
     ro.ln_out = d.h; ro.ln_dt = ct; ro.ln_g = L.fl_g; ro.ln_b = L.fl_b; ro.eps = w->eps;
     if (w->subln) {
       // inner_attn_ln folded into out_proj: the attention kernel emits per-(row, head) partial statistics, the GEMM
       // multiplies the un-normalised output by γ⊙Wo and applies rstd·(acc − mean·colsum) + (β·Woᵀ + bo) in its epilogue
       a.stats_out = d.partials;
-      KX_TRY(kx_attention(&a, stream));
+      KX_TRY(attend());
       if (fuse_o) {
         ro.partials = d.partials; ro.nseg = w->heads; ro.seg = 64;
         KX_FAM(1);
@@ -617,7 +628,7 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
                     0, 0, nullptr, L.wo_colsum, nullptr, &fo, fold ? &lop : nullptr));
       }
     } else {
-      KX_TRY(kx_attention(&a, stream));
+      KX_TRY(attend());
       KX_FAM(1);
       KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr, 0,
                   0, nullptr, nullptr, nullptr, fuse_o ? &ro : nullptr, fold ? &lop : nullptr));
@@ -659,6 +670,7 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     if (fold) KX_TRY(kx_row_stats_finalize(d.partials2, M, D / 64, 64, w->eps, d.stats2, stream));
     h_ready = fuse_2;                                     // d.h = the next layer's (or the final) LayerNorm of x
   }
+  if (!need_logits) return KX_OK;                         // (an extend whose rows nobody reads: the caches are what it was for)
   if (fold) {                                             // decoder.layer_norm folded into the output projection
     KX_FAM(4);
     KX_TRY(gemm(d.h, D, w->wout_f, D, logits, w->vocab, ldt, M, w->vocab, w->bout_f, nullptr, 0, 1.f, 0, prec, s, nullptr,
@@ -685,6 +697,17 @@ extern "C" int kx_decoder_prefill(const kx_decoder_weights* w, float* x, int64_t
   KX_REQUIRE(kcache && vcache && Tmax > 0, "kx_decoder_prefill: cache missing");
   return decoder_forward_impl(w, x, B, T, xq_cs, xq_ss, xk_cs, xk_ss, logits, ldt, workspace, workspace_bytes, prec,
                               stream, kcache, vcache, Tmax);
+}
+
+extern "C" int kx_decoder_extend(const kx_decoder_weights* w, float* x, int64_t B, int64_t T, int64_t P, const float* xq_cs,
+                                 const float* xq_ss, const float* xk_cs, const float* xk_ss, void* logits, int32_t ldt,
+                                 void* kcache, void* vcache, int64_t Tmax, void* workspace, size_t workspace_bytes, int32_t prec,
+                                 void* stream) {
+  KX_REQUIRE(kcache && vcache && Tmax > 0, "kx_decoder_extend: cache missing");
+  KX_REQUIRE(P >= 0 && T >= 1 && P + T <= Tmax, "kx_decoder_extend: rows %lld .. %lld outside the cache of %lld rows", (long long)P,
+             (long long)(P + T - 1), (long long)Tmax);
+  return decoder_forward_impl(w, x, B, T, xq_cs, xq_ss, xk_cs, xk_ss, logits, ldt, workspace, workspace_bytes, prec, stream, kcache,
+                              vcache, Tmax, P, logits != nullptr);
 }
 
 // How the step's rows map to cache rows.

@@ -45,8 +45,11 @@ from . import ops
 def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
-                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None):
+                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
+                  prompt_rows=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
+    ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
+    reads — the last position, or lengths[b] - 1 of a ragged row.
     ``prompt_tokens`` [B, Tt] int64: what the repetition penalty sees before the first new token.  ``pos_shift`` > 0: the
     prompt holds that many spliced rows that are not tokens and text rows carry two position rows (the multimodal prompt
     under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t].
@@ -58,6 +61,9 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     row b's number of prompt TOKENS, where ``lengths`` counts the spliced rows too.  ``output_logits`` keeps returning the
     model's own logits, taken before the bans."""
     B, T, V = logits.shape
+    gathered = prompt_rows is not None
+    if gathered:
+        T = prompt_rows
     dev = logits.device
     cons = check_constraint_args(V, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                  min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
@@ -78,7 +84,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         # history slots already hold the row's own first prompt token (mask_padding): the penalty is applied once per distinct
         # id, so the duplicates change nothing and every row keeps the common hist_len.
         last = torch.tensor([l - 1 for l in lengths], dtype=torch.int64, device=dev)
-        row = logits[torch.arange(B, device=dev), last]                   # [B, V]
+        row = logits[:, 0] if gathered else logits[torch.arange(B, device=dev), last]   # [B, V]
         positions = torch.tensor(lengths, dtype=torch.int32, device=dev)
         state.update(positions=positions, pos_max=max(lengths))
         decoder._ragged_scratch(state, dev)                               # (before the first sampler launch: no fill between steps)
@@ -222,8 +228,9 @@ def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_seq
 
 def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tokens: int, *, num_beams: int, pos_shift: int = 0,
               length_penalty=1.0, early_stopping=False, num_return_sequences=1, eos_token_id=None, pad_token_id=1, eos_poll=8,
-              output_scores=False, output_trace=False, bad_words_ids=None, min_new_tokens=0):
-    """Beam search after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (the prefill ran once per batch row).
+              output_scores=False, output_trace=False, bad_words_ids=None, min_new_tokens=0, prompt_rows=None):
+    """Beam search after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (the prefill ran once per batch row;
+    ``prompt_rows`` as there: ``logits`` [B, 1, V] holds the last position alone).
     Per token: kx_beam_step on the rows the last step wrote (step 0: the B prefill rows, one input beam each), kx_kv_cache_gather
     of cache rows 0:t into the other B * W-row cache by the step's src_row, then the uniform decode step at B * W rows and
     the common host position.  Every buffer is allocated before the first step; the host reads ``done.all()`` at the stop poll
@@ -233,6 +240,8 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
     Returns tokens int64 [B, n] (R = 1) or [B, R, n], then the fp32 [B, R] scores with ``output_scores``, then the trace dict
     with ``output_trace`` (the contract: include/kosmosx_hip.h, "Beam search on the device")."""
     B, T, V = logits.shape
+    if prompt_rows is not None:
+        T = prompt_rows
     dev = logits.device
     W, R, N = int(num_beams), int(num_return_sequences), int(max_new_tokens)
     BW = B * W
@@ -333,8 +342,9 @@ def check_lookup_args(batch: int, *, prompt_lookup_num_tokens=0, max_matching_ng
 
 def lookup_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
                 num_drafts: int, ngram_max: int = 2, pos_shift: int = 0, eos_token_id=None, pad_token_id=1, eos_poll=8,
-                output_logits=False, output_acceptance=False, draft_from=None):
+                output_logits=False, output_acceptance=False, draft_from=None, prompt_rows=None):
     """Greedy decoding with prompt-lookup speculation after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop
+    (``prompt_rows`` as there: ``logits`` [B, 1, V] holds the last position alone)
     (state["max_len"] >= T + max_new_tokens + num_drafts), ``prompt_tokens`` [B, Tt] int64 the ids the lookup starts from (the
     TEXT ids: spliced image rows contribute none).  Per verify step g: kx_sample_logits (greedy) on the step's [B * Kin, V] block
     (Kin = 1: the prefill's last row; K = num_drafts + 1 afterwards), kx_spec_accept (the contract: include/kosmosx_hip.h,
@@ -347,6 +357,8 @@ def lookup_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_to
     row's end); then with ``output_acceptance`` the int32 [B, steps] tokens emitted per step, for the steps in which some row still
     emitted (the steps issued after the last row finished and before the poll noticed are not listed)."""
     B, T, V = logits.shape
+    if prompt_rows is not None:
+        T = prompt_rows
     dev = logits.device
     D, N = int(num_drafts), int(max_new_tokens)
     K = D + 1
@@ -473,9 +485,9 @@ def check_score_args(batch: int, continuations, continuation_lengths=None, promp
 
 
 def score_loop(decoder, prec: str, state: dict, logits: torch.Tensor, continuations: torch.Tensor, clens: list, pidx: list,
-               plens: list, *, pos_shift: int = 0, output_logits=False):
+               plens: list, *, pos_shift: int = 0, output_logits=False, prompt_rows=None):
     """The log-probs of C candidates after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (state["max_len"] >=
-    T + L - 1), ``continuations`` int64 [C, L] on the device, ``clens`` / ``pidx`` the host lists check_score_args returned and
+    T + L - 1; ``prompt_rows`` as there: ``logits`` [B, 1, V] holds row len_b - 1 of every prompt alone), ``continuations`` int64 [C, L] on the device, ``clens`` / ``pidx`` the host lists check_score_args returned and
     ``plens`` [B] the prompts' positions (spliced rows included).  Column 0: kx_token_logprob on the prefill's rows, addressed
     through a row index (row len_b - 1 of the candidate's prompt; no [C, V] copy).  Columns 1..L-1: ONE kx_decoder_score_step with
     M = C * (L - 1) rows — candidate c's row j is fed continuations[c, j] at position len_b + j, its last token is never fed — and one
@@ -495,7 +507,10 @@ def score_loop(decoder, prec: str, state: dict, logits: torch.Tensor, continuati
     if getattr(decoder, "validate_token_ids", True):
         check = _begin_token_id_check(tokens, decoder.embed_tokens.weight.shape[0])              # finished after the launches
     target = torch.where(live, tokens, torch.full((), -1, dtype=torch.int64, device=dev))       # -1: kx_token_logprob leaves 0.0
-    rows0 = torch.tensor([pidx[c] * T + plens[pidx[c]] - 1 for c in range(C)], dtype=torch.int32, device=dev)
+    if prompt_rows is not None:                                                                  # one row per prompt: its own
+        rows0 = torch.tensor(pidx, dtype=torch.int32, device=dev)
+    else:
+        rows0 = torch.tensor([pidx[c] * T + plens[pidx[c]] - 1 for c in range(C)], dtype=torch.int32, device=dev)
     flat = logits.view(B * T, V)
     out = torch.empty((C, L), dtype=torch.float32, device=dev)
     lp0 = ops.token_logprob(flat, target[:, 0].contiguous(), row_index=rows0)
@@ -525,10 +540,24 @@ def score_loop(decoder, prec: str, state: dict, logits: torch.Tensor, continuati
     return out
 
 
-def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True):
+def check_prefill_chunk(prefill_chunk):
+    """ValueError for a ``prefill_chunk`` that is not None or a positive int (bool excluded); host only."""
+    if prefill_chunk is None:
+        return None
+    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1:
+        raise ValueError(f"prefill_chunk must be a positive integer (the rows prefilled per pass) or None, got {prefill_chunk!r}")
+    return prefill_chunk
+
+
+def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True, chunk=None):
     """The prompt's prefill, under torch.no_grad(): ``prompt`` as run_generate takes it, ``new_rows`` (+ ``spare``) the positions the
     caller will add, checked against the tables when ``budget``.  Returns the tokens as prefilled (trimmed to the longest prompt, the
-    padding masked), the host lengths (None: a uniform batch), T (prefix rows included), the state and the prefill's logits."""
+    padding masked), the host lengths (None: a uniform batch), T (prefix rows included), the state, the prefill's logits and the
+    loops' ``prompt_rows``: None with the [B, T, V] logits of the one-piece prefill.
+    ``chunk`` C < T (check_prefill_chunk): the rows are embedded once and prefilled C at a time — rows [0, C) by the prefill call,
+    with the XPos centring of the whole T (state["xpos_centre"]), every later slice by Decoder._extend — the first slice always
+    writes its C logits rows, a later one only if it holds a row the loops read, last position or len_b - 1; those rows are
+    returned as [B, 1, V] with ``prompt_rows`` = T."""
     tokens, lens = prompt["tokens"], None
     if prompt_lengths is not None:
         lens = resolve_prompt_lengths(prompt_lengths, tokens.shape[0], tokens.shape[1], min_len=prompt["min_len"])
@@ -547,8 +576,28 @@ def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0,
     # a score() candidate reads cache rows < len_b only.
     passed_x = prompt["passed_x"](tokens)                                   # (the prompt's ids are range-checked here or in the prefill, once)
     state = {"max_len": T + new_rows + spare}                               # (rejected drafts still occupy table and cache rows)
-    logits = model.decoder._forward_incremental(tokens if passed_x is None else None, state, passed_x, model.precision)
-    return tokens, lens, T, state, logits
+    if chunk is None or chunk >= T:
+        logits = model.decoder._forward_incremental(tokens if passed_x is None else None, state, passed_x, model.precision)
+        return tokens, lens, T, state, logits, None
+    decoder = model.decoder
+    x = decoder.embed(tokens, model.precision) if passed_x is None else passed_x               # [B, T, D], embedded once
+    B = x.shape[0]
+    last = [T - 1] * B if lens is None else [prompt["prefix_rows"] + l - 1 for l in lens]      # the row every sequence reads
+    rows = None
+    state["xpos_centre"] = T
+    for s0 in range(0, T, chunk):
+        s1 = min(s0 + chunk, T)
+        want = [b for b in range(B) if s0 <= last[b] < s1]
+        if s0 == 0:
+            logits = decoder._forward_incremental(None, state, x[:, :s1], model.precision)
+        else:
+            logits = decoder._extend(x[:, s0:s1], state, model.precision, output_logits=bool(want))
+        if want:
+            if rows is None:
+                rows = torch.empty((B, 1, logits.shape[2]), dtype=torch.float32, device=logits.device)
+            idx = torch.tensor(want, dtype=torch.int64, device=logits.device)
+            rows[idx, 0] = logits[idx, torch.tensor([last[b] - s0 for b in want], dtype=torch.int64, device=logits.device)]
+    return tokens, lens, T, state, rows, T
 
 
 def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
@@ -569,10 +618,12 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     drafts = check_lookup_args(tokens.shape[0] if tokens.dim() else 0, draft_from=kw["_draft_from"], **pick(
         "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
         "sequence_ids", *constraints, "eos_poll"))
+    chunk = check_prefill_chunk(kw["prefill_chunk"])
     prompt["check"]()
     with torch.no_grad():
-        tokens, lens, _, state, logits = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts)
-        common = dict(pos_shift=prompt["pos_shift"], **pick("eos_token_id", "pad_token_id", "eos_poll"))
+        tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts,
+                                                               chunk=chunk)
+        common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
                                ngram_max=kw["max_matching_ngram_size"], draft_from=kw["_draft_from"], **common,
@@ -591,13 +642,14 @@ def run_score(model, prompt: dict, continuations, kw: dict):
     tokens = prompt["tokens"]
     B = tokens.shape[0] if tokens.dim() else 0
     clens, pidx = check_score_args(B, continuations, kw["continuation_lengths"], kw["prompt_index"])
+    chunk = check_prefill_chunk(kw["prefill_chunk"])
     prompt["check"](continuations=continuations)
     L = continuations.shape[1]
     with torch.no_grad():
-        _, lens, T, state, logits = _prefill(model, prompt, kw["prompt_lengths"], L - 1, budget=L > 1)
+        _, lens, T, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], L - 1, budget=L > 1, chunk=chunk)
         return score_loop(model.decoder, model.precision, state, logits, continuations, clens, pidx,
                           [T] * B if lens is None else [prompt["prefix_rows"] + l for l in lens], pos_shift=prompt["pos_shift"],
-                          output_logits=kw["output_logits"])
+                          output_logits=kw["output_logits"], prompt_rows=prompt_rows)
 
 
 def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0):

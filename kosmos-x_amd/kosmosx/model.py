@@ -803,6 +803,61 @@ class Decoder(_PackedMixin, nn.Module):
         return logits
 
     # -- incremental decoding ---------------------------------------------------
+    def _incremental_precision(self, prec: str) -> str:
+        """The stage precision the KV-cache kernels run ``prec`` in (bf16, fp32 or f16c), or the refusal."""
+        if self.args.activation_fn != "gelu":
+            raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
+                                      "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
+        model_prec = prec
+        prec = H.stage_precision(prec, "decoder", self._gemm_widths())
+        if prec == "bf16x3":
+            # the cache kernels are offered in bf16, fp32 and f16c.  Under the default mode the bf16x3 stage fallback (widths
+            # that are not multiples of 128, ADVICE r3) decodes in fp32 — the other arithmetic inside the tolerance that
+            # the prefill / step kernels implement; an explicit bf16x3 is refused here, not by a C error three calls down.
+            if model_prec != "mixed":
+                raise ValueError("incremental decoding is offered in bf16, fp32, f16c and mixed; precision 'bf16x3' has no "
+                                 "KV-cache kernels (use 'fp32' for the same accuracy class)")
+            prec = "fp32"
+        return prec
+
+    def _extend(self, x, state: dict, prec: str, output_logits: bool = True, tokens=None):
+        """Append Tn rows per sequence to a filled uniform state in one pass (kx_decoder_extend): ``x`` [B, Tn, D] fp32, the rows
+        already embedded for positions len .. len + Tn - 1 (copied, not consumed) — or None and ``tokens`` [B, Tn], embedded here at
+        those positions after the checks.  Returns the fp32 logits [B, Tn, V], or None without ``output_logits`` (the call then
+        ends after the last layer).  Advances state["len"] by Tn; any error leaves the state where it was (a later valid call
+        rewrites the rows)."""
+        if state.get("positions") is not None:
+            raise ValueError("a ragged incremental state (state['positions']) is stepped with next_token only: extend() takes a "
+                             "uniform state, every sequence at state['len']")
+        prec = self._incremental_precision(prec)
+        w, _, _, emb, pos = self._pack(prec)
+        lib = H.load()
+        P, Tmax, B = state["len"], state["max_len"], state["batch"]
+        Bx, Tn = (tokens if x is None else x).shape[:2]
+        if state["prec"] != prec:
+            raise RuntimeError("precision changed between incremental steps")
+        if Bx != B:
+            raise ValueError("batch size changed between incremental steps")
+        if Tn < 1:
+            raise ValueError("extend() takes at least one new row per sequence")
+        t = P + Tn - 1                                                     # the furthest row: what the table / cache must still hold
+        if t >= Tmax or t + 2 >= pos.shape[0]:
+            raise IndexError(f"index out of range in self: position {t + 2} exceeds the table / cache")
+        if x is None:
+            x = self.embed(tokens, prec, pos_offset=P, defer_check=True)
+        else:
+            _require_cuda(x, "passed_x")
+            x = x.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        logits = torch.empty((B, Tn, w.vocab), dtype=torch.float32, device=x.device) if output_logits else None
+        need = lib.kx_decoder_workspace_bytes(C.byref(w), B, Tn, H.PRECS[prec])
+        buf = self._ws.get(need, x.device)
+        H.check(lib.kx_decoder_extend(C.byref(w), x.data_ptr(), B, Tn, P, *(H.ptr(tb) for tb in state["xpos"]), H.ptr(logits),
+                                      H.KX_F32, state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, buf.data_ptr(),
+                                      buf.numel(), H.PRECS[prec], _stream()), "kx_decoder_extend")
+        self._finish_check()
+        state["len"] = P + Tn
+        return logits
+
     def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None,
                              pos_shift: int = 0, logits_out=None) -> torch.Tensor:
         """torchscale's incremental_state protocol: the first call runs the whole prefix and fills the KV cache,
@@ -822,20 +877,10 @@ class Decoder(_PackedMixin, nn.Module):
         buffer for the step's logits.  Returns [B * K, 1, V].
         Score steps (score()): ``state["score"]`` = (K, cache_seq) with ``cache_seq`` an int32 [C] device tensor makes the step C
         candidates of K rows over the B cache sequences, candidate c reading sequence cache_seq[c] and nobody appending
-        (kx_decoder_score_step); ``next_token`` and ``state["positions"]`` are [C * K].  Returns [C * K, 1, V]."""
-        if self.args.activation_fn != "gelu":
-            raise NotImplementedError(f"incremental decoding with activation_fn={self.args.activation_fn!r}: the weight-streaming "
-                                      "decode kernels offer gelu only (kx_act in include/kosmosx_hip.h)")
-        model_prec = prec
-        prec = H.stage_precision(prec, "decoder", self._gemm_widths())
-        if prec == "bf16x3":
-            # the cache kernels are offered in bf16, fp32 and f16c.  Under the default mode the bf16x3 stage fallback (widths
-            # that are not multiples of 128, ADVICE r3) decodes in fp32 — the other arithmetic inside the tolerance that
-            # the prefill / step kernels implement; an explicit bf16x3 is refused here, not by a C error three calls down.
-            if model_prec != "mixed":
-                raise ValueError("incremental decoding is offered in bf16, fp32, f16c and mixed; precision 'bf16x3' has no "
-                                 "KV-cache kernels (use 'fp32' for the same accuracy class)")
-            prec = "fp32"
+        (kx_decoder_score_step); ``next_token`` and ``state["positions"]`` are [C * K].  Returns [C * K, 1, V].
+        ``state["xpos_centre"]`` (first call only; chunked prefill): the sequence length the XPos tables are centred on when the
+        first call holds only the prompt's first rows; default: the first call's own length."""
+        prec = self._incremental_precision(prec)
         w, _, _, emb, pos = self._pack(prec)
         lib = H.load()
         D, L = self.args.decoder_embed_dim, self.num_layers
@@ -855,8 +900,9 @@ class Decoder(_PackedMixin, nn.Module):
             state["vcache"] = torch.empty((L, B, nh, Tmax, 64), dtype=dt, device=x.device)
             xp = self.layers[0].self_attn.xpos
             if xp is not None:
-                q = xp.tables_centred(Tmax, T, False)
-                k = xp.tables_centred(Tmax, T, True)
+                centre = int(state.get("xpos_centre", T))
+                q = xp.tables_centred(Tmax, centre, False)
+                k = xp.tables_centred(Tmax, centre, True)
                 state["xpos"] = tuple(t.to(x.device) for t in (*q, *k))
             else:
                 state["xpos"] = (None,) * 4
@@ -1209,7 +1255,8 @@ class Kosmos(nn.Module):
                  sequence_ids=None, eos_poll=8, output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0,
                  early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
-                 prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None):
+                 prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
+                 prefill_chunk=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1241,7 +1288,13 @@ class Kosmos(nn.Module):
         Greedy only, B * (D + 1) <= 16 rows, and the budget is T + max_new_tokens + D positions; sampling, the filters, the
         penalty, beams, ``prompt_lengths``, ``sequence_ids`` and the constraints raise ValueError together with it.
         ``output_acceptance``: also the int32 [B, steps] number of tokens every row emitted at every verify step (column 0:
-        the token taken from the prefill).  Returned after the logits when both are asked for."""
+        the token taken from the prefill).  Returned after the logits when both are asked for.
+        ``prefill_chunk`` C (a positive int; default None: one piece): the prompt's T rows — embedded once, spliced image rows
+        included — are prefilled C at a time, rows [0, C) through the prefill and every later slice through kx_decoder_extend on
+        top of the cache the earlier ones filled, with the XPos centring of the whole prompt.  The first slice always writes its C logits rows
+        (it is the prefill call); a later slice computes logits only if it holds a row the loop reads (the last position;
+        ``prompt_lengths[b] - 1`` of a ragged row), so the memory of the prefill is that of C rows instead of T; the new tokens are those of the one-piece prefill up to the rounding of a
+        different summation order.  C >= T is the one-piece path.  It composes with every other argument."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1252,10 +1305,11 @@ class Kosmos(nn.Module):
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from))
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
+            prefill_chunk=prefill_chunk))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
-              prompt_index=None, prompt_lengths=None, output_logits=False):
+              prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
         """Log-likelihood of candidate continuations of the prompts -> ``token_logprobs`` fp32 [C, L] on the device: entry [c, j] is
         log P(continuations[c, j] | prompt, continuations[c, :j]), and exactly 0.0 at padded slots.  A candidate's sequence score
         is ``token_logprobs.sum(1)``; divide by the lengths for a per-token score.  With ``output_logits`` also the fp32 [C, L, V]
@@ -1263,7 +1317,8 @@ class Kosmos(nn.Module):
         ``continuations`` int64 [C, L], 1 <= L <= 16 (the K-row decode step's limit); ``continuation_lengths`` [C] ints or an
         integer tensor, each in 1..L (default L): the slots at and after a candidate's length are padding and are ignored
         whatever they hold.  ``prompt_index`` [C] host ints in [0, B): the prompt every candidate continues — any mapping;
-        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` as in generate().
+        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` and ``prefill_chunk``
+        as in generate().
         The prompts are prefilled once, exactly as generate() prefills them; column 0 is read from the prefill's row at the prompt's
         end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
         prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
@@ -1273,7 +1328,7 @@ class Kosmos(nn.Module):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
         return generation.run_score(self, self._prompt(text_tokens, images), continuations, dict(
             continuation_lengths=continuation_lengths, prompt_index=prompt_index, prompt_lengths=prompt_lengths,
-            output_logits=output_logits))
+            output_logits=output_logits, prefill_chunk=prefill_chunk))
 
     def _prompt(self, text_tokens, images) -> dict:
         """The multimodal prompt as generation.run_generate / run_score take it: tower -> resampler -> splice, as in forward()."""
@@ -1387,17 +1442,40 @@ class KosmosLanguage(nn.Module):
         model_input = self.decoder.embed(x, self.precision)         # :319
         return self.decoder.run(model_input, self.precision)        # :320
 
+    def extend(self, x: torch.Tensor, incremental_state: dict, *, output_logits=True):
+        """Append the Tn new tokens ``x`` [B, Tn] (the new ids only, not the history) to the KV cache of ``incremental_state`` in
+        one pass through the forward's GEMMs and flash attention -> fp32 logits [B, Tn, V], row i what forward() returns at
+        position len + i of the whole sequence; None with ``output_logits=False`` (no final LayerNorm, no output projection: for
+        known text whose continuation is not wanted yet).  The tokens are embedded at positions len .. len + Tn - 1, ids outside
+        the vocabulary and positions past the table / cache raise IndexError as in forward() and leave the state where it was.
+        An empty state: the prefill, exactly as ``forward(x, incremental_state=state)`` — its logits are computed whatever
+        ``output_logits`` says, the saving applies to a filled state only.  A ragged, block or score state
+        (``state["positions"]``) raises ValueError.  Afterwards single-token steps through ``forward(history,
+        incremental_state=state)`` continue as before."""
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("x must be an instance of torch.Tensor")
+        if not isinstance(incremental_state, dict):
+            raise TypeError("incremental_state must be the dict the first incremental call filled (or an empty one)")
+        if x.dim() != 2:
+            raise ValueError(f"x must be [batch, new tokens], got {tuple(x.shape)}")
+        _warn_train_mode(self)
+        if "len" not in incremental_state:
+            logits = self.decoder._forward_incremental(x, incremental_state, None, self.precision)
+            return logits if output_logits else None
+        return self.decoder._extend(None, incremental_state, self.precision, output_logits, tokens=x)
+
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
                  repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
-                 max_matching_ngram_size=2, output_acceptance=False, _draft_from=None):
+                 max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
         arguments that go with it: beam search, as there; ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens`` and
         ``stop_sequences``: the constraints, as there; ``prompt_lookup_num_tokens``, ``max_matching_ngram_size`` and
-        ``output_acceptance``: speculative decoding by prompt lookup, as there)."""
+        ``output_acceptance``: speculative decoding by prompt lookup, as there; ``prefill_chunk``: the prompt prefilled that many
+        rows at a time, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1408,10 +1486,11 @@ class KosmosLanguage(nn.Module):
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from))
+            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
+            prefill_chunk=prefill_chunk))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
-              prompt_lengths=None, output_logits=False):
+              prompt_lengths=None, output_logits=False, prefill_chunk=None):
         """Log-likelihood of candidate continuations of the prompts -> ``token_logprobs`` fp32 [C, L] on the device: entry [c, j] is
         log P(continuations[c, j] | prompt, continuations[c, :j]), and exactly 0.0 at padded slots.  A candidate's sequence score
         is ``token_logprobs.sum(1)``; divide by the lengths for a per-token score.  With ``output_logits`` also the fp32 [C, L, V]
@@ -1419,7 +1498,8 @@ class KosmosLanguage(nn.Module):
         ``continuations`` int64 [C, L], 1 <= L <= 16 (the K-row decode step's limit); ``continuation_lengths`` [C] ints or an
         integer tensor, each in 1..L (default L): the slots at and after a candidate's length are padding and are ignored
         whatever they hold.  ``prompt_index`` [C] host ints in [0, B): the prompt every candidate continues — any mapping;
-        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` as in generate().
+        default: C is a multiple of B and candidate c belongs to prompt c // (C // B).  ``prompt_lengths`` and ``prefill_chunk``
+        as in generate().
         The prompts are prefilled once, exactly as generate() prefills them; column 0 is read from the prefill's row at the prompt's
         end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
         prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
@@ -1429,7 +1509,7 @@ class KosmosLanguage(nn.Module):
             raise TypeError("x must be an instance of torch.Tensor")
         return generation.run_score(self, self._prompt(x), continuations, dict(
             continuation_lengths=continuation_lengths, prompt_index=prompt_index, prompt_lengths=prompt_lengths,
-            output_logits=output_logits))
+            output_logits=output_logits, prefill_chunk=prefill_chunk))
 
     def _prompt(self, x) -> dict:
         """The text prompt as generation.run_generate / run_score take it."""

@@ -623,6 +623,26 @@ def attention_decode_shared(qkv, kcache, vcache, positions, cache_seq, error_wor
     return out
 
 
+def attention_extend(qkv, kcache, vcache, P, *, out_dtype="f32", stats_out=None, layout="head_major", f16c=False):
+    """Kernel-level wrapper of kx_attention_extend (include/kosmosx_hip.h, "Chunked prefill"): Tn new rows per sequence on top of
+    caches that hold ``P`` rows (a host int, the same for every sequence).  qkv [B * Tn, 3 * H * 64] fp32 or bf16, row b * Tn + i the
+    i-th new token of sequence b; kcache / vcache [B, H, Tmax, 64] ([B, Tmax, H, 64] with ``layout`` "row_major", as
+    ops.attention_decode) of the same dtype: rows P .. P + Tn - 1 are appended, query i attends rows 0 .. P + i.  out_dtype "f32" |
+    "bf16" | "f16c" (KX_F16C rows: the split-fp16 kernel; ``f16c`` asks for that kernel with an fp32 output); stats_out
+    [B * Tn, H, 2] fp32 optional.  Returns the output rows [B * Tn, ...]."""
+    _need_cuda(qkv, kcache, vcache, stats_out)
+    B = kcache.shape[0]
+    if B < 1 or qkv.dim() != 2 or qkv.shape[0] % B:
+        raise ValueError("attention_extend: qkv [B*Tn, 3*H*64] holds the same number of new rows for each of the caches' B sequences")
+    Tn = qkv.shape[0] // B
+    B, Hh, Tmax, _, odt, out, prec = _decode_attention_args("attention_extend", qkv, kcache, vcache, layout, out_dtype, None, None, Tn)
+    if f16c and prec == H.KX_PREC_F32:
+        prec = H.KX_PREC_F16C
+    H.check(H.load().kx_attention_extend(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                         H.ptr(stats_out), B, Hh, Tn, int(P), Tmax, prec, _stream()), "kx_attention_extend")
+    return out
+
+
 def token_logprob(logits, target, *, row_index=None, vocab=None, out=None):
     """Kernel-level wrapper of kx_token_logprob (include/kosmosx_hip.h, "Scoring candidates over a shared prompt cache"):
     out[r] = log softmax(logits[row_index[r], :V])[target[r]] in one launch, no softmax written.  logits fp32 [rows_available, ld]
