@@ -99,40 +99,16 @@ extern "C" int kx_prof_collect(kx_prof_record* out, int max_records) {
   return n;
 }
 
-// split-K scratch of the stage currently being launched (set by the stage entry points, read by gemm())
-thread_local void* g_splitk_ws = nullptr;
-thread_local size_t g_splitk_ws_bytes = 0;
+namespace {
+
+// Stage scratch, carved from the caller's workspace by the *_plan functions below and handed to every launch through Stage.
 constexpr size_t KX_SPLITK_WS = 32u << 20;   // 32 MB: enough for 16 slices of every batch-1 GEMM on the path
 // The last 4 KB of the stage's split-K scratch are the arrival words of the in-launch reduction (kx_gemm_args.splitk_flags: one
-// per workgroup; every launch writes its own epoch, so the launches of a stream share them): cleared once per stage call on
-// the stage's stream.
-thread_local unsigned* g_coop_counters = nullptr;
+// per workgroup; every launch writes its own epoch, so the launches of a stream share them).
 constexpr size_t KX_COOP_WORDS = 1024;
-struct SplitkScope {
-  bool ok = true;
-  SplitkScope(void* p, size_t n, hipStream_t s) {
-    g_splitk_ws = p; g_splitk_ws_bytes = n - KX_COOP_WORDS * 4;
-    g_coop_counters = p ? (unsigned*)((char*)p + n - KX_COOP_WORDS * 4) : nullptr;
-    // (only when the in-launch reduction is switched on, tuning key 17 = 1: the shipped path never reads these words)
-    if (g_coop_counters && kx_tuning_get(KX_TUNE_SPLITK_COOP) == 1 && hipMemsetAsync(g_coop_counters, 0, KX_COOP_WORDS * 4, s) != hipSuccess) {
-      kx_set_error("clearing the split-K arrival counters failed");
-      ok = false;
-    }
-  }
-  ~SplitkScope() { g_splitk_ws = nullptr; g_splitk_ws_bytes = 0; g_coop_counters = nullptr; }
-};
-#define KX_SPLITK_SCOPE(ptr, stream) SplitkScope sk((ptr), KX_SPLITK_WS, (stream)); if (!sk.ok) return KX_ERR_LAUNCH
-// scratch of the 256x256 kernel's pair split (kx_gemm_args.pair_ws) of the stage being launched: 4 KB of hand-off words,
-// cleared once per stage call, + one 128 KB slab per workgroup of a full round
-thread_local void* g_pair_ws = nullptr;
-thread_local size_t g_pair_ws_bytes = 0;
+// scratch of the 256x256 kernel's pair split (kx_gemm_args.pair_ws): 4 KB of hand-off words + one 128 KB slab per workgroup
+// of a full round
 constexpr size_t KX_PAIR_WS = 4096 + (size_t)256 * 131072;
-struct PairScope {
-  PairScope(void* p, size_t n) { g_pair_ws = p; g_pair_ws_bytes = p ? n : 0; }
-  ~PairScope() { g_pair_ws = nullptr; g_pair_ws_bytes = 0; }
-};
-
-namespace {
 
 struct Carver {
   char* base; size_t off;
@@ -160,21 +136,19 @@ inline int aprec(int prec) {
 // operand row length in 2-byte units per value (the unit lda / ldc / attention output strides count for these formats)
 inline int64_t kmul(int prec) { return prec == KX_PREC_BF16X3 ? 3 : prec == KX_PREC_F16C ? 2 : 1; }
 
-// what the row-owning split-K reduce can absorb (kx_gemm_args: stats_partials, ln_out)
-// GEMM family of the NEXT gemm() call of this thread, for the per-family fp8-correction assignment of KX_PREC_F16C stages
-// (kx_gemm_args.f16c_corr, tuning key 16: two bits per family — 0 decoder qkv, 1 out_proj, 2 fc1, 3 fc2, 4 output projection,
-// 5 every Perceiver GEMM).  gemm() consumes it; a call without KX_FAM contracts both corrections.
-thread_local int g_gemm_family = -1;
-#define KX_FAM(f) g_gemm_family = (f)
+// GEMM family of a launch, for the per-family fp8-correction assignment of KX_PREC_F16C stages (kx_gemm_args.f16c_corr,
+// tuning key 16: two bits per family, numbered as here).  A launch without a family contracts both corrections.
+enum GemmFamily { FAM_NONE = -1, FAM_QKV = 0, FAM_OUT_PROJ = 1, FAM_FC1 = 2, FAM_FC2 = 3, FAM_LOGITS = 4, FAM_PERCEIVER = 5 };
 // The shipped assignment (tuning key 16 = -1 selects it too): DESIGN.md §5 "one correction instead of two, per family".
 constexpr int KX_F16C_CORR_DEFAULT = 0;
-static int f16c_corr_of(int family) {
-  if (family < 0) return KX_CORR_BOTH;
+static int f16c_corr_of(GemmFamily family) {
+  if (family == FAM_NONE) return KX_CORR_BOTH;
   int v = kx_tuning_get(KX_TUNE_F16C_CORR);
   if (v < 0) v = KX_F16C_CORR_DEFAULT;
   return (v >> (2 * family)) & 3;
 }
 
+// what the row-owning split-K reduce can absorb (kx_gemm_args: stats_partials, ln_out)
 struct RowFusion {
   const float* partials = nullptr; int64_t nseg = 0, seg = 0;            // folded-LN statistics straight from the producer
   float* scratch = nullptr;                                              // tile kernels: kx_gemm_args.row_stats_scratch (finalised (mean, rstd))
@@ -186,52 +160,82 @@ struct RowFusion {
 struct LnOp { void* out; int dt; float* stats; };
 inline bool fold_prec(int prec) { return prec == KX_PREC_BF16 || prec == KX_PREC_F16 || prec == KX_PREC_F16C; }
 
-int gemm(const void* A, int64_t lda, const void* W, int64_t K, void* C, int64_t ldc, int cdtype, int64_t M, int64_t N,
-         const float* bias, const float* residual, int act, float qscale, int64_t qcols, int prec, hipStream_t s,
-         const float* xq_cs = nullptr, const float* xq_ss = nullptr, const float* xk_cs = nullptr,
-         const float* xk_ss = nullptr, int64_t xT = 0, int64_t xdim = 0, const float* row_stats = nullptr,
-         const float* colsum = nullptr, float* stats_out = nullptr, const RowFusion* rf = nullptr,
-         const LnOp* lo = nullptr) {
-  kx_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  // bf16x3: the same bf16 kernels over the 3K-wide split operands ([hi|hi|lo] activations x [hi|lo|hi] weights)
-  // f16c: fp16 + fp8 correction segments, 4K bytes per row; a packed weight matrix is N rows followed by N scale bytes
-  const int64_t km = kmul(prec);
-  const bool f16c = prec == KX_PREC_F16C;
-  g.A = A; g.lda = lda * km; g.W = W; g.ldw = K * km; g.C = C;
-  g.ldc = cdtype == KX_BF16X3 ? 3 * ldc : cdtype == KX_F16C ? 2 * ldc : ldc; g.cdt = cdtype;
-  g.bias = bias; g.residual = residual; g.ldr = ldc; g.M = M; g.N = N; g.K = f16c ? K : K * km;
-  if (f16c) g.w_scale = (const uint8_t*)W + (size_t)N * (size_t)K * 4;
-  g.f16c_corr = f16c ? f16c_corr_of(g_gemm_family) : KX_CORR_BOTH;
-  g_gemm_family = -1;
-  g.act = act; g.qscale = qscale; g.qcols = qcols;
-  g.xq_cs = xq_cs; g.xq_ss = xq_ss; g.xk_cs = xk_cs; g.xk_ss = xk_ss; g.xpos_T = xT; g.xpos_dim = xdim;
-  g.prec = km == 3 ? KX_PREC_BF16 : prec;   // bf16x3 runs the bf16 kernels over 3K
-  g.tile = kx_tuning_get(KX_TUNE_GEMM_TILE);
-  g.row_stats = row_stats; g.colsum = colsum; g.stats_out = stats_out;
-  g.splitk_ws = g_splitk_ws; g.splitk_ws_bytes = g_splitk_ws_bytes; g.splitk = 0;
-  // opt-in (tuning key 17 = 1): the in-launch reduction measured 0.4-4 us SLOWER per GEMM than the reduce launch it replaces on
-  // every batch-1 shape (write-through partials + the arrival poll against a 1.5-1.9 us launch boundary), the batch-1 forward
-  // 4.52 vs 3.85 ms (profiles/r06_d_coop_bench.log, r06_d_b1_ab.log)
-  g.splitk_flags = kx_tuning_get(KX_TUNE_SPLITK_COOP) == 1 ? g_coop_counters : nullptr;
-  g.pair_ws = g_pair_ws; g.pair_ws_bytes = g_pair_ws_bytes;
-  if (rf) {
-    g.stats_partials = rf->partials; g.stats_in_nseg = rf->nseg; g.stats_in_seg = rf->seg; g.stats_eps = rf->eps;
-    g.row_stats_scratch = rf->scratch;
-    g.ln_out = rf->ln_out; g.ln_out_dt = rf->ln_dt; g.ln_out_gamma = rf->ln_g; g.ln_out_beta = rf->ln_b; g.ln_out_eps = rf->eps;
-  }
-  if (lo) { g.ln_operand_out = lo->out; g.ln_operand_dt = lo->dt; g.ln_operand_stats = lo->stats; }
-  return kx_gemm(&g, (void*)s);
-}
+// One tile-kernel / split-K GEMM launch of a stage — see kx_gemm_args in the header.  Precision and stream are the stage's.
+struct Gemm {
+  const void* A; int64_t lda; const void* W; int64_t K; void* C; int64_t ldc; int cdt; int64_t M, N;
+  const float* bias = nullptr; const float* residual = nullptr; int act = 0; float qscale = 1.f; int64_t qcols = 0;
+  const float *xq_cs = nullptr, *xq_ss = nullptr, *xk_cs = nullptr, *xk_ss = nullptr; int64_t xT = 0, xdim = 0;
+  const float* row_stats = nullptr; const float* colsum = nullptr; float* stats_out = nullptr;
+  const RowFusion* rf = nullptr; const LnOp* lo = nullptr;
+  GemmFamily family = FAM_NONE;
+};
 
-// Will kx_gemm's automatic choice split this (M, N, K) problem, i.e. is the row-owning reduce (RowFusion) available?
-// Same rule as kx_gemm itself; an explicit tile override (A/B runs) keeps the separate kernels.
-bool row_reduce_available(int64_t M, int64_t N, int64_t K, int prec) {
-  if (kx_tuning_get(KX_TUNE_GEMM_TILE) != 0 || N > 8192 || N % 4 != 0) return false;
-  if (prec == KX_PREC_F16C) return kx_gemm_auto_splits(M, N, K, prec, g_splitk_ws_bytes) > 1;
-  const int gp = prec == KX_PREC_BF16X3 ? KX_PREC_BF16 : prec;
-  return kx_gemm_auto_splits(M, N, K * kmul(prec), gp, g_splitk_ws_bytes) > 1;
-}
+// What every launch of one stage call shares: built once by the stage entry point, after its plan.
+struct Stage {
+  hipStream_t s; int prec;
+  void* splitk_ws; size_t splitk_ws_bytes;      // split-K scratch (KX_SPLITK_WS less the arrival words)
+  unsigned* coop_words;                         // the arrival words
+  void* pair_ws; size_t pair_ws_bytes;          // pair-split scratch (decoder forward / prefill / extend only)
+  Stage(hipStream_t s, int prec, void* splitk, void* pair = nullptr)
+      : s(s), prec(prec), splitk_ws(splitk), splitk_ws_bytes(KX_SPLITK_WS - KX_COOP_WORDS * 4),
+        coop_words(splitk ? (unsigned*)((char*)splitk + splitk_ws_bytes) : nullptr), pair_ws(pair), pair_ws_bytes(pair ? KX_PAIR_WS : 0) {}
+
+  // The words a stage call must find zero, cleared on its stream before its first launch.
+  int clear_words() const {
+    // (only when the in-launch reduction is switched on, tuning key 17 = 1: the shipped path never reads these words)
+    if (coop_words && kx_tuning_get(KX_TUNE_SPLITK_COOP) == 1 && hipMemsetAsync(coop_words, 0, KX_COOP_WORDS * 4, s) != hipSuccess) {
+      kx_set_error("clearing the split-K arrival counters failed");
+      return KX_ERR_LAUNCH;
+    }
+    if (pair_ws && hipMemsetAsync(pair_ws, 0, 4096, s) != hipSuccess) {      // hand-off words: zero when a call is issued
+      kx_set_error("kx_decoder_forward: clearing the pair-split hand-off words failed");
+      return KX_ERR_LAUNCH;
+    }
+    return KX_OK;
+  }
+
+  int gemm(const Gemm& v) const {
+    kx_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    // bf16x3: the same bf16 kernels over the 3K-wide split operands ([hi|hi|lo] activations x [hi|lo|hi] weights)
+    // f16c: fp16 + fp8 correction segments, 4K bytes per row; a packed weight matrix is N rows followed by N scale bytes
+    const int64_t km = kmul(prec);
+    const bool f16c = prec == KX_PREC_F16C;
+    g.A = v.A; g.lda = v.lda * km; g.W = v.W; g.ldw = v.K * km; g.C = v.C;
+    g.ldc = v.cdt == KX_BF16X3 ? 3 * v.ldc : v.cdt == KX_F16C ? 2 * v.ldc : v.ldc; g.cdt = v.cdt;
+    g.bias = v.bias; g.residual = v.residual; g.ldr = v.ldc; g.M = v.M; g.N = v.N; g.K = f16c ? v.K : v.K * km;
+    if (f16c) g.w_scale = (const uint8_t*)v.W + (size_t)v.N * (size_t)v.K * 4;
+    g.f16c_corr = f16c ? f16c_corr_of(v.family) : KX_CORR_BOTH;
+    g.act = v.act; g.qscale = v.qscale; g.qcols = v.qcols;
+    g.xq_cs = v.xq_cs; g.xq_ss = v.xq_ss; g.xk_cs = v.xk_cs; g.xk_ss = v.xk_ss; g.xpos_T = v.xT; g.xpos_dim = v.xdim;
+    g.prec = km == 3 ? KX_PREC_BF16 : prec;   // bf16x3 runs the bf16 kernels over 3K
+    g.tile = kx_tuning_get(KX_TUNE_GEMM_TILE);
+    g.row_stats = v.row_stats; g.colsum = v.colsum; g.stats_out = v.stats_out;
+    g.splitk_ws = splitk_ws; g.splitk_ws_bytes = splitk_ws_bytes; g.splitk = 0;
+    // opt-in (tuning key 17 = 1): the in-launch reduction measured 0.4-4 us SLOWER per GEMM than the reduce launch it replaces on
+    // every batch-1 shape (write-through partials + the arrival poll against a 1.5-1.9 us launch boundary), the batch-1 forward
+    // 4.52 vs 3.85 ms (profiles/r06_d_coop_bench.log, r06_d_b1_ab.log)
+    g.splitk_flags = kx_tuning_get(KX_TUNE_SPLITK_COOP) == 1 ? coop_words : nullptr;
+    g.pair_ws = pair_ws; g.pair_ws_bytes = pair_ws_bytes;
+    if (v.rf) {
+      const RowFusion& rf = *v.rf;
+      g.stats_partials = rf.partials; g.stats_in_nseg = rf.nseg; g.stats_in_seg = rf.seg; g.stats_eps = rf.eps;
+      g.row_stats_scratch = rf.scratch;
+      g.ln_out = rf.ln_out; g.ln_out_dt = rf.ln_dt; g.ln_out_gamma = rf.ln_g; g.ln_out_beta = rf.ln_b; g.ln_out_eps = rf.eps;
+    }
+    if (v.lo) { g.ln_operand_out = v.lo->out; g.ln_operand_dt = v.lo->dt; g.ln_operand_stats = v.lo->stats; }
+    return kx_gemm(&g, (void*)s);
+  }
+
+  // Will kx_gemm's automatic choice split this (M, N, K) problem, i.e. is the row-owning reduce (RowFusion) available?
+  // Same rule as kx_gemm itself; an explicit tile override (A/B runs) keeps the separate kernels.
+  bool row_reduce_available(int64_t M, int64_t N, int64_t K) const {
+    if (kx_tuning_get(KX_TUNE_GEMM_TILE) != 0 || N > 8192 || N % 4 != 0) return false;
+    if (prec == KX_PREC_F16C) return kx_gemm_auto_splits(M, N, K, prec, splitk_ws_bytes) > 1;
+    const int gp = prec == KX_PREC_BF16X3 ? KX_PREC_BF16 : prec;
+    return kx_gemm_auto_splits(M, N, K * kmul(prec), gp, splitk_ws_bytes) > 1;
+  }
+};
 
 static int cu_count() {   // CUs of the current device (cached for device 0..63)
   static std::atomic<int> cus[64];
@@ -278,6 +282,18 @@ int gemv16(const Gemv16& v, hipStream_t s) {
 int ln(const float* x, const float* pre, const float* g, const float* b, void* y, int ydt, int64_t rows, int64_t cols,
        float eps, hipStream_t s, int64_t rpg = 0, int64_t ogs = 0, int64_t oro = 0) {
   return kx_layernorm(x, pre, g, b, y, (kx_dtype)ydt, rows, cols, eps, rpg ? rpg : rows, ogs, oro, (void*)s);
+}
+
+// self-attention of B sequences of T rows out of a packed [B * T, 3 D] q | k | v buffer, into operand rows of the stage's format
+kx_attn_args packed_qkv_attention(const void* qkv, void* out, int64_t B, int64_t H, int64_t T, int64_t D, int mask, int prec) {
+  kx_attn_args a;
+  memset(&a, 0, sizeof(a));
+  a.q = qkv; a.q_batch_stride = T * 3 * D; a.q_row_stride = 3 * D;
+  a.k = (const char*)qkv + D * qes(prec); a.v = (const char*)qkv + 2 * D * qes(prec);
+  a.kv_batch_stride = T * 3 * D; a.kv_row_stride = 3 * D;
+  a.out = out; a.out_batch_stride = T * D * kmul(prec); a.out_row_stride = D * kmul(prec); a.odt = cdt(prec);
+  a.B = B; a.H = H; a.Tq = T; a.Tk = T; a.mask = mask; a.prec = aprec(prec);
+  return a;
 }
 
 // Binding guard (header, "Binding safety"): the caller's sizeof() of the weights struct and of its per-layer struct
@@ -402,16 +418,16 @@ extern "C" int kx_vit_forward(const kx_vit_weights* w, const float* pixels, int6
     return KX_ERR_WORKSPACE;
   }
   const int64_t G = w->image / w->patch, P = G * G, S = P + 1, M = B * S, MP = B * P, D = w->dim;
-  KX_SPLITK_SCOPE(v.splitk, s);
+  const Stage st(s, prec, v.splitk);
+  KX_TRY(st.clear_words());
   const int ct = cdt(prec);
   KX_TRY(kx_launch_patchify(pixels, v.patches, B, w->image, w->patch, w->kpad, prec, s));
-  KX_TRY(gemm(v.patches, w->kpad, w->wpatch, w->kpad, v.patch_out, D, KX_F32, MP, D, nullptr, nullptr, 0, 1.f, 0,
-              prec, s));
+  KX_TRY(st.gemm({v.patches, w->kpad, w->wpatch, w->kpad, v.patch_out, D, KX_F32, MP, D}));
   KX_TRY(kx_launch_vit_assemble(v.patch_out, w->cls, w->pos, v.xpre, B, (int)S, (int)D, s));
   KX_TRY(ln(v.xpre, nullptr, w->pre_g, w->pre_b, out, KX_F32, M, D, w->eps, s));
   // At batch 1 (M = 257) the GEMMs are split-K and the layer is a chain of dependent ~12 us launches: the residual
   // GEMMs' row-owning reduce kernels also write the LayerNorm that follows (layer_norm2 / the next layer's layer_norm1).
-  const bool fuse_o = row_reduce_available(M, D, D, prec), fuse_2 = row_reduce_available(M, D, w->ffn, prec);
+  const bool fuse_o = st.row_reduce_available(M, D, D), fuse_2 = st.row_reduce_available(M, D, w->ffn);
   // Folded layer_norm1 / layer_norm2 (large batches, the tile kernels): the residual GEMMs write the operand rows and the
   // row statistics of what they finish, qkv / fc1 multiply by gamma-folded weights — no LayerNorm kernel between layers.
   const bool fold = w->layers > 0 && w->layer[0].wqkv_f && fold_prec(prec) && !fuse_o && !fuse_2 && D % 64 == 0 &&
@@ -423,30 +439,33 @@ extern "C" int kx_vit_forward(const kx_vit_weights* w, const float* pixels, int6
     const bool st1 = fold && i > 0;                        // v.h = un-normalised rows + v.stats2 from the previous fc2
     if (fold && i == 0) KX_TRY(ln(out, nullptr, nullptr, nullptr, v.h, ct, M, D, w->eps, s));   // unit affine: the fold carries gamma / beta
     else if (!fold && !h_ready) KX_TRY(ln(out, nullptr, L.ln1_g, L.ln1_b, v.h, ct, M, D, w->eps, s));
-    KX_TRY(gemm(v.h, D, fold ? L.wqkv_f : L.wqkv, D, v.qkv, 3 * D, qdt(prec), M, 3 * D, fold ? L.bqkv_f : L.bqkv, nullptr, 0,
-                0.125f, D, prec, s, nullptr, nullptr, nullptr, nullptr, 0, 0, st1 ? v.stats2 : nullptr,
-                st1 ? L.wqkv_colsum : nullptr));
-    kx_attn_args a;
-    memset(&a, 0, sizeof(a));
-    a.q = v.qkv; a.q_batch_stride = S * 3 * D; a.q_row_stride = 3 * D;
-    a.k = (char*)v.qkv + D * qes(prec); a.v = (char*)v.qkv + 2 * D * qes(prec);
-    a.kv_batch_stride = S * 3 * D; a.kv_row_stride = 3 * D;
-    a.out = v.att; a.out_batch_stride = S * D * kmul(prec); a.out_row_stride = D * kmul(prec); a.odt = ct;
-    a.B = B; a.H = w->heads; a.Tq = S; a.Tk = S; a.mask = KX_ATTN_FULL; a.prec = aprec(prec);
+    Gemm q{v.h, D, fold ? L.wqkv_f : L.wqkv, D, v.qkv, 3 * D, qdt(prec), M, 3 * D};
+    q.bias = fold ? L.bqkv_f : L.bqkv; q.qscale = 0.125f; q.qcols = D;
+    if (st1) { q.row_stats = v.stats2; q.colsum = L.wqkv_colsum; }
+    KX_TRY(st.gemm(q));
+    const kx_attn_args a = packed_qkv_attention(v.qkv, v.att, B, w->heads, S, D, KX_ATTN_FULL, prec);
     KX_TRY(kx_attention(&a, stream));
     RowFusion ro, r2;
     ro.ln_out = v.h; ro.ln_dt = ct; ro.ln_g = L.ln2_g; ro.ln_b = L.ln2_b; ro.eps = w->eps;
-    KX_TRY(gemm(v.att, D, L.wo, D, out, D, KX_F32, M, D, L.bo, out, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr, 0,
-                0, nullptr, nullptr, nullptr, fuse_o ? &ro : nullptr, fold ? &lop : nullptr));
+    Gemm o{v.att, D, L.wo, D, out, D, KX_F32, M, D};
+    o.bias = L.bo; o.residual = out;
+    if (fuse_o) o.rf = &ro;
+    if (fold) o.lo = &lop;
+    KX_TRY(st.gemm(o));
     if (fold) KX_TRY(kx_row_stats_finalize(v.partials2, M, D / 64, 64, w->eps, v.stats2, stream));
     else if (!fuse_o) KX_TRY(ln(out, nullptr, L.ln2_g, L.ln2_b, v.h, ct, M, D, w->eps, s));
-    KX_TRY(gemm(v.h, D, fold ? L.w1_f : L.w1, D, v.ff, w->ffn, ct, M, w->ffn, fold ? L.b1_f : L.b1, nullptr, w->act, 1.f, 0,
-                prec, s, nullptr, nullptr, nullptr, nullptr, 0, 0, fold ? v.stats2 : nullptr, fold ? L.w1_colsum : nullptr));
+    Gemm f1{v.h, D, fold ? L.w1_f : L.w1, D, v.ff, w->ffn, ct, M, w->ffn};
+    f1.bias = fold ? L.b1_f : L.b1; f1.act = w->act;
+    if (fold) { f1.row_stats = v.stats2; f1.colsum = L.w1_colsum; }
+    KX_TRY(st.gemm(f1));
     const bool next = fuse_2 && i + 1 < w->layers;
     if (next) { r2.ln_out = v.h; r2.ln_dt = ct; r2.ln_g = w->layer[i + 1].ln1_g; r2.ln_b = w->layer[i + 1].ln1_b; r2.eps = w->eps; }
     const bool emit = fold && i + 1 < w->layers;           // the last layer's output is the tower's output: nothing follows
-    KX_TRY(gemm(v.ff, w->ffn, L.w2, w->ffn, out, D, KX_F32, M, D, L.b2, out, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr,
-                nullptr, 0, 0, nullptr, nullptr, nullptr, next ? &r2 : nullptr, emit ? &lop : nullptr));
+    Gemm f2{v.ff, w->ffn, L.w2, w->ffn, out, D, KX_F32, M, D};
+    f2.bias = L.b2; f2.residual = out;
+    if (next) f2.rf = &r2;
+    if (emit) f2.lo = &lop;
+    KX_TRY(st.gemm(f2));
     if (emit) KX_TRY(kx_row_stats_finalize(v.partials2, M, D / 64, 64, w->eps, v.stats2, stream));
     h_ready = next;
   }
@@ -474,7 +493,8 @@ extern "C" int kx_perceiver_forward(const kx_perceiver_weights* w, const float* 
     return KX_ERR_WORKSPACE;
   }
   const int64_t n = w->latents, D = w->dim, inner = (int64_t)w->heads * 64, MQ = B * n, MK = B * (m + n);
-  KX_SPLITK_SCOPE(p.splitk, s);
+  const Stage st(s, prec, p.splitk);
+  KX_TRY(st.clear_words());
   const int64_t F = D * w->ff_mult;
   const int ct = cdt(prec);
   KX_TRY(kx_launch_rows_bcast(w->latents_p, p.lat, B, n, D, s));
@@ -484,10 +504,12 @@ extern "C" int kx_perceiver_forward(const kx_perceiver_weights* w, const float* 
     KX_TRY(ln(x, w->media_pos, L.nm_g, L.nm_b, p.kvin, ct, B * m, D, w->eps, s, m, m + n, 0));
     KX_TRY(ln(p.lat, nullptr, L.nl_g, L.nl_b, p.kvin, ct, MQ, D, w->eps, s, n, m + n, m));
     KX_TRY(ln(p.lat, nullptr, L.nl_g, L.nl_b, p.lnq, ct, MQ, D, w->eps, s));
-    KX_FAM(5);
-    KX_TRY(gemm(p.lnq, D, L.wq, D, p.qb, inner, qdt(prec), MQ, inner, nullptr, nullptr, 0, 0.125f, inner, prec, s));
-    KX_FAM(5);
-    KX_TRY(gemm(p.kvin, D, L.wkv, D, p.kvb, 2 * inner, qdt(prec), MK, 2 * inner, nullptr, nullptr, 0, 1.f, 0, prec, s));
+    Gemm q{p.lnq, D, L.wq, D, p.qb, inner, qdt(prec), MQ, inner};
+    q.qscale = 0.125f; q.qcols = inner; q.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(q));
+    Gemm kv{p.kvin, D, L.wkv, D, p.kvb, 2 * inner, qdt(prec), MK, 2 * inner};
+    kv.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(kv));
     kx_attn_args a;
     memset(&a, 0, sizeof(a));
     a.q = p.qb; a.q_batch_stride = n * inner; a.q_row_stride = inner;
@@ -496,20 +518,23 @@ extern "C" int kx_perceiver_forward(const kx_perceiver_weights* w, const float* 
     a.out = p.att; a.out_batch_stride = n * inner * kmul(prec); a.out_row_stride = inner * kmul(prec); a.odt = ct;
     a.B = B; a.H = w->heads; a.Tq = n; a.Tk = m + n; a.mask = KX_ATTN_FULL; a.prec = aprec(prec);
     KX_TRY(kx_attention(&a, stream));
-    KX_FAM(5);
-    KX_TRY(gemm(p.att, inner, L.wout, inner, p.lat, D, KX_F32, MQ, D, nullptr, p.lat, 0, 1.f, 0, prec, s));
+    Gemm o{p.att, inner, L.wout, inner, p.lat, D, KX_F32, MQ, D};
+    o.residual = p.lat; o.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(o));
     KX_TRY(ln(p.lat, nullptr, L.ff_g, L.ff_b, p.lnq, ct, MQ, D, w->eps, s));
-    KX_FAM(5);
-    KX_TRY(gemm(p.lnq, D, L.w1, D, p.ffh, F, ct, MQ, F, nullptr, nullptr, KX_ACT_GELU, 1.f, 0, prec, s));
-    KX_FAM(5);
-    KX_TRY(gemm(p.ffh, F, L.w2, F, p.lat, D, KX_F32, MQ, D, nullptr, p.lat, 0, 1.f, 0, prec, s));
+    Gemm f1{p.lnq, D, L.w1, D, p.ffh, F, ct, MQ, F};
+    f1.act = KX_ACT_GELU; f1.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(f1));
+    Gemm f2{p.ffh, F, L.w2, F, p.lat, D, KX_F32, MQ, D};
+    f2.residual = p.lat; f2.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(f2));
   }
   if (lat_out) KX_TRY(ln(p.lat, nullptr, w->norm_g, w->norm_b, lat_out, KX_F32, MQ, D, w->eps, s));
   if (out && w->wproj) {
     KX_TRY(ln(p.lat, nullptr, w->norm_g, w->norm_b, p.fin, ct, MQ, D, w->eps, s));
-    KX_FAM(5);
-    KX_TRY(gemm(p.fin, D, w->wproj, D, out, w->out_dim, KX_F32, MQ, w->out_dim, nullptr, nullptr, 0, 1.f, 0, prec,
-                s));
+    Gemm pr{p.fin, D, w->wproj, D, out, w->out_dim, KX_F32, MQ, w->out_dim};
+    pr.family = FAM_PERCEIVER;
+    KX_TRY(st.gemm(pr));
   }
   return KX_OK;
 }
@@ -546,18 +571,13 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     return KX_ERR_WORKSPACE;
   }
   const int64_t M = B * T, D = w->dim, F = w->ffn;
-  KX_SPLITK_SCOPE(d.splitk, s);
-  PairScope pk(d.pair, KX_PAIR_WS);
-  if (d.pair && hipMemsetAsync(d.pair, 0, 4096, s) != hipSuccess) {      // hand-off words: zero when a call is issued
-    kx_set_error("kx_decoder_forward: clearing the pair-split hand-off words failed");
-    return KX_ERR_LAUNCH;
-  }
+  const Stage st(s, prec, d.splitk, d.pair);
+  KX_TRY(st.clear_words());
   const int ct = cdt(prec);
-  const size_t es = esz(prec);
   // Batch-1-sized problems (M = T = 114: every GEMM is split-K): the residual GEMMs' row-owning reduce kernels take the
   // folded-LN statistics straight from the producer's partials and write the LayerNorm that follows (final_layer_norm,
   // the next layer's self_attn_layer_norm, the decoder's last LayerNorm) — 9 launches per layer instead of 13.
-  const bool fuse_o = row_reduce_available(M, D, D, prec), fuse_2 = row_reduce_available(M, D, F, prec);
+  const bool fuse_o = st.row_reduce_available(M, D, D), fuse_2 = st.row_reduce_available(M, D, F);
   // Folded self_attn_layer_norm / final_layer_norm / decoder.layer_norm (large M, the tile kernels): out_proj and fc2 —
   // the GEMMs that finish a row of the residual stream — also write it as the next GEMM's operand (d.h) with its partial
   // statistics; qkv / fc1 / the output projection multiply by gamma-folded weights and apply rstd*(acc - mean*colsum) +
@@ -577,110 +597,80 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
                       kx_tuning_get(KX_TUNE_GEMM_TILE) == 0 && kx_tuning_get(KX_TUNE_ATTN_VARIANT) == 0;
   bool h_ready = false;                                   // d.h already holds the LayerNorm this layer starts with
   const int64_t xo = w->xpos ? P * 32 : 0;                // the XPos tables' first row ([*, 32] floats each)
+  const size_t layer_bytes = (size_t)B * Tmax * D * qes(prec);   // one layer of a cache (q/k/v-typed values)
   for (int i = 0; i < w->layers; ++i) {
     const kx_decoder_layer& L = w->layer[i];
     // x = x + out_proj(inner_attn_ln(attn(xpos(q), xpos(k), v)))   on self_attn_layer_norm(x)
     const bool st1 = fold && i > 0;                        // d.h = un-normalised rows of x + d.stats2 from the previous fc2
     if (fold && i == 0) KX_TRY(ln(x, nullptr, nullptr, nullptr, d.h, ct, M, D, w->eps, s));     // unit affine
     else if (!fold && !h_ready) KX_TRY(ln(x, nullptr, L.sa_g, L.sa_b, d.h, ct, M, D, w->eps, s));
-    KX_FAM(0);
-    KX_TRY(gemm(d.h, D, fold ? L.wqkv_f : L.wqkv, D, d.qkv, 3 * D, (qkv_hl && !st1) ? KX_F16HL : qdt(prec), M, 3 * D,
-                fold ? L.bqkv_f : L.bqkv, nullptr, 0,
-                0.125f, D, prec, s, w->xpos ? xq_cs + xo : nullptr, xq_ss + xo, xk_cs + xo, xk_ss + xo, w->xpos ? T : 0,
-                w->xpos ? D : 0, st1 ? d.stats2 : nullptr, st1 ? L.wqkv_colsum : nullptr));   // ([*, 32] tables: row m % T of those from row P)
-    if (kcache && P == 0) {   // incremental decoding: keep this layer's (XPos-rotated) keys and values
-      const size_t layer_bytes = (size_t)B * Tmax * D * qes(prec);
-      KX_TRY(kx_launch_kv_prefill(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, B, T, D, Tmax,
-                                  prec, s));
-    }
-    kx_attn_args a;
-    memset(&a, 0, sizeof(a));
-    a.q = d.qkv; a.q_batch_stride = T * 3 * D; a.q_row_stride = 3 * D;
-    a.k = (char*)d.qkv + D * qes(prec); a.v = (char*)d.qkv + 2 * D * qes(prec);
-    a.kv_batch_stride = T * 3 * D; a.kv_row_stride = 3 * D;
-    a.B = B; a.H = w->heads; a.Tq = T; a.Tk = T; a.mask = KX_ATTN_CAUSAL; a.prec = (qkv_hl && !st1) ? KX_PREC_F16CHL : aprec(prec);
-    a.out = d.att; a.out_batch_stride = T * D * kmul(prec); a.out_row_stride = D * kmul(prec); a.odt = ct;
+    const bool hl = qkv_hl && !st1;
+    Gemm q{d.h, D, fold ? L.wqkv_f : L.wqkv, D, d.qkv, 3 * D, hl ? KX_F16HL : qdt(prec), M, 3 * D};
+    q.bias = fold ? L.bqkv_f : L.bqkv; q.qscale = 0.125f; q.qcols = D; q.family = FAM_QKV;
+    // ([*, 32] tables: row m % T of those from row P)
+    q.xq_cs = w->xpos ? xq_cs + xo : nullptr; q.xq_ss = xq_ss + xo; q.xk_cs = xk_cs + xo; q.xk_ss = xk_ss + xo;
+    if (w->xpos) { q.xT = T; q.xdim = D; }
+    if (st1) { q.row_stats = d.stats2; q.colsum = L.wqkv_colsum; }
+    KX_TRY(st.gemm(q));
+    if (kcache && P == 0)     // incremental decoding: keep this layer's (XPos-rotated) keys and values
+      KX_TRY(kx_launch_kv_prefill(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, B, T, D, Tmax, prec, s));
+    // inner_attn_ln folded into out_proj (sub-LN): the attention kernel emits per-(row, head) partial statistics, the GEMM
+    // multiplies the un-normalised output by γ⊙Wo and applies rstd·(acc − mean·colsum) + (β·Woᵀ + bo) in its epilogue
+    kx_attn_args a = packed_qkv_attention(d.qkv, d.att, B, w->heads, T, D, KX_ATTN_CAUSAL, prec);
+    if (hl) a.prec = KX_PREC_F16CHL;
+    if (w->subln) a.stats_out = d.partials;
     // the layer's attention: the prefill's causal launch, or over the P cached rows (which appends the new keys and values itself)
-    auto attend = [&]() -> int {
-      if (P == 0) return kx_attention(&a, stream);
-      const size_t layer_bytes = (size_t)B * Tmax * D * qes(prec);
-      return kx_attention_extend(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct, a.stats_out, B,
-                                 w->heads, T, P, Tmax, aprec(prec), stream);
-    };
+    if (P == 0) KX_TRY(kx_attention(&a, stream));
+    else KX_TRY(kx_attention_extend(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct, a.stats_out, B,
+                                    w->heads, T, P, Tmax, aprec(prec), stream));
+    // The residual GEMMs' RowFusion: with the row-owning reduce (fuse_*) it writes the LayerNorm that follows and takes the sub-LN
+    // statistics straight from the partials; without it (row_stats_scratch + stats_partials) kx_gemm finalises the partials inside
+    // the pair-split launch where it takes that, else runs kx_row_stats_finalize into d.stats itself.
     RowFusion ro, r2;
-    ro.ln_out = d.h; ro.ln_dt = ct; ro.ln_g = L.fl_g; ro.ln_b = L.fl_b; ro.eps = w->eps;
+    ro.eps = r2.eps = w->eps;
+    if (fuse_o) { ro.ln_out = d.h; ro.ln_dt = ct; ro.ln_g = L.fl_g; ro.ln_b = L.fl_b; }
+    Gemm o{d.att, D, L.wo, D, x, D, KX_F32, M, D};
+    o.bias = L.bo; o.residual = x; o.family = FAM_OUT_PROJ;
     if (w->subln) {
-      // inner_attn_ln folded into out_proj: the attention kernel emits per-(row, head) partial statistics, the GEMM
-      // multiplies the un-normalised output by γ⊙Wo and applies rstd·(acc − mean·colsum) + (β·Woᵀ + bo) in its epilogue
-      a.stats_out = d.partials;
-      KX_TRY(attend());
-      if (fuse_o) {
-        ro.partials = d.partials; ro.nseg = w->heads; ro.seg = 64;
-        KX_FAM(1);
-        KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                    0, 0, nullptr, L.wo_colsum, nullptr, &ro));
-      } else {
-        // (row_stats_scratch + stats_partials: kx_gemm finalises the partials inside the pair-split launch where it takes that, else
-        //  runs kx_row_stats_finalize into d.stats itself)
-        RowFusion fo; fo.partials = d.partials; fo.nseg = w->heads; fo.seg = 64; fo.eps = w->eps; fo.scratch = d.stats;
-        KX_FAM(1);
-        KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                    0, 0, nullptr, L.wo_colsum, nullptr, &fo, fold ? &lop : nullptr));
-      }
-    } else {
-      KX_TRY(attend());
-      KX_FAM(1);
-      KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr, 0,
-                  0, nullptr, nullptr, nullptr, fuse_o ? &ro : nullptr, fold ? &lop : nullptr));
+      ro.partials = d.partials; ro.nseg = w->heads; ro.seg = 64;
+      if (!fuse_o) ro.scratch = d.stats;
+      o.colsum = L.wo_colsum;
     }
+    if (w->subln || fuse_o) o.rf = &ro;
+    if (fold) o.lo = &lop;
+    KX_TRY(st.gemm(o));
     // x = x + fc2(ffn_layernorm(gelu(fc1(final_layer_norm(x)))))
     if (fold) KX_TRY(kx_row_stats_finalize(d.partials2, M, D / 64, 64, w->eps, d.stats2, stream));
     else if (!fuse_o) KX_TRY(ln(x, nullptr, L.fl_g, L.fl_b, d.h, ct, M, D, w->eps, s));
-    const bool last = i + 1 == w->layers;
-    r2.ln_out = d.h; r2.ln_dt = ct; r2.eps = w->eps;
-    r2.ln_g = last ? w->ln_g : w->layer[i + 1].sa_g; r2.ln_b = last ? w->ln_b : w->layer[i + 1].sa_b;
-    const void* w1 = fold ? L.w1_f : L.w1;
-    const float* b1 = fold ? L.b1_f : L.b1;
-    const float* rs1 = fold ? d.stats2 : nullptr;
-    const float* cs1 = fold ? L.w1_colsum : nullptr;
-    if (w->subln) {
-      // ffn_layernorm folded into fc2 the same way; fc1's epilogue emits the row statistics of gelu(fc1)
-      KX_FAM(2);
-      KX_TRY(gemm(d.h, D, w1, D, d.g, F, ct, M, F, b1, nullptr, w->act, 1.f, 0, prec, s, nullptr, nullptr, nullptr,
-                  nullptr, 0, 0, rs1, cs1, d.partials));
-      if (fuse_2) {
-        r2.partials = d.partials; r2.nseg = F / 64; r2.seg = 64;
-        KX_FAM(3);
-        KX_TRY(gemm(d.g, F, L.w2, F, x, D, KX_F32, M, D, L.b2, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                    0, 0, nullptr, L.w2_colsum, nullptr, &r2));
-      } else {
-        RowFusion f2; f2.partials = d.partials; f2.nseg = F / 64; f2.seg = 64; f2.eps = w->eps; f2.scratch = d.stats;
-        KX_FAM(3);
-        KX_TRY(gemm(d.g, F, L.w2, F, x, D, KX_F32, M, D, L.b2, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                    0, 0, nullptr, L.w2_colsum, nullptr, &f2, fold ? &lop : nullptr));
-      }
-    } else {
-      KX_FAM(2);
-      KX_TRY(gemm(d.h, D, w1, D, d.g, F, ct, M, F, b1, nullptr, w->act, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                  0, 0, rs1, cs1));
-      KX_FAM(3);
-      KX_TRY(gemm(d.g, F, L.w2, F, x, D, KX_F32, M, D, L.b2, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                  nullptr, nullptr, nullptr, fuse_2 ? &r2 : nullptr, fold ? &lop : nullptr));
+    Gemm f1{d.h, D, fold ? L.w1_f : L.w1, D, d.g, F, ct, M, F};
+    f1.bias = fold ? L.b1_f : L.b1; f1.act = w->act; f1.family = FAM_FC1;
+    if (fold) { f1.row_stats = d.stats2; f1.colsum = L.w1_colsum; }
+    if (w->subln) f1.stats_out = d.partials;   // ffn_layernorm folded into fc2 the same way: fc1's epilogue emits the row statistics of gelu(fc1)
+    KX_TRY(st.gemm(f1));
+    if (fuse_2) {
+      const bool last = i + 1 == w->layers;
+      r2.ln_out = d.h; r2.ln_dt = ct;
+      r2.ln_g = last ? w->ln_g : w->layer[i + 1].sa_g; r2.ln_b = last ? w->ln_b : w->layer[i + 1].sa_b;
     }
+    Gemm f2{d.g, F, L.w2, F, x, D, KX_F32, M, D};
+    f2.bias = L.b2; f2.residual = x; f2.family = FAM_FC2;
+    if (w->subln) {
+      r2.partials = d.partials; r2.nseg = F / 64; r2.seg = 64;
+      if (!fuse_2) r2.scratch = d.stats;
+      f2.colsum = L.w2_colsum;
+    }
+    if (w->subln || fuse_2) f2.rf = &r2;
+    if (fold) f2.lo = &lop;
+    KX_TRY(st.gemm(f2));
     if (fold) KX_TRY(kx_row_stats_finalize(d.partials2, M, D / 64, 64, w->eps, d.stats2, stream));
     h_ready = fuse_2;                                     // d.h = the next layer's (or the final) LayerNorm of x
   }
   if (!need_logits) return KX_OK;                         // (an extend whose rows nobody reads: the caches are what it was for)
-  if (fold) {                                             // decoder.layer_norm folded into the output projection
-    KX_FAM(4);
-    KX_TRY(gemm(d.h, D, w->wout_f, D, logits, w->vocab, ldt, M, w->vocab, w->bout_f, nullptr, 0, 1.f, 0, prec, s, nullptr,
-                nullptr, nullptr, nullptr, 0, 0, d.stats2, w->wout_colsum));
-    return KX_OK;
-  }
-  if (!h_ready) KX_TRY(ln(x, nullptr, w->ln_g, w->ln_b, d.h, ct, M, D, w->eps, s));
-  KX_FAM(4);
-  KX_TRY(gemm(d.h, D, w->wout, D, logits, w->vocab, ldt, M, w->vocab, nullptr, nullptr, 0, 1.f, 0, prec, s));
-  return KX_OK;
+  if (!fold && !h_ready) KX_TRY(ln(x, nullptr, w->ln_g, w->ln_b, d.h, ct, M, D, w->eps, s));
+  Gemm lg{d.h, D, fold ? w->wout_f : w->wout, D, logits, w->vocab, ldt, M, w->vocab};
+  lg.family = FAM_LOGITS;
+  if (fold) { lg.bias = w->bout_f; lg.row_stats = d.stats2; lg.colsum = w->wout_colsum; }   // decoder.layer_norm folded into the output projection
+  return st.gemm(lg);
 }
 
 extern "C" int kx_decoder_forward(const kx_decoder_weights* w, float* x, int64_t B, int64_t T, const float* xq_cs,
@@ -756,7 +746,8 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     return KX_ERR_WORKSPACE;
   }
   const int64_t M = B, D = w->dim, F = w->ffn;
-  KX_SPLITK_SCOPE(d.splitk, s);
+  const Stage st(s, prec, d.splitk);
+  KX_TRY(st.clear_words());
   const int ct = cdt(prec);
   const size_t es = esz(prec);
   const size_t layer_bytes = (size_t)(r.cache_seq ? r.Bc : r.K > 0 ? B / r.K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
@@ -827,40 +818,38 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     const kx_decoder_layer& L = w->layer[i];
     KX_TRY(ln(x, nullptr, L.sa_g, L.sa_b, d.h, ct, M, D, w->eps, s));
     // XPos rows of absolute position t (xpos_T = 1: every batch row is the same position; ragged: xpos_T = B, row m its own)
-    KX_FAM(0);
-    KX_TRY(gemm(d.h, D, L.wqkv, D, d.qkv, 3 * D, qdt(prec), M, 3 * D, L.bqkv, nullptr, 0, 0.125f, D, prec, s,
-                w->xpos ? xq_cs : nullptr, xq_ss, xk_cs, xk_ss, w->xpos ? xT : 0, w->xpos ? D : 0));
+    Gemm q{d.h, D, L.wqkv, D, d.qkv, 3 * D, qdt(prec), M, 3 * D};
+    q.bias = L.bqkv; q.qscale = 0.125f; q.qcols = D; q.family = FAM_QKV;
+    q.xq_cs = w->xpos ? xq_cs : nullptr; q.xq_ss = xq_ss; q.xk_cs = xk_cs; q.xk_ss = xk_ss;
+    if (w->xpos) { q.xT = xT; q.xdim = D; }
+    KX_TRY(st.gemm(q));
     KX_TRY(step_attention(r, d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
                           w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream));
+    // sub-LN: the folded inner_attn_ln / ffn_layernorm statistics are finalised by a launch of their own here
+    Gemm o{d.att, D, L.wo, D, x, D, KX_F32, M, D};
+    o.bias = L.bo; o.residual = x; o.family = FAM_OUT_PROJ;
     if (w->subln) {
       KX_TRY(kx_row_stats_finalize(d.partials, M, w->heads, 64, w->eps, d.stats, stream));
-      KX_FAM(1);
-      KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                  0, 0, d.stats, L.wo_colsum, nullptr));
-    } else {
-      KX_FAM(1);
-      KX_TRY(gemm(d.att, D, L.wo, D, x, D, KX_F32, M, D, L.bo, x, 0, 1.f, 0, prec, s));
+      o.row_stats = d.stats; o.colsum = L.wo_colsum;
     }
+    KX_TRY(st.gemm(o));
     KX_TRY(ln(x, nullptr, L.fl_g, L.fl_b, d.h, ct, M, D, w->eps, s));
+    Gemm f1{d.h, D, L.w1, D, d.g, F, ct, M, F};
+    f1.bias = L.b1; f1.act = w->act; f1.family = FAM_FC1;
+    if (w->subln) f1.stats_out = d.partials;
+    KX_TRY(st.gemm(f1));
+    Gemm f2{d.g, F, L.w2, F, x, D, KX_F32, M, D};
+    f2.bias = L.b2; f2.residual = x; f2.family = FAM_FC2;
     if (w->subln) {
-      KX_FAM(2);
-      KX_TRY(gemm(d.h, D, L.w1, D, d.g, F, ct, M, F, L.b1, nullptr, w->act, 1.f, 0, prec, s, nullptr, nullptr, nullptr,
-                  nullptr, 0, 0, nullptr, nullptr, d.partials));
       KX_TRY(kx_row_stats_finalize(d.partials, M, F / 64, 64, w->eps, d.stats, stream));
-      KX_FAM(3);
-      KX_TRY(gemm(d.g, F, L.w2, F, x, D, KX_F32, M, D, L.b2, x, 0, 1.f, 0, prec, s, nullptr, nullptr, nullptr, nullptr,
-                  0, 0, d.stats, L.w2_colsum, nullptr));
-    } else {
-      KX_FAM(2);
-      KX_TRY(gemm(d.h, D, L.w1, D, d.g, F, ct, M, F, L.b1, nullptr, w->act, 1.f, 0, prec, s));
-      KX_FAM(3);
-      KX_TRY(gemm(d.g, F, L.w2, F, x, D, KX_F32, M, D, L.b2, x, 0, 1.f, 0, prec, s));
+      f2.row_stats = d.stats; f2.colsum = L.w2_colsum;
     }
+    KX_TRY(st.gemm(f2));
   }
   KX_TRY(ln(x, nullptr, w->ln_g, w->ln_b, d.h, ct, M, D, w->eps, s));
-  KX_FAM(4);
-  KX_TRY(gemm(d.h, D, w->wout, D, logits, w->vocab, ldt, M, w->vocab, nullptr, nullptr, 0, 1.f, 0, prec, s));
-  return KX_OK;
+  Gemm lg{d.h, D, w->wout, D, logits, w->vocab, ldt, M, w->vocab};
+  lg.family = FAM_LOGITS;
+  return st.gemm(lg);
 }
 
 extern "C" int kx_decoder_decode_step(const kx_decoder_weights* w, float* x, int64_t B, int64_t t, const float* xq_cs,

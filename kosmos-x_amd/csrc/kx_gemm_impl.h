@@ -64,7 +64,7 @@ struct GemmParams {
   // word the host reads with kx_pair_split_errors().  The launch then completes with WRONG rows instead of hanging the
   // GPU.  pk_fault (tuning key 13 = 2, tests only): workgroups with an odd pair index never publish, spin bound 2 ms.
   unsigned* pk_err; unsigned pk_spin_ticks; int pk_fault;
-  // In-launch split-K reduction of the 64 x 64 kernel (kx_gemm_args.splitk_counter, ABI 7; "coop"): every (tile, K slice)
+  // In-launch split-K reduction of the 64 x 64 kernel (kx_gemm_args.splitk_flags, ABI 7; "coop"): every (tile, K slice)
   // workgroup writes its partial tile write-through, drains, and stores the launch's epoch (pk_epoch) into its own word of
   // coop_flags [workgroups]; the LAST M workgroups in dispatch order then wait until every word shows the epoch (bounded poll,
   // pk_err) and each reduces ONE whole output row with the row-owning reduce's arithmetic — slices in slice order, epilogue, the LayerNorm that follows.  One
