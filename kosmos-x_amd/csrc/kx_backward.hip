@@ -1818,13 +1818,13 @@ extern "C" int kx_attention_backward(const void* qv_, const void* kv_, const voi
   KX_REQUIRE(qkv_row_stride % 4 == 0 && out_row_stride % 4 == 0 && qkv_batch_stride % 4 == 0 && out_batch_stride % 4 == 0 &&
                  (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) == 0,
              "kx_attention_backward: pointers and strides must keep 16-byte alignment");
+  KX_REQUIRE(prec == KX_PREC_F32 || prec == KX_PREC_BF16, "kx_attention_backward: products in fp32 or bf16");   // before the first launch
   hipStream_t s = (hipStream_t)stream;
   KxProfScope prof(KX_K_ATTN_F32, B * H, T, -T, s);
   const long long nw = (long long)B * T * H;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, out, dout, delta, (int)B, (int)T,
                      (int)H, (long long)out_row_stride, (long long)out_batch_stride);
   const dim3 grid((unsigned)((T + 63) / 64), (unsigned)H, (unsigned)B);
-  KX_REQUIRE(prec == KX_PREC_F32 || prec == KX_PREC_BF16, "kx_attention_backward: products in fp32 or bf16");
   if (prec == KX_PREC_BF16) {                                      // bf16 products, fp32 inputs / statistics / accumulators
     const dim3 gridh((unsigned)H, (unsigned)((T + 63) / 64), (unsigned)B);      // head fastest: XCD-local Q / dO / K / V tiles
 #define KX_ATTN_BWD_B(CAUSAL, QT)                                                                                      \
