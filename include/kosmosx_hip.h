@@ -871,6 +871,37 @@ int kx_decoder_extend(const kx_decoder_weights* w, float* x, int64_t B, int64_t 
                       void* workspace, size_t workspace_bytes, int32_t prec, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged extend: the chunked prefill above with a per-sequence P on the DEVICE (added within ABI 7: functions only).  positions
+ * int32 [B]: sequence b already holds positions[b] = P_b cache rows; its Tn new rows are positions P_b .. P_b + Tn - 1.  Tn is one
+ * host value for the whole batch.  Nothing is read back to the host.
+ *
+ * kx_attention_extend_ragged: kx_attention_extend's operands, append and launch (same grid, same tiles, same order of sums), with P
+ *   and Tk = P + Tn loaded once per workgroup from positions[b].  Sequence b of the launch gives, bit for bit in all three
+ *   precisions, what a B = 1 kx_attention_extend launch at P = P_b gives: outputs, statistics and cache rows.
+ *   Guard (as kx_attention_decode_block): a sequence with P_b < 0 or P_b + Tn > Tmax writes nothing — no output row, no statistics,
+ *   no cache row, in the append or in the attention — and ORs KX_RAGGED_ERR_CACHE into *error_word (int32, device, sticky; the
+ *   caller clears it).  The other sequences are unaffected.
+ *   KX_ERR_INVALID_ARG and nothing launched: kx_attention_extend's refusals (with Tn > Tmax for the range), null positions or
+ *   error_word.  Both cache layouts (tuning key 9).
+ * kx_decoder_extend_ragged: kx_decoder_extend for rows that are still token ids.  Row (b, i) is embedded as kx_step_prepare embeds a
+ *   row at position positions[b] + i (pos_shift as there) into x [B, T, dim] fp32 (workspace of the caller, consumed), and its
+ *   four XPos rows are gathered from the FULL [Tmax, 32] tables into xpos_rows [4, B * T, 32] (caller scratch; the qkv GEMM reads
+ *   them with xpos_T = B * T); then the layers, with kx_attention_extend_ragged.  A row whose position leaves the position table
+ *   or the XPos tables sets KX_RAGGED_ERR_TABLE and is not embedded, a sequence that leaves the cache KX_RAGGED_ERR_CACHE: its
+ *   logits rows are then undefined, the other sequences' are not touched by it.  logits [B, T, vocab], or NULL: the call ends
+ *   after the last layer.  Workspace: kx_decoder_workspace_bytes(w, B, T, prec).  Precisions: bf16, fp32, f16c.
+ * ------------------------------------------------------------------------------------------ */
+int kx_attention_extend_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                               int64_t B, int64_t H, int64_t Tn, const int32_t* positions, int64_t Tmax, int32_t prec,
+                               int32_t* error_word, void* stream);
+int kx_decoder_extend_ragged(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                             int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t B, int64_t T,
+                             const int32_t* positions, const float* xq_cs, const float* xq_ss, const float* xk_cs,
+                             const float* xk_ss, float* xpos_rows, void* logits, int32_t ldt, void* kcache, void* vcache,
+                             int64_t Tmax, void* workspace, size_t workspace_bytes, int32_t prec, int32_t* error_word,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host pre-processing, tensor half: what KosmosTokenizer does to images and token ids before
  * Kosmos.forward, on the device.  Integer / byte work; results are bit-identical to the HF processor.
  * ------------------------------------------------------------------------------------------ */

@@ -43,18 +43,40 @@ struct AttnParams {
   // the EXT instantiations only (kx_attention_extend; appended, so the other kernels' argument offsets stay): k / v are a KV cache
   // whose head h starts khs elements after the sequence's base (the others: h * 64), and query i is the sequence's row P + i
   long long khs; int P;
+  // the ragged EXT instantiations only (kx_attention_extend_ragged; appended again): sequence b holds positions[b] rows instead of P,
+  // checked against Tmax in the kernel (err: the sticky error word)
+  const int* positions; int* err; int Tmax;
 };
 
 // EXT (kx_attention_extend): the causal kernels over a KV cache that already holds P rows.  Tq new queries, Tk = P + Tq keys read
 // from the cache (head stride p.khs); query i sits at sequence position P + i, so P enters the causal tile count, the per-wave /
 // per-block "tile has work" tests and the mask compare.  Without EXT both fold to h * 64 and 0: the same instructions as before.
-template <bool EXT> __device__ __forceinline__ long long kv_head_off(const AttnParams& p, int h) {
-  if constexpr (EXT) return (long long)h * p.khs;
+// EXT = KX_EXT_RAGGED (kx_attention_extend_ragged): the same with P = positions[blockIdx.z], one scalar load per workgroup, and
+// Tk = P + Tq derived from it in the kernel: P and Tk are workgroup-uniform values, and everything after the two helpers below is
+// the same code on them, so a sequence gives the bits of the uniform launch at its P.  A sequence whose rows leave [0, Tmax) is the
+// caller's error: its workgroups return before any barrier, having written nothing, and set KX_RAGGED_ERR_CACHE in the sticky word.
+// The other two values keep p.P / p.Tk (0 / p.Tk): their instantiations keep their code.
+enum : int { KX_EXT_NONE = 0, KX_EXT_UNIFORM = 1, KX_EXT_RAGGED = 2 };
+template <int EXT> __device__ __forceinline__ long long kv_head_off(const AttnParams& p, int h) {
+  if constexpr (EXT != KX_EXT_NONE) return (long long)h * p.khs;
   else return (long long)h * 64;
 }
-template <bool EXT> __device__ __forceinline__ int q_shift(const AttnParams& p) {
-  if constexpr (EXT) return p.P;
+template <int EXT> __device__ __forceinline__ int q_shift(const AttnParams& p) {
+  if constexpr (EXT == KX_EXT_RAGGED) return p.positions[blockIdx.z];
+  else if constexpr (EXT == KX_EXT_UNIFORM) return p.P;
   else return 0;
+}
+template <int EXT> __device__ __forceinline__ int key_rows(const AttnParams& p, int P) {
+  if constexpr (EXT == KX_EXT_RAGGED) return P + p.Tq;
+  else return p.Tk;
+}
+// (uniform over the workgroup: nobody reaches a barrier; host-checked 1 <= Tq <= Tmax, so the compare cannot overflow)
+__device__ __forceinline__ bool ragged_rows_outside(const AttnParams& p, int P) {
+  if ((P < 0) | (P > p.Tmax - p.Tq)) {
+    if (threadIdx.x == 0) atomicOr(p.err, KX_RAGGED_ERR_CACHE);
+    return true;
+  }
+  return false;
 }
 
 constexpr int KSTR = 72;  // LDS row stride (elements) for the 64-wide K / Vᵀ tiles: 144 B, 16-B aligned rows
@@ -236,12 +258,14 @@ __device__ __forceinline__ unsigned pack16x2(float lo, float hi) { return F16 ? 
 // unchanged), O^T += V^T P^T takes the kept ones, 1 / (1 - p) goes into the final 1 / l; mask bits from kx_dropout.h, one
 // Philox block per (query, four keys) = per accumulator register quadruple (two when Tk % 4 != 0: the rows of the mask then
 // do not start on block boundaries).
-template <bool CAUSAL, bool F16 = false, bool FOLD = false, bool DROP = false, bool EXT = false>
+template <bool CAUSAL, bool F16 = false, bool FOLD = false, bool DROP = false, int EXT = KX_EXT_NONE>
 __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const AttnParams p) {
   static_assert(!(CAUSAL && FOLD), "the tail fold is for unmasked launches (causal blocks are paired instead)");
   static_assert(!EXT || (CAUSAL && !F16 && !FOLD && !DROP), "EXT: the causal bf16 forward kernel over a KV cache");
   static_assert(!(DROP && (F16 || FOLD)), "attention dropout: the bf16 training kernel");
   const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
+  if constexpr (EXT == KX_EXT_RAGGED) { if (ragged_rows_outside(p, P)) return; }
+  const int Tk = key_rows<EXT>(p, P);                        // (ragged EXT: P + Tq; else p.Tk)
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2][64 * 64];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[2][64 * VSTR];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -283,7 +307,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
     for (int d = 0; d < 4; ++d) ot[qb][d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   }
 
-  int ntiles = (p.Tk + 63) >> 6;
+  int ntiles = (Tk + 63) >> 6;
   if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 127, p.Tq - 1) + P) >> 6) + 1);
 
   // cooperative tile loads: thread owns chunks c = tid, tid+256 -> (row c>>3, 16-B part c&7)
@@ -293,7 +317,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int c = tid + 256 * j, row = c >> 3, part = c & 7;
-      const long long off = (long long)min(t * 64 + row, p.Tk - 1) * p.krs + part * 8;
+      const long long off = (long long)min(t * 64 + row, Tk - 1) * p.krs + part * 8;
       kreg[j] = *reinterpret_cast<const u32x4_t*>(kp + off);
       vreg[j] = *reinterpret_cast<const u32x4_t*>(vp + off);
     }
@@ -334,7 +358,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
       }
       // ---- online softmax per query block (query = lane&15; its keys sit in 4 lanes x 16 registers) ----
       // Masking is needed only on the tile that holds the sequence end or crosses this wave's diagonal (wave-uniform).
-      const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qw0 + P);
+      const bool need_mask = (kv0 + 63 >= Tk) || (CAUSAL && kv0 + 63 > qw0 + P);
       // Tile 0 holds key 0, which no mask removes (causal: key 0 <= every query), so the running maximum is finite
       // from the first tile on and exp2(-inf - finite) = 0 covers the start: no -inf guard in the chain.
       u32x4_t pf[2][2];
@@ -349,7 +373,7 @@ __global__ __launch_bounds__(FOLD ? 320 : 256, 2) void attn_bf16_v2_kernel(const
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = kv0 + kb * 16 + 4 * g + r;
-              const bool ok = key < p.Tk && (!CAUSAL || key <= qi);
+              const bool ok = key < Tk && (!CAUSAL || key <= qi);
               st[qb][kb][r] = ok ? st[qb][kb][r] : -INFINITY;
             }
         }
@@ -531,10 +555,12 @@ __device__ __forceinline__ f32x4_t mma_f16(u32x4_t a, u32x4_t b, f32x4_t c) {
 // one and a half tiles of the block's last two instead of waves 0-1 one and waves 2-3 two (T = 114: 6 wave-tiles in 1.5 tile
 // times instead of 2).  Per query nothing changes — same tiles in the same order, a skipped tile is one whose every score was
 // masked (alpha = 1, p = 0 exactly): bit-identical to the consecutive mapping.
-template <bool CAUSAL, int PVS, bool HL = false, bool EXT = false>
+template <bool CAUSAL, int PVS, bool HL = false, int EXT = KX_EXT_NONE>
 __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
   static_assert(!EXT || (CAUSAL && PVS == 1 && !HL), "EXT: the causal split-fp16 kernel on fp32 rows over a KV cache");
   const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
+  if constexpr (EXT == KX_EXT_RAGGED) { if (ragged_rows_outside(p, P)) return; }
+  const int Tk = key_rows<EXT>(p, P);                        // (ragged EXT: P + Tq; else p.Tk)
   __shared__ __attribute__((aligned(16))) unsigned short Kh[2][64 * 64], Kl[2][64 * 64];
   __shared__ __attribute__((aligned(16))) unsigned short Vh[2][64 * VSTR], Vl[2][64 * VSTR];
   constexpr float SC = 256.0f;                               // operand pre-scale (see above)
@@ -580,7 +606,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) ot[qb][d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   }
-  int ntiles = (p.Tk + 63) >> 6;
+  int ntiles = (Tk + 63) >> 6;
   if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 127, p.Tq - 1) + P) >> 6) + 1);
 
   // cooperative tile loads: thread owns (row c>>3, 8-value part c&7) for c = tid, tid + 256: two float4 each of K and V
@@ -592,13 +618,13 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
     for (int j = 0; j < 2; ++j) {
       const int c = tid + 256 * j, row = c >> 3, part = c & 7;
       if constexpr (HL) {       // [0] = the eight hi pieces of values 8 part .. + 7, [1] = their lo pieces
-        const long long off = (long long)min(t * 64 + row, p.Tk - 1) * p.krs;
+        const long long off = (long long)min(t * 64 + row, Tk - 1) * p.krs;
         const char* ks_ = reinterpret_cast<const char*>(kp + off) + part * 16;
         const char* vs_ = reinterpret_cast<const char*>(vp + off) + part * 16;
         kpc[j][0] = *reinterpret_cast<const u32x4_t*>(ks_); kpc[j][1] = *reinterpret_cast<const u32x4_t*>(ks_ + 128);
         vpc[j][0] = *reinterpret_cast<const u32x4_t*>(vs_); vpc[j][1] = *reinterpret_cast<const u32x4_t*>(vs_ + 128);
       } else {
-      const long long off = (long long)min(t * 64 + row, p.Tk - 1) * p.krs + part * 8;
+      const long long off = (long long)min(t * 64 + row, Tk - 1) * p.krs + part * 8;
       kreg[j][0] = *reinterpret_cast<const float4*>(kp + off); kreg[j][1] = *reinterpret_cast<const float4*>(kp + off + 4);
       vreg[j][0] = *reinterpret_cast<const float4*>(vp + off); vreg[j][1] = *reinterpret_cast<const float4*>(vp + off + 4);
       }
@@ -671,7 +697,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
       constexpr float L2S = 1.44269504088896340736f / (SC * SC);     // exp(S) = exp2(S' * log2e / 2^16)
 #pragma unroll
       for (int qb = Q0; qb < 2; ++qb) {
-        const bool need_mask = (kv0 + 63 >= p.Tk) || (CAUSAL && kv0 + 63 > qrow[qb] + P);
+        const bool need_mask = (kv0 + 63 >= Tk) || (CAUSAL && kv0 + 63 > qrow[qb] + P);
         if (need_mask) {
           const int qi = qrow[qb] + li + P;
 #pragma unroll
@@ -679,7 +705,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16s_kernel(const AttnParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = kv0 + kb * 16 + 4 * g + r;
-              const bool ok = key < p.Tk && (!CAUSAL || key <= qi);
+              const bool ok = key < Tk && (!CAUSAL || key <= qi);
               st[qb][kb][r] = ok ? st[qb][kb][r] : -INFINITY;
             }
         }
@@ -879,10 +905,12 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
 // 16 queries per wave, 64 per workgroup.  k-slice map of S^T = K Q^T: slice g <-> head dims 16g + s (s = MFMA step),
 // so a lane's 16 operand values are contiguous: 4 x 16-byte reads of its key row / query row.
 // Replaces the wave-per-query VALU kernel below as the default (36 -> a few ms of a 150 ms fp32-mode step).
-template <bool CAUSAL, bool EXT = false>
+template <bool CAUSAL, int EXT = KX_EXT_NONE>
 __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) {
   static_assert(!EXT || CAUSAL, "EXT: the causal kernel over a KV cache");
   const int P = q_shift<EXT>(p);                             // (EXT: rows the cache held before this launch; else 0)
+  if constexpr (EXT == KX_EXT_RAGGED) { if (ragged_rows_outside(p, P)) return; }
+  const int Tk = key_rows<EXT>(p, P);                        // (ragged EXT: P + Tq; else p.Tk)
   constexpr int PITCH = 68;                                  // floats per LDS row (272 B: 16-byte aligned, bank-skewed)
   __shared__ __attribute__((aligned(16))) float Ks[64 * PITCH];
   __shared__ __attribute__((aligned(16))) float Vs[64 * PITCH];
@@ -908,7 +936,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
 #pragma unroll
   for (int d = 0; d < 4; ++d) ot[d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
-  int ntiles = (p.Tk + 63) >> 6;
+  int ntiles = (Tk + 63) >> 6;
   if (CAUSAL) ntiles = min(ntiles, ((min(qblk0 + 63, p.Tq - 1) + P) >> 6) + 1);
 
   for (int t = 0; t < ntiles; ++t) {
@@ -919,7 +947,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
       const int c = tid + 256 * j, row = c >> 4, part = c & 15;
       const int key = kv0 + row;
       float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-      if (key < p.Tk) {
+      if (key < Tk) {
         kk = *reinterpret_cast<const float4*>(kp + (long long)key * p.krs + part * 4);
         vv = *reinterpret_cast<const float4*>(vp + (long long)key * p.krs + part * 4);
       }
@@ -948,7 +976,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnParams p) 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kv0 + kb * 16 + 4 * g + r;
-        const bool ok = key < p.Tk && (!CAUSAL || key <= qi + P);
+        const bool ok = key < Tk && (!CAUSAL || key <= qi + P);
         st[kb][r] = ok ? (CAUSAL ? score_nan_to_num(st[kb][r]) : st[kb][r]) : -INFINITY;
         mloc = fmaxf(mloc, st[kb][r]);
       }
@@ -1357,11 +1385,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
 }
 
 // prefill: copy the k and v column blocks of the fused qkv rows [B*T, 3D] into rows [row0, row0 + T) of the caches [B, Tmax, D]
-template <typename T>
+// R = RaggedParams (kx_attention_extend_ragged): sequence b's rows go to [positions[b], positions[b] + T) instead; a sequence whose
+// rows leave [0, Tmax) writes nothing and sets KX_RAGGED_ERR_CACHE.  The empty pack is the launch it always was.
+template <typename T, typename... R>
 __global__ __launch_bounds__(256) void kv_prefill_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                          int Tlen, int D, long long cache_batch, long long cache_head,
-                                                         long long cache_row, int row0) {
+                                                         long long cache_row, int row0, const R... r) {
   const long long row = blockIdx.x;                       // b*T + i
+  if constexpr (sizeof...(R) != 0) {
+    const RaggedParams& rp = first_arg(r...);
+    row0 = rp.positions[row / Tlen];
+    if ((row0 < 0) | (row0 > rp.Tmax - Tlen)) {            // (uniform over the workgroup)
+      if (threadIdx.x == 0) atomicOr(rp.err, KX_RAGGED_ERR_CACHE);
+      return;
+    }
+  }
   const long long b = row / Tlen, t = row0 + row % Tlen;
   const uint4* src = reinterpret_cast<const uint4*>(qkv + row * 3 * D);
   constexpr int EPV = 16 / sizeof(T);
@@ -1377,11 +1415,19 @@ __global__ __launch_bounds__(256) void kv_prefill_kernel(const T* __restrict__ q
 }  // namespace
 
 int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t T, int64_t D, int64_t Tmax, int prec,
-                         hipStream_t s, int64_t row0) {
+                         hipStream_t s, int64_t row0, const int32_t* positions, int32_t* err) {
   KxProfScope prof(KX_K_MISC, B * T, D, 4, s);
   const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;
   const long long ch = head_major ? Tmax * 64 : 64, cr = head_major ? 64 : D;
-  if (prec == KX_PREC_BF16)
+  if (positions) {                                        // per-sequence row offsets from the device (row0 unused)
+    const RaggedParams r{positions, err, (int)Tmax};
+    if (prec == KX_PREC_BF16)
+      hipLaunchKernelGGL((kv_prefill_kernel<bf16_t, RaggedParams>), dim3((unsigned)(B * T)), dim3(256), 0, s, (const bf16_t*)qkv,
+                         (bf16_t*)kc, (bf16_t*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr, 0, r);
+    else
+      hipLaunchKernelGGL((kv_prefill_kernel<float, RaggedParams>), dim3((unsigned)(B * T)), dim3(256), 0, s, (const float*)qkv,
+                         (float*)kc, (float*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr, 0, r);
+  } else if (prec == KX_PREC_BF16)
     hipLaunchKernelGGL(kv_prefill_kernel<bf16_t>, dim3((unsigned)(B * T)), dim3(256), 0, s, (const bf16_t*)qkv,
                        (bf16_t*)kc, (bf16_t*)vc, (int)T, (int)D, (long long)(Tmax * D), ch, cr, (int)row0);
   else
@@ -1394,20 +1440,23 @@ int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t
 // Attention of Tn new rows per sequence over a cache that holds P: the append (its own launch, so every key — the new rows' too —
 // is then read from the cache alone), and the EXT instantiation of the precision's causal flash kernel: the prefill's grid
 // (query-block pairs (x, nx-1-x) over the Tn queries), key tiles from 0, the mask's diagonal at key P + i.
-extern "C" int kx_attention_extend(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out, int64_t B,
-                                   int64_t H, int64_t Tn, int64_t P, int64_t Tmax, int32_t prec, void* stream) {
-  KX_REQUIRE(qkv && kcache && vcache && out, "kx_attention_extend: null pointer");
-  KX_REQUIRE(B > 0 && H > 0 && B < 65536 && H < 65536, "kx_attention_extend: B/H empty or beyond the grid limits");
+// positions == nullptr: the uniform launch at host P; else the ragged launch (P unused): sequence b holds positions[b] rows, read on the
+// device by the append and by the KX_EXT_RAGGED instantiation — same grid, pairing, LDS and tile body.
+static int attention_extend_impl(const char* fn, const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                                 int64_t B, int64_t H, int64_t Tn, int64_t P, const int32_t* positions, int32_t* err, int64_t Tmax,
+                                 int32_t prec, void* stream) {
+  KX_REQUIRE(qkv && kcache && vcache && out, "%s: null pointer", fn);
+  KX_REQUIRE(B > 0 && H > 0 && B < 65536 && H < 65536, "%s: B/H empty or beyond the grid limits", fn);
   KX_REQUIRE(Tn >= 1 && P >= 0 && P + Tn <= Tmax && Tmax <= 0x7fffffffll,
-             "kx_attention_extend: rows %lld .. %lld outside the cache of %lld rows", (long long)P, (long long)(P + Tn - 1), (long long)Tmax);
-  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "kx_attention_extend: bad precision");
+             "%s: rows %lld .. %lld outside the cache of %lld rows", fn, (long long)P, (long long)(P + Tn - 1), (long long)Tmax);
+  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "%s: bad precision", fn);
   KX_REQUIRE(odt == KX_F32 || (prec == KX_PREC_F16C ? odt == KX_F16C : odt == KX_BF16),
-             "kx_attention_extend: the output is fp32, or bf16 (KX_PREC_BF16, KX_PREC_F32) / KX_F16C rows (KX_PREC_F16C)");
-  KX_REQUIRE(prec != KX_PREC_F32 || kx_tuning_get(KX_TUNE_ATTN_VARIANT) != 1, "kx_attention_extend: the first-version fp32 kernel (tuning key 2 = 1) has no cache form");
-  KX_REQUIRE((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out) & 15) == 0, "kx_attention_extend: pointers must be 16-byte aligned");
+             "%s: the output is fp32, or bf16 (KX_PREC_BF16, KX_PREC_F32) / KX_F16C rows (KX_PREC_F16C)", fn);
+  KX_REQUIRE(prec != KX_PREC_F32 || kx_tuning_get(KX_TUNE_ATTN_VARIANT) != 1, "%s: the first-version fp32 kernel (tuning key 2 = 1) has no cache form", fn);
+  KX_REQUIRE((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out) & 15) == 0, "%s: pointers must be 16-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   const int64_t D = H * 64;
-  KX_TRY(kx_launch_kv_prefill(qkv, kcache, vcache, B, Tn, D, Tmax, prec, s, P));
+  KX_TRY(kx_launch_kv_prefill(qkv, kcache, vcache, B, Tn, D, Tmax, prec, s, P, positions, err));
   const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;   // per sequence [H][Tmax][64]; tuning key 9 = 1: [Tmax][H*64]
   AttnParams p;
   memset(&p, 0, sizeof(p));
@@ -1417,17 +1466,37 @@ extern "C" int kx_attention_extend(const void* qkv, void* kcache, void* vcache, 
   const int64_t ors = odt == KX_F16C ? 2 * D : D;                     // (KX_F16C rows: strides count 2-byte units)
   p.out = out; p.obs = Tn * ors; p.ors = ors; p.o_bf16 = odt == KX_BF16; p.o_f16c = odt == KX_F16C;
   p.B = (int)B; p.H = (int)H; p.Tq = (int)Tn; p.Tk = (int)(P + Tn); p.P = (int)P;
+  p.positions = positions; p.err = err; p.Tmax = (int)Tmax;
   p.stats_out = stats_out;
   p.drop_inv_keep = 1.0f;
   p.interleave = kx_tuning_get(KX_TUNE_ATTN_VARIANT) != 8;
-  KxProfScope prof(prec == KX_PREC_F32 ? KX_K_ATTN_F32 : prec == KX_PREC_F16C ? KX_K_ATTN_F16S : KX_K_ATTN_BF16, B * H, Tn, P + Tn, s);
+  KxProfScope prof(prec == KX_PREC_F32 ? KX_K_ATTN_F32 : prec == KX_PREC_F16C ? KX_K_ATTN_F16S : KX_K_ATTN_BF16, B * H, Tn,
+                   positions ? Tmax : P + Tn, s);
   const unsigned nx = (unsigned)((Tn + 127) / 128);
   const dim3 gc((unsigned)H, (nx + 1) / 2, (unsigned)B);
-  if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_bf16_v2_kernel<true, false, false, false, true>), gc, dim3(256), 0, s, p);
-  else if (prec == KX_PREC_F16C) hipLaunchKernelGGL((attn_f16s_kernel<true, 1, false, true>), gc, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((attn_f32_mfma_kernel<true, true>), dim3((unsigned)((Tn + 63) / 64), (unsigned)H, (unsigned)B), dim3(256), 0, s, p);
-  KX_CHECK_LAUNCH("kx_attention_extend");
+  if (positions) {
+    if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_bf16_v2_kernel<true, false, false, false, KX_EXT_RAGGED>), gc, dim3(256), 0, s, p);
+    else if (prec == KX_PREC_F16C) hipLaunchKernelGGL((attn_f16s_kernel<true, 1, false, KX_EXT_RAGGED>), gc, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attn_f32_mfma_kernel<true, KX_EXT_RAGGED>), dim3((unsigned)((Tn + 63) / 64), (unsigned)H, (unsigned)B), dim3(256), 0, s, p);
+  } else if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_bf16_v2_kernel<true, false, false, false, KX_EXT_UNIFORM>), gc, dim3(256), 0, s, p);
+  else if (prec == KX_PREC_F16C) hipLaunchKernelGGL((attn_f16s_kernel<true, 1, false, KX_EXT_UNIFORM>), gc, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_f32_mfma_kernel<true, KX_EXT_UNIFORM>), dim3((unsigned)((Tn + 63) / 64), (unsigned)H, (unsigned)B), dim3(256), 0, s, p);
+  KX_CHECK_LAUNCH(fn);
   return KX_OK;
+}
+
+extern "C" int kx_attention_extend(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out, int64_t B,
+                                   int64_t H, int64_t Tn, int64_t P, int64_t Tmax, int32_t prec, void* stream) {
+  return attention_extend_impl("kx_attention_extend", qkv, kcache, vcache, out, odt, stats_out, B, H, Tn, P, nullptr, nullptr, Tmax, prec,
+                               stream);
+}
+
+extern "C" int kx_attention_extend_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
+                                          int64_t B, int64_t H, int64_t Tn, const int32_t* positions, int64_t Tmax, int32_t prec,
+                                          int32_t* error_word, void* stream) {
+  KX_REQUIRE(positions && error_word, "kx_attention_extend_ragged: null positions / error_word");
+  return attention_extend_impl("kx_attention_extend_ragged", qkv, kcache, vcache, out, odt, stats_out, B, H, Tn, 0, positions, error_word,
+                               Tmax, prec, stream);
 }
 
 // one decode launch on a cache of T: the form picks the pack and the grid (see attention_decode_impl)

@@ -315,6 +315,11 @@ int kx_launch_rows_bcast(const float* src, float* dst, int64_t B, int64_t rows, 
 int kx_launch_patchify(const float* pixels, void* patches, int64_t B, int image, int patch, int kpad, int prec,
                        hipStream_t s);
 int kx_launch_kv_prefill(const void* qkv, void* kc, void* vc, int64_t B, int64_t T, int64_t D, int64_t Tmax, int prec,
-                         hipStream_t s, int64_t row0 = 0);   // the rows go to cache rows [row0, row0 + T)
+                         hipStream_t s, int64_t row0 = 0,    // the rows go to cache rows [row0, row0 + T)
+                         const int32_t* positions = nullptr, int32_t* err = nullptr);   // ... or, per sequence, from positions[b] (device)
+int kx_launch_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
+                           const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
+                           float* xpos_rows, int64_t B, int64_t span, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
+                           int64_t xpos_len, int32_t* error_word, void* stream);   // kx_step_prepare on `span` consecutive rows per position
 int kx_launch_vit_assemble(const float* patch_out, const float* cls, const float* pos, float* x, int64_t B,
                            int tokens, int dim, hipStream_t s);

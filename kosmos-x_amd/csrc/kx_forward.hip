@@ -547,10 +547,14 @@ extern "C" size_t kx_decoder_workspace_bytes(const kx_decoder_weights* w, int64_
 static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B, int64_t T, const float* xq_cs,
                                 const float* xq_ss, const float* xk_cs, const float* xk_ss, void* logits, int32_t ldt,
                                 void* workspace, size_t workspace_bytes, int32_t prec, void* stream, void* kcache,
-                                void* vcache, int64_t Tmax, int64_t P = 0, bool need_logits = true) {
+                                void* vcache, int64_t Tmax, int64_t P = 0, bool need_logits = true,
+                                const int32_t* positions = nullptr, int32_t* error_word = nullptr) {
   // P > 0 (kx_decoder_extend): the caches already hold P rows per sequence and the T rows are positions P .. P + T - 1 — the XPos
   // tables are read from row P, the append goes to row P and the attention reads its keys from the cache (kx_attention_extend).
   // !need_logits (kx_decoder_extend with logits == NULL): the call ends after the last layer.
+  // positions (kx_decoder_extend_ragged; device, P unused): sequence b's caches hold positions[b] rows and its T rows are positions
+  // positions[b] .. + T - 1 — xq_* / xk_* are [B * T, 32] tables that already hold every row's own XPos row (xpos_T = B * T), and
+  // the append and the attention read positions[b] on the device (kx_attention_extend_ragged).  Null: the path above, launch for launch.
   KX_REQUIRE(w && x && (logits || !need_logits) && workspace, "kx_decoder_forward: null pointer");
   KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_forward");
   KX_REQUIRE(prec >= KX_PREC_BF16 && prec <= KX_PREC_F16, "kx_decoder_forward: bad precision %d (KX_PREC_F32W24 / W16 are decode-step formats)", prec);
@@ -609,10 +613,10 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     q.bias = fold ? L.bqkv_f : L.bqkv; q.qscale = 0.125f; q.qcols = D; q.family = FAM_QKV;
     // ([*, 32] tables: row m % T of those from row P)
     q.xq_cs = w->xpos ? xq_cs + xo : nullptr; q.xq_ss = xq_ss + xo; q.xk_cs = xk_cs + xo; q.xk_ss = xk_ss + xo;
-    if (w->xpos) { q.xT = T; q.xdim = D; }
+    if (w->xpos) { q.xT = positions ? M : T; q.xdim = D; }
     if (st1) { q.row_stats = d.stats2; q.colsum = L.wqkv_colsum; }
     KX_TRY(st.gemm(q));
-    if (kcache && P == 0)     // incremental decoding: keep this layer's (XPos-rotated) keys and values
+    if (kcache && P == 0 && !positions)     // incremental decoding: keep this layer's (XPos-rotated) keys and values
       KX_TRY(kx_launch_kv_prefill(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, B, T, D, Tmax, prec, s));
     // inner_attn_ln folded into out_proj (sub-LN): the attention kernel emits per-(row, head) partial statistics, the GEMM
     // multiplies the un-normalised output by γ⊙Wo and applies rstd·(acc − mean·colsum) + (β·Woᵀ + bo) in its epilogue
@@ -620,7 +624,10 @@ static int decoder_forward_impl(const kx_decoder_weights* w, float* x, int64_t B
     if (hl) a.prec = KX_PREC_F16CHL;
     if (w->subln) a.stats_out = d.partials;
     // the layer's attention: the prefill's causal launch, or over the P cached rows (which appends the new keys and values itself)
-    if (P == 0) KX_TRY(kx_attention(&a, stream));
+    if (positions)
+      KX_TRY(kx_attention_extend_ragged(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct, a.stats_out, B,
+                                        w->heads, T, positions, Tmax, aprec(prec), error_word, stream));
+    else if (P == 0) KX_TRY(kx_attention(&a, stream));
     else KX_TRY(kx_attention_extend(d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct, a.stats_out, B,
                                     w->heads, T, P, Tmax, aprec(prec), stream));
     // The residual GEMMs' RowFusion: with the row-owning reduce (fuse_*) it writes the LayerNorm that follows and takes the sub-LN
@@ -698,6 +705,35 @@ extern "C" int kx_decoder_extend(const kx_decoder_weights* w, float* x, int64_t 
              (long long)(P + T - 1), (long long)Tmax);
   return decoder_forward_impl(w, x, B, T, xq_cs, xq_ss, xk_cs, xk_ss, logits, ldt, workspace, workspace_bytes, prec, stream, kcache,
                               vcache, Tmax, P, logits != nullptr);
+}
+
+// Ragged extend: kx_decoder_extend with a per-sequence P on the device.  Row (b, i) is embedded at position positions[b] + i and its
+// four XPos rows gathered into xpos_rows [4, B * T, 32] (kx_step_prepare's kernel on T rows per sequence: no host read), then the
+// forward above in its per-sequence form.
+extern "C" int kx_decoder_extend_ragged(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                        int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t B, int64_t T,
+                                        const int32_t* positions, const float* xq_cs, const float* xq_ss, const float* xk_cs,
+                                        const float* xk_ss, float* xpos_rows, void* logits, int32_t ldt, void* kcache, void* vcache,
+                                        int64_t Tmax, void* workspace, size_t workspace_bytes, int32_t prec, int32_t* error_word,
+                                        void* stream) {
+  KX_REQUIRE(w && tokens && embed && pos && x && positions && error_word && workspace, "kx_decoder_extend_ragged: null pointer");
+  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_decoder_extend_ragged");
+  KX_REQUIRE(kcache && vcache && Tmax > 0 && Tmax <= 0x7fffffffll, "kx_decoder_extend_ragged: cache missing");
+  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C,
+             "kx_decoder_extend_ragged: incremental decoding is offered in bf16, fp32 and f16c (fp32 cache)");
+  KX_REQUIRE(B > 0 && T >= 1 && T <= Tmax && B * T <= 0x7fffffffll, "kx_decoder_extend_ragged: %lld rows per sequence do not fit a %lld-row cache",
+             (long long)T, (long long)Tmax);
+  KX_REQUIRE(!w->xpos || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows),
+             "kx_decoder_extend_ragged: the [Tmax, 32] XPos tables and the xpos_rows scratch are missing");
+  const bool xp = w->xpos != 0;
+  const int64_t M = B * T;
+  KX_TRY(kx_launch_step_prepare(tokens, embed, pos, positions, xp ? xq_cs : nullptr, xp ? xq_ss : nullptr, xp ? xk_cs : nullptr,
+                                xp ? xk_ss : nullptr, x, xp ? xpos_rows : nullptr, M, T, w->dim, vocab, max_pos, pos_shift, Tmax,
+                                error_word, stream));
+  const float* xr = xp ? xpos_rows : nullptr;
+  return decoder_forward_impl(w, x, B, T, xr, xr ? xr + M * 32 : nullptr, xr ? xr + 2 * M * 32 : nullptr, xr ? xr + 3 * M * 32 : nullptr,
+                              logits, ldt, workspace, workspace_bytes, prec, stream, kcache, vcache, Tmax, 0, logits != nullptr, positions,
+                              error_word);
 }
 
 // How the step's rows map to cache rows.

@@ -258,15 +258,23 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
 
 // The start of a ragged decode step: embed_step_kernel with the row's own position rows, read from positions[b], and the
 // gather of the row's four XPos table rows into [B, 32] tables (see kx_step_prepare in include/kosmosx_hip.h).
+// R = SpanRows (kx_decoder_extend_ragged): the launch's B rows are sequences of `span` consecutive rows, row b = (b / span, b % span)
+// at position positions[b / span] + b % span.  The empty pack is the launch it always was.
+struct SpanRows { int span; };
+template <typename... R>
 __global__ __launch_bounds__(256) void step_prepare_kernel(const long long* __restrict__ tokens, const float* __restrict__ embed,
                                                            const float* __restrict__ pos, const int* __restrict__ positions,
                                                            const float* __restrict__ t0, const float* __restrict__ t1,
                                                            const float* __restrict__ t2, const float* __restrict__ t3,
                                                            float* __restrict__ out, float* __restrict__ xrows, int B, int d,
                                                            long long vocab, long long max_pos, int pos_shift, long long xpos_len,
-                                                           int* err) {
+                                                           int* err, const R... r) {
   const long long b = blockIdx.x;
-  const long long t = positions[b];
+  long long t;
+  if constexpr (sizeof...(R) != 0) {
+    const int span = first_arg(r...).span;
+    t = (long long)positions[b / span] + b % span;
+  } else t = positions[b];
   if (t < pos_shift || t + 2 >= max_pos || (xrows && t >= xpos_len)) {   // the caller's error: nothing of this row is read or written
     if (threadIdx.x == 0) atomicOr(err, KX_RAGGED_ERR_TABLE);
     return;
@@ -375,10 +383,11 @@ extern "C" int kx_sample_logits_ragged(const kx_sample_args* args, int32_t* posi
   return sample_impl(args, positions, advance, stream);
 }
 
-extern "C" int kx_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
-                               const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
-                               float* xpos_rows, int64_t B, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
-                               int64_t xpos_len, int32_t* error_word, void* stream) {
+// span == 1: kx_step_prepare's launch.  span > 1: B counts the rows, `span` consecutive ones per entry of positions (see the kernel).
+int kx_launch_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
+                           const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
+                           float* xpos_rows, int64_t B, int64_t span, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
+                           int64_t xpos_len, int32_t* error_word, void* stream) {
   KX_REQUIRE(tokens && embed && pos && positions && x && error_word, "kx_step_prepare: null pointer");
   KX_REQUIRE(B > 0 && B <= 0x7fffffffll && d > 0 && d % 4 == 0 && d <= 0x7fffffffll && vocab > 0,
              "kx_step_prepare: bad shape B=%lld d=%lld vocab=%lld", (long long)B, (long long)d, (long long)vocab);
@@ -388,12 +397,27 @@ extern "C" int kx_step_prepare(const int64_t* tokens, const float* embed, const 
   const bool tabs = xq_cs || xq_ss || xk_cs || xk_ss || xpos_rows;
   KX_REQUIRE(!tabs || (xq_cs && xq_ss && xk_cs && xk_ss && xpos_rows && xpos_len > 0),
              "kx_step_prepare: the four XPos tables, xpos_rows and xpos_len > 0 are given together or not at all");
+  KX_REQUIRE(span >= 1 && span <= 0x7fffffffll && B % span == 0, "kx_step_prepare: %lld rows are no multiple of %lld per sequence",
+             (long long)B, (long long)span);
   KxProfScope prof(KX_K_EMBED, B, d, 1, (hipStream_t)stream);
-  hipLaunchKernelGGL(step_prepare_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const long long*)tokens, embed,
-                     pos, (const int*)positions, xq_cs, xq_ss, xk_cs, xk_ss, x, xpos_rows, (int)B, (int)d, (long long)vocab,
-                     (long long)max_pos, (int)pos_shift, (long long)xpos_len, (int*)error_word);
+  if (span > 1)
+    hipLaunchKernelGGL(step_prepare_kernel<SpanRows>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const long long*)tokens, embed,
+                       pos, (const int*)positions, xq_cs, xq_ss, xk_cs, xk_ss, x, xpos_rows, (int)B, (int)d, (long long)vocab,
+                       (long long)max_pos, (int)pos_shift, (long long)xpos_len, (int*)error_word, SpanRows{(int)span});
+  else
+    hipLaunchKernelGGL(step_prepare_kernel<>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const long long*)tokens, embed,
+                       pos, (const int*)positions, xq_cs, xq_ss, xk_cs, xk_ss, x, xpos_rows, (int)B, (int)d, (long long)vocab,
+                       (long long)max_pos, (int)pos_shift, (long long)xpos_len, (int*)error_word);
   KX_CHECK_LAUNCH("kx_step_prepare");
   return KX_OK;
+}
+
+extern "C" int kx_step_prepare(const int64_t* tokens, const float* embed, const float* pos, const int32_t* positions,
+                               const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* x,
+                               float* xpos_rows, int64_t B, int64_t d, int64_t vocab, int64_t max_pos, int64_t pos_shift,
+                               int64_t xpos_len, int32_t* error_word, void* stream) {
+  return kx_launch_step_prepare(tokens, embed, pos, positions, xq_cs, xq_ss, xk_cs, xk_ss, x, xpos_rows, B, 1, d, vocab, max_pos, pos_shift,
+                                xpos_len, error_word, stream);
 }
 
 extern "C" int kx_embed_step(const int64_t* tokens, const float* embed, const float* pos, float* out, int64_t B,

@@ -238,6 +238,9 @@ SYMBOLS = {
     "kx_attention_extend": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, i64, i64, i32, vp]),
     "kx_decoder_extend": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp,
                                     C.c_size_t, i32, vp]),
+    "kx_attention_extend_ragged": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp]),
+    "kx_decoder_extend_ragged": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp,
+                                           vp, vp, i32, vp, vp, i64, vp, C.c_size_t, i32, vp, vp]),
     "kx_decoder_forward": (C.c_int, [C.POINTER(DecoderWeights), vp, i64, i64, vp, vp, vp, vp, vp, i32, vp,
                                      C.c_size_t, i32, vp]),
     "kx_clip_preprocess_workspace_bytes": (C.c_size_t, [i64, i32, i32]),

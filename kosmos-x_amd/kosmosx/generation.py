@@ -28,7 +28,12 @@ Scoring (``score()``, score_loop): the log-likelihood of C candidate continuatio
 prefill's rows, every later column from ONE step of C * (L - 1) rows in which the candidates read their prompt's cache rows and
 nobody appends (kx_decoder_score_step), the log-probs taken row by row without a softmax (kx_token_logprob).
 
-Not offered: compaction of finished rows, replaying the step as a captured graph, padding masks in
+Sessions (``return_session``, Session): the plain loop's state kept after the call.  A later turn's ids — behind the row's pending
+token, the last one sampled and never fed — are appended at every row's own device-resident position in one ragged extend pass
+(kx_decoder_extend_ragged via Decoder._extend_ragged), then the same loop runs on; the host reads the error word and the rows'
+valid token counts once per turn.
+
+Not offered: sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
 """
@@ -46,7 +51,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
-                  prompt_rows=None):
+                  prompt_rows=None, pad_launches=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -59,7 +64,11 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     history is ``prompt_tokens`` followed by the generated tokens — the TEXT ids only: spliced image rows contribute no ids, so
     an n-gram, a bad word or a stop sequence may span the splice point.  ``text_lengths`` (ragged batches; default ``lengths``):
     row b's number of prompt TOKENS, where ``lengths`` counts the spliced rows too.  ``output_logits`` keeps returning the
-    model's own logits, taken before the bans."""
+    model's own logits, taken before the bans.
+    ``pad_launches`` (sessions; ragged batches only): an int32 [B] device tensor, zero on entry.  Before every sampler launch — after
+    the step's constraint launch — the ``finished`` bytes are added to it, so that row b entered n - pad_launches[b] of the n
+    sampler launches unfinished: its valid tokens, an EOS or the last token of a stop sequence included.  It is read back once,
+    after the loop, in the same copy as the step kernels' error word, and left in state["turn"] = (n, [pad launches per row])."""
     B, T, V = logits.shape
     gathered = prompt_rows is not None
     if gathered:
@@ -105,6 +114,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
                                  no_repeat_ngram_size=cons["ngram"], bad_words=bad, stop_sequences=stop,
                                  min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
+        if pad_launches is not None:
+            pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
         if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
@@ -133,7 +144,11 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         t = T + g
         pos = (t - pos_shift, t) if pos_shift else (t, -1)
         row = decoder._forward_incremental(None, state, None, prec, next_token=nxt, next_pos=pos)[:, 0]
-    if positions is not None:
+    if pad_launches is not None:                                          # the turn's one read: the error word and the counts
+        word, *pads = torch.cat([err, pad_launches]).tolist()
+        _raise_position_error(word, state)
+        state["turn"] = (n, pads)
+    elif positions is not None:
         _raise_position_error(int(err.item()), state)                     # device positions are validated by the kernels, not here
     out = out[:, :n]
     if output_logits:
@@ -549,7 +564,7 @@ def check_prefill_chunk(prefill_chunk):
     return prefill_chunk
 
 
-def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True, chunk=None):
+def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True, chunk=None, capacity=None):
     """The prompt's prefill, under torch.no_grad(): ``prompt`` as run_generate takes it, ``new_rows`` (+ ``spare``) the positions the
     caller will add, checked against the tables when ``budget``.  Returns the tokens as prefilled (trimmed to the longest prompt, the
     padding masked), the host lengths (None: a uniform batch), T (prefix rows included), the state, the prefill's logits and the
@@ -557,14 +572,15 @@ def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0,
     ``chunk`` C < T (check_prefill_chunk): the rows are embedded once and prefilled C at a time — rows [0, C) by the prefill call,
     with the XPos centring of the whole T (state["xpos_centre"]), every later slice by Decoder._extend — the first slice always
     writes its C logits rows, a later one only if it holds a row the loops read, last position or len_b - 1; those rows are
-    returned as [B, 1, V] with ``prompt_rows`` = T."""
+    returned as [B, 1, V] with ``prompt_rows`` = T.
+    ``capacity`` (sessions): the cache rows per sequence instead of T + ``new_rows``; the budget is checked against it too."""
     tokens, lens = prompt["tokens"], None
     if prompt_lengths is not None:
         lens = resolve_prompt_lengths(prompt_lengths, tokens.shape[0], tokens.shape[1], min_len=prompt["min_len"])
         tokens = tokens[:, :max(lens)]                                      # columns no row uses
     T = tokens.shape[1] + prompt["prefix_rows"]
     if budget:
-        check_budget(model.decoder, T, new_rows, spare=spare)
+        check_budget(model.decoder, T, new_rows, spare=spare, rows=capacity)
     if lens is not None:
         tokens = mask_padding(tokens.long(), lens)
     # Ragged prompts go through the ordinary prefill, right-padded, with no padding mask and no new kernel: attention is
@@ -575,7 +591,7 @@ def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0,
     # first that could see it (kx_attention_decode_ragged appends row positions[b] and reads that key from the qkv row);
     # a score() candidate reads cache rows < len_b only.
     passed_x = prompt["passed_x"](tokens)                                   # (the prompt's ids are range-checked here or in the prefill, once)
-    state = {"max_len": T + new_rows + spare}                               # (rejected drafts still occupy table and cache rows)
+    state = {"max_len": T + new_rows + spare if capacity is None else capacity}   # (rejected drafts still occupy table and cache rows)
     if chunk is None or chunk >= T:
         logits = model.decoder._forward_incremental(tokens if passed_x is None else None, state, passed_x, model.precision)
         return tokens, lens, T, state, logits, None
@@ -619,10 +635,15 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
         "sequence_ids", *constraints, "eos_poll"))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
+    capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
+                                                                              "prompt_lookup_num_tokens"))
     prompt["check"]()
     with torch.no_grad():
         tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts,
-                                                               chunk=chunk)
+                                                               chunk=chunk, capacity=capacity)
+        if capacity is not None:
+            return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
+                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", *constraints)))
         common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
@@ -652,12 +673,13 @@ def run_score(model, prompt: dict, continuations, kw: dict):
                           output_logits=kw["output_logits"], prompt_rows=prompt_rows)
 
 
-def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0):
+def check_budget(decoder, T: int, max_new_tokens: int, spare: int = 0, rows=None):
     """IndexError before any launch when prompt + new tokens (+ ``spare`` rows: the drafts of a lookup step) overrun the position
-    table / cache."""
+    table / cache (``rows``: a session's cache rows, at most the table's)."""
     if not isinstance(max_new_tokens, int) or max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
-    rows = decoder.embed_positions.weight.shape[0] - 2
+    if rows is None:
+        rows = decoder.embed_positions.weight.shape[0] - 2
     # (conservative by one token: the last generated token is never embedded, so it would not need a row of its own)
     if T + max_new_tokens + spare > rows:
         raise IndexError(f"index out of range in self: {T} prompt positions + {max_new_tokens} new tokens"
@@ -704,3 +726,224 @@ def mask_padding(tokens: torch.Tensor, lengths: list) -> torch.Tensor:
     T = tokens.shape[1]
     lens = torch.tensor(lengths, dtype=torch.int64, device=tokens.device)
     return torch.where(torch.arange(T, device=tokens.device)[None, :] < lens[:, None], tokens, tokens[:, :1])
+
+
+# ---- sessions: generate() that keeps its KV cache and takes further turns ----
+
+def check_session_args(decoder, *, return_session=False, session_capacity=None, num_beams=1, prompt_lookup_num_tokens=0, beams=False,
+                       drafts=0):
+    """ValueError (naming the argument) for what generate() refuses of the session arguments, before the device check and any
+    launch.  Returns the cache rows per sequence of the session, or None when none was asked for."""
+    if not return_session:
+        if session_capacity is not None:
+            raise ValueError("session_capacity is the cache size of a session: it needs return_session=True")
+        return None
+    if beams:
+        raise ValueError(f"return_session is not offered together with beam search (num_beams = {num_beams}): its caches are gathered "
+                         "per beam, no row of them is one conversation; see DESIGN.md §8")
+    if drafts:
+        raise ValueError(f"return_session is not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
+                         f"{prompt_lookup_num_tokens}): its caches hold draft rows; see DESIGN.md §8")
+    rows = decoder.embed_positions.weight.shape[0] - 2
+    if session_capacity is None:
+        return rows
+    if isinstance(session_capacity, bool) or not isinstance(session_capacity, int) or session_capacity < 1:
+        raise ValueError(f"session_capacity must be a positive integer (cache rows per sequence) or None, got {session_capacity!r}")
+    if session_capacity > rows:
+        raise ValueError(f"session_capacity = {session_capacity} exceeds the {rows}-row position table")
+    return session_capacity
+
+
+def session_after_turn(cached: list, block_lens: list, n_valid: list):
+    """A turn's bookkeeping, host lists in and out.  Row b's cache held cached[b] valid rows, the turn appended its block of
+    block_lens[b] rows (a pending token and the new ids) and generated n_valid[b] valid tokens, of which all but the last were fed
+    back.  Returns (logical lengths, valid cache rows, index of the pending token among the row's generated ones or -1): the last
+    valid token was sampled but never fed — or fed at the very row the next turn rewrites — so it is pending and its row is not
+    counted as cached."""
+    lengths = [c + bl + nv for c, bl, nv in zip(cached, block_lens, n_valid)]
+    rows = [c + bl + max(nv - 1, 0) for c, bl, nv in zip(cached, block_lens, n_valid)]
+    return lengths, rows, [nv - 1 for nv in n_valid]
+
+
+def _loop_turn(session, rows, history, hist_lens, starts, max_new_tokens, kw):
+    """generate_loop on a session's state: ``rows`` [B, 1, V] the logits every sequence draws its first token from, ``history``
+    [B, W] the conversation's text ids (mask_padding-ed), ``hist_lens`` their lengths, ``starts`` the positions the first new
+    tokens take = the valid cache rows.  Returns (what generate_loop returns, n_valid per row)."""
+    dev = rows.device
+    pads = torch.zeros(len(starts), dtype=torch.int32, device=dev)
+    res = generate_loop(session._decoder, session._model.precision, session._state, rows, history, max_new_tokens,
+                        pos_shift=session._pos_shift, lengths=list(starts), text_lengths=list(hist_lens), prompt_rows=max(starts),
+                        pad_launches=pads, **kw)
+    n, padded = session._state.pop("turn")
+    return res, [n - p for p in padded]
+
+
+def _first_turn(model, prompt, state, logits, tokens, lens, prompt_rows, max_new_tokens, capacity, kw):
+    """The generate() call that opens a session: the plain ragged loop on the prefilled state (a uniform batch as a ragged one of
+    equal lengths: the same Philox positions, the same bits), then the Session around what it left."""
+    B, Tt = tokens.shape
+    text_lens = [Tt] * B if lens is None else list(lens)
+    starts = [prompt["prefix_rows"] + l for l in text_lens]
+    if prompt_rows is None:                                               # the row every sequence reads, as a chunked prefill returns it
+        idx = torch.tensor([s - 1 for s in starts], dtype=torch.int64, device=logits.device)
+        logits = logits[torch.arange(B, device=logits.device), idx][:, None]
+    session = Session(model, state, capacity, prompt["pos_shift"], prompt["prefix_rows"])
+    res, n_valid = _loop_turn(session, logits, tokens, text_lens, starts, max_new_tokens, kw)
+    out = res[0] if isinstance(res, tuple) else res
+    session._advance([tokens[b, :l] for b, l in enumerate(text_lens)], starts, [0] * B, out, n_valid)
+    return (*res, session) if isinstance(res, tuple) else (res, session)
+
+
+class Session:
+    """A batch of conversations whose KV cache outlives generate(): ``generate(..., return_session=True)`` returns one after its
+    usual outputs.  After any number of turns row b behaves like a fresh ragged generate() whose prompt is the row's whole logical
+    sequence so far — its first prompt (spliced image rows included), every turn's valid output and every appended turn — with the
+    XPos tables centred on the first call's T (rounding only).  Later turns are text only.
+
+    ``lengths``: host list, every row's logical length in positions.  ``capacity``: the cache rows per sequence.
+    A row's last valid token of a turn was sampled but never fed: it is pending, and the next turn's block for the row is that
+    token followed by the new ids, right-padded to the widest block (padding ids as mask_padding), appended at the row's own
+    position by one ragged extend (Decoder._extend_ragged).  Cache rows at or after a row's valid length hold leftovers from pad
+    steps and padding; every launch that could read them rewrites them first (the argument of _prefill's comment)."""
+
+    def __init__(self, model, state: dict, capacity: int, pos_shift: int = 0, prefix_rows: int = 0):
+        self._model, self._decoder, self._state = model, model.decoder, state
+        self.capacity = int(capacity)
+        self._pos_shift = int(pos_shift)
+        self.prefix_rows = int(prefix_rows)           # spliced image rows of the first prompt: counted in ``lengths``, not text ids
+        self.batch = int(state["batch"])
+        self.lengths = [0] * self.batch
+        self._cached = [0] * self.batch               # valid cache rows per sequence
+        self._text = [None] * self.batch              # the conversation's text ids per row (device, int64 [n])
+        self._pending = [None] * self.batch           # the sampled-but-unfed token per row (device, int64 [1]) or None
+
+    # -- host-side checks: before the device check and any launch --
+    def _check_turn(self, x, prompt_lengths):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("x must be an instance of torch.Tensor")
+        if x.dim() != 2 or x.shape[1] < 1:
+            raise ValueError(f"x must be [batch, new tokens] with at least one token, got {tuple(x.shape)}")
+        if x.shape[0] != self.batch:
+            raise ValueError(f"x holds {x.shape[0]} rows, the session {self.batch}: a session keeps its batch size")
+        if prompt_lengths is None:
+            return [x.shape[1]] * self.batch
+        return resolve_prompt_lengths(prompt_lengths, self.batch, x.shape[1])
+
+    def _check_room(self, block_width: int, new_tokens: int):
+        """The conservative budget: the padded block's rows need cache room too (there is no per-row row count on the device)."""
+        need = max(self._cached) + block_width + new_tokens
+        if need > self.capacity:
+            raise IndexError(f"index out of range in self: {max(self._cached)} cached rows + a block of {block_width} rows + "
+                             f"{new_tokens} new tokens exceed the session's {self.capacity}-row cache")
+
+    def _advance(self, new_text, cached, block_lens, out, n_valid):
+        """After a turn: ``new_text`` per row the ids the turn brought in (device), ``out`` [B, n] what it generated (or None)."""
+        self.lengths, self._cached, pend = session_after_turn(cached, block_lens, n_valid)
+        for b in range(self.batch):
+            parts = [t for t in (self._text[b], new_text[b]) if t is not None]
+            if out is not None and n_valid[b] > 0:
+                parts.append(out[b, :n_valid[b]])
+                self._pending[b] = out[b, pend[b]:pend[b] + 1].clone()
+            else:
+                self._pending[b] = None
+            self._text[b] = torch.cat(parts)
+
+    def _block(self, x, lens):
+        """The turn's block [B, W] (pending token, then the row's new ids; right-padded with the row's first id), its lengths and
+        the conversation's text ids with the new ones [B, Wt] (padded the same way) with their lengths."""
+        rows = [x[b, :l] if self._pending[b] is None else torch.cat([self._pending[b], x[b, :l]]) for b, l in enumerate(lens)]
+        block_lens = [int(r.shape[0]) for r in rows]
+        hist = [torch.cat([self._text[b], x[b, :l]]) for b, l in enumerate(lens)]
+        hist_lens = [int(h.shape[0]) for h in hist]
+        pad = torch.nn.utils.rnn.pad_sequence
+        return (mask_padding(pad(rows, batch_first=True), block_lens), block_lens,
+                mask_padding(pad(hist, batch_first=True), hist_lens), hist_lens)
+
+    def _extend(self, block, block_lens, chunk, want_logits: bool):
+        """The block through Decoder._extend_ragged, ``chunk`` columns at a time; a slice computes logits only if it holds a row's
+        last position.  Returns the [B, 1, V] rows the loop reads (None without ``want_logits``).  Moves the device positions to
+        the rows' new valid lengths."""
+        state, dec, prec = self._state, self._decoder, self._model.precision
+        dev, B, W = block.device, self.batch, block.shape[1]
+        base = torch.tensor(self._cached, dtype=torch.int32, device=dev)
+        state["positions"], state["pos_max"] = base, max(self._cached)
+        step = W if chunk is None else min(chunk, W)
+        rows = None
+        for s0 in range(0, W, step):
+            s1 = min(s0 + step, W)
+            want = [b for b in range(B) if s0 <= block_lens[b] - 1 < s1] if want_logits else []
+            logits = dec._extend_ragged(block[:, s0:s1], state, base if s0 == 0 else base + s0, prec, output_logits=bool(want),
+                                        pos_shift=self._pos_shift)
+            if want:
+                if rows is None:
+                    rows = torch.empty((B, 1, logits.shape[2]), dtype=torch.float32, device=dev)
+                idx = torch.tensor(want, dtype=torch.int64, device=dev)
+                rows[idx, 0] = logits[idx, torch.tensor([block_lens[b] - 1 - s0 for b in want], dtype=torch.int64, device=dev)]
+        return rows
+
+    def generate(self, x: torch.Tensor, max_new_tokens: int, *, prompt_lengths=None, do_sample=False, temperature=1.0, top_k=0,
+                 top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
+                 output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
+                 prefill_chunk=None):
+        """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
+        at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
+        session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
+        constraints see the text ids of the whole conversation.  A turn that does not fit — the longest row's cached rows + the
+        padded block's width + ``max_new_tokens`` > capacity — raises IndexError before any launch and leaves the session where it
+        was.  An error after the first launch (an id outside the vocabulary) leaves it where it was too: the rows the turn wrote
+        lie at or after every row's valid length."""
+        lens = self._check_turn(x, prompt_lengths)
+        vocab = self._model.embed.weight.shape[0]
+        check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                              min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
+        chunk = check_prefill_chunk(prefill_chunk)
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
+        width = max(l + (self._pending[b] is not None) for b, l in enumerate(lens))
+        self._check_room(width, max_new_tokens)
+        _need_device(x)
+        with torch.no_grad():
+            x = x.long()
+            block, block_lens, history, hist_lens = self._block(x, lens)
+            cached = list(self._cached)
+            try:
+                rows = self._extend(block, block_lens, chunk, True)
+                starts = [c + bl for c, bl in zip(cached, block_lens)]
+                res, n_valid = _loop_turn(self, rows, history, hist_lens, starts, max_new_tokens, dict(
+                    do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                    seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
+                    output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                    min_new_tokens=min_new_tokens, stop_sequences=stop_sequences))
+            finally:
+                self._state["pos_max"] = max(self._cached)
+            out = res[0] if isinstance(res, tuple) else res
+            self._advance([x[b, :l] for b, l in enumerate(lens)], cached, block_lens, out, n_valid)
+            self._state["pos_max"] = max(self._cached)
+        return res
+
+    def append(self, x: torch.Tensor, *, prompt_lengths=None, prefill_chunk=None):
+        """Known tokens — a tool result, a system turn — into every row's cache; nothing is generated and no logits are computed.
+        ``x`` and ``prompt_lengths`` as in generate().  IndexError before any launch when the padded block does not fit."""
+        lens = self._check_turn(x, prompt_lengths)
+        chunk = check_prefill_chunk(prefill_chunk)
+        width = max(l + (self._pending[b] is not None) for b, l in enumerate(lens))
+        self._check_room(width, 0)
+        _need_device(x)
+        with torch.no_grad():
+            x = x.long()
+            block, block_lens, _, _ = self._block(x, lens)
+            cached = list(self._cached)
+            try:
+                self._extend(block, block_lens, chunk, False)
+                word = int(self._state["error"].item())
+                _raise_position_error(word, self._state)
+            finally:
+                self._state["pos_max"] = max(self._cached)
+            # every id of the block was fed: the rows are cached, nothing is pending (n_valid = 0 rows keep lengths = cached)
+            self._advance([x[b, :l] for b, l in enumerate(lens)], cached, block_lens, None, [0] * self.batch)
+            self._state["pos_max"] = max(self._cached)
+
+
+def _need_device(x):
+    from .model import _require_cuda
+    _require_cuda(x, "x")

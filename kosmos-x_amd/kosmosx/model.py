@@ -858,6 +858,56 @@ class Decoder(_PackedMixin, nn.Module):
         state["len"] = P + Tn
         return logits
 
+    def _extend_ragged(self, tokens, state: dict, seq_positions, prec: str, output_logits: bool = True, pos_shift: int = 0):
+        """Append Tn rows per sequence to a filled RAGGED state in one pass (kx_decoder_extend_ragged): ``tokens`` int64 [B, Tn],
+        sequence b's rows at positions seq_positions[b] .. + Tn - 1 — ``seq_positions`` an int32 [B] DEVICE tensor of the rows each
+        sequence has cached (usually state["positions"]); nothing is read back.  Embedding (with ``pos_shift`` as the ragged step)
+        and the XPos gather happen on the device.  Returns the fp32 logits [B, Tn, V], or None without ``output_logits``.
+        The checks of _extend, against the host-side maximum state["pos_max"]; any error leaves the state where it was.  On
+        success state["pos_max"] grows by Tn (the furthest row a sequence may now hold); ``seq_positions`` is NOT moved — the
+        caller knows how many of a sequence's Tn rows were real — and a sequence that left the cache or the tables shows in
+        state["error"], as after a ragged step."""
+        if state.get("positions") is None:
+            raise ValueError("_extend_ragged takes a ragged incremental state (state['positions']); a uniform one is extended with extend()")
+        prec = self._incremental_precision(prec)
+        w, _, _, emb, pos = self._pack(prec)
+        lib = H.load()
+        Tmax, B = state["max_len"], state["batch"]
+        _require_cuda(tokens, "tokens")
+        _require_cuda(seq_positions, "seq_positions")
+        if tokens.dim() != 2 or tokens.dtype != torch.int64:
+            raise TypeError("_extend_ragged: tokens must be an int64 [B, Tn] tensor")
+        if seq_positions.dtype != torch.int32 or tuple(seq_positions.shape) != (B,) or not seq_positions.is_contiguous():
+            raise TypeError(f"_extend_ragged: seq_positions must be a contiguous int32 [{B}] tensor on the device")
+        Bx, Tn = tokens.shape
+        if state["prec"] != prec:
+            raise RuntimeError("precision changed between incremental steps")
+        if Bx != B:
+            raise ValueError("batch size changed between incremental steps")
+        if Tn < 1:
+            raise ValueError("extend() takes at least one new row per sequence")
+        t = state["pos_max"] + Tn - 1                                      # the furthest row: what the table / cache must still hold
+        if t >= Tmax or t + 2 >= pos.shape[0]:
+            raise IndexError(f"index out of range in self: position {t + 2} exceeds the table / cache")
+        tokens = tokens.contiguous()
+        dev, D = emb.device, self.args.decoder_embed_dim
+        check = _begin_token_id_check(tokens, emb.shape[0]) if getattr(self, "validate_token_ids", True) else None
+        self._ragged_scratch(state, dev)                                   # (the sticky error word)
+        x = torch.zeros((B, Tn, D), dtype=torch.float32, device=dev)       # zeros: a rejected row is not written
+        xrows = None if state["xpos"][0] is None else torch.zeros((4, B * Tn, 32), dtype=torch.float32, device=dev)
+        logits = torch.empty((B, Tn, w.vocab), dtype=torch.float32, device=dev) if output_logits else None
+        need = lib.kx_decoder_workspace_bytes(C.byref(w), B, Tn, H.PRECS[prec])
+        buf = self._ws.get(need, dev)
+        H.check(lib.kx_decoder_extend_ragged(
+            C.byref(w), tokens.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift), x.data_ptr(),
+            B, Tn, seq_positions.data_ptr(), *(H.ptr(tb) for tb in state["xpos"]), H.ptr(xrows), H.ptr(logits), H.KX_F32,
+            state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, buf.data_ptr(), buf.numel(), H.PRECS[prec],
+            state["error"].data_ptr(), _stream()), "kx_decoder_extend_ragged")
+        if check is not None:
+            check()
+        state["pos_max"] += Tn
+        return logits
+
     def _forward_incremental(self, tokens, state: dict, passed_x, prec: str, next_token=None, next_pos=None,
                              pos_shift: int = 0, logits_out=None) -> torch.Tensor:
         """torchscale's incremental_state protocol: the first call runs the whole prefix and fills the KV cache,
@@ -1256,7 +1306,7 @@ class Kosmos(nn.Module):
                  early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
-                 prefill_chunk=None):
+                 prefill_chunk=None, return_session=False, session_capacity=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1294,7 +1344,12 @@ class Kosmos(nn.Module):
         top of the cache the earlier ones filled, with the XPos centring of the whole prompt.  The first slice always writes its C logits rows
         (it is the prefill call); a later slice computes logits only if it holds a row the loop reads (the last position;
         ``prompt_lengths[b] - 1`` of a ragged row), so the memory of the prefill is that of C rows instead of T; the new tokens are those of the one-piece prefill up to the rounding of a
-        different summation order.  C >= T is the one-piece path.  It composes with every other argument."""
+        different summation order.  C >= T is the one-piece path.  It composes with every other argument.
+        ``return_session``: a kosmosx.generation.Session is appended to what the call returns — the KV cache kept, with
+        ``session_capacity`` rows per sequence (default: the position table's rows) — whose ``generate(x, max_new_tokens, ...)`` and
+        ``append(x)`` take further, text-only turns: only the new ids are run, appended at every row's own position in one ragged
+        pass (kx_decoder_extend_ragged).  Row b then behaves like a fresh ragged generate() over its whole logical sequence.  Not
+        offered together with ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0 (ValueError)."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1306,7 +1361,7 @@ class Kosmos(nn.Module):
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk))
+            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1469,13 +1524,15 @@ class KosmosLanguage(nn.Module):
                  output_logits=False, prompt_lengths=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
-                 max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None):
+                 max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
+                 session_capacity=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
         arguments that go with it: beam search, as there; ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens`` and
         ``stop_sequences``: the constraints, as there; ``prompt_lookup_num_tokens``, ``max_matching_ngram_size`` and
         ``output_acceptance``: speculative decoding by prompt lookup, as there; ``prefill_chunk``: the prompt prefilled that many
-        rows at a time, as there)."""
+        rows at a time, as there; ``return_session`` and ``session_capacity``: the call also returns a Session that takes
+        further turns on the kept KV cache, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1487,7 +1544,7 @@ class KosmosLanguage(nn.Module):
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk))
+            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):

@@ -643,6 +643,35 @@ def attention_extend(qkv, kcache, vcache, P, *, out_dtype="f32", stats_out=None,
     return out
 
 
+def attention_extend_ragged(qkv, kcache, vcache, positions, error_word, *, out_dtype="f32", stats_out=None, layout="head_major",
+                            f16c=False, out=None):
+    """Kernel-level wrapper of kx_attention_extend_ragged (include/kosmosx_hip.h, "Ragged extend"): ops.attention_extend with a
+    per-sequence P on the device.  positions [B] int32: sequence b's caches hold positions[b] rows; its Tn rows are appended at
+    positions[b] .. + Tn - 1.  error_word int32 [1] (sticky: KX_RAGGED_ERR_CACHE for a sequence whose rows leave the cache — that
+    sequence writes nothing).  ``out``: the rows to write into instead of fresh zeros (a guarded sequence leaves its rows as they
+    were).  Sequence b gives the bits of a B = 1 ops.attention_extend at P = positions[b].  Returns the output rows [B * Tn, ...]."""
+    _need_cuda(qkv, kcache, vcache, positions, error_word, stats_out, out)
+    B = kcache.shape[0]
+    if B < 1 or qkv.dim() != 2 or qkv.shape[0] % B:
+        raise ValueError("attention_extend_ragged: qkv [B*Tn, 3*H*64] holds the same number of new rows for each of the caches' B sequences")
+    Tn = qkv.shape[0] // B
+    if positions is None or positions.dtype != torch.int32 or tuple(positions.shape) != (B,) or not positions.is_contiguous():
+        raise TypeError(f"attention_extend_ragged: positions must be a contiguous int32 [{B}] tensor")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError("attention_extend_ragged: error_word is an int32 [1] tensor on the device (the kernel's sticky word)")
+    B, Hh, Tmax, _, odt, fresh, prec = _decode_attention_args("attention_extend_ragged", qkv, kcache, vcache, layout, out_dtype, None, None, Tn)
+    if out is None:
+        out = fresh
+    elif out.shape != fresh.shape or out.dtype != fresh.dtype or not out.is_contiguous():
+        raise TypeError(f"attention_extend_ragged: out must be a contiguous {fresh.dtype} {tuple(fresh.shape)} tensor")
+    if f16c and prec == H.KX_PREC_F32:
+        prec = H.KX_PREC_F16C
+    H.check(H.load().kx_attention_extend_ragged(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), odt,
+                                                H.ptr(stats_out), B, Hh, Tn, positions.data_ptr(), Tmax, prec, error_word.data_ptr(),
+                                                _stream()), "kx_attention_extend_ragged")
+    return out
+
+
 def token_logprob(logits, target, *, row_index=None, vocab=None, out=None):
     """Kernel-level wrapper of kx_token_logprob (include/kosmosx_hip.h, "Scoring candidates over a shared prompt cache"):
     out[r] = log softmax(logits[row_index[r], :V])[target[r]] in one launch, no softmax written.  logits fp32 [rows_available, ld]
