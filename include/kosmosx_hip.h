@@ -264,6 +264,18 @@ typedef struct {
   uint32_t* splitk_flags;
 } kx_gemm_args;
 int kx_gemm(const kx_gemm_args* args, void* stream);
+/* What kx_gemm would launch for `args`, as text — nothing is launched and no operand pointer is dereferenced (only their
+ * alignment is looked at), so it runs on a machine without a GPU.  kx_gemm takes one snapshot of the tuning table, plans the
+ * whole call from (args, snapshot, CU count) in one pure host function, and executes the plan; this entry point prints the same
+ * plan.  One line per launch, in launch order: "kx_row_stats_finalize" (when the call finalises stats_partials first), then the
+ * main kernel as "template<arguments> grid=XxY block=B" — gemm_kernel<T, BM, BN, ACT, EPI, NST, COOP>,
+ * gemm_kernel_p3<T, ACT, PHASED> or gemm_kernel_p5<T, ACT, BM, EPI, KS2, BAL>, grid in workgroups; "gemv_fused" for
+ * tile 16, whose launcher keeps its own variant choice — then the split-K reduce (splitk_reduce_kernel<ACT> or
+ * splitk_reduce_rows_kernel<ACT, NJ>) when there is one; last, one line "plan tile=... kind=... ..." with the resolved tile, the
+ * profile kind (kx_prof_kind) and the host flags.  cu_count <= 0: the current device's CU count (256 without a device).
+ * A call kx_gemm would refuse returns the same code and leaves the same message; out_bytes too small is KX_ERR_INVALID_ARG
+ * (4096 bytes always suffice).  A function-only addition: no struct changed, kx_version() stays 7. */
+int kx_gemm_describe(const kx_gemm_args* args, int cu_count, char* out, size_t out_bytes);
 /* Diagnostics of the pair split's bounded hand-off: *word_out = 0 when every poll since the last call met its partner, else
  * 1 + the index of the last workgroup that gave up (the word is then cleared).  SYNCHRONISES the device — call it after a
  * batch of steps, never inside the step. */

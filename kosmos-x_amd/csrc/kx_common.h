@@ -41,9 +41,11 @@ void kx_set_error(const char* fmt, ...);
     if (rc__ != KX_OK) return rc__; \
   } while (0)
 
-// ---- runtime tuning knobs (kx_set_tuning) ----
-enum { KX_TUNE_LN_VARIANT = 0, KX_TUNE_GEMM_TILE = 1, KX_TUNE_ATTN_VARIANT = 2, KX_TUNE_GEMM_STAGGER = 3, KX_TUNE_GEMM_EPILOGUE = 4, KX_TUNE_GEMM_IDLE_SKIP = 5, KX_TUNE_PREPROCESS_NO_LDS = 6, KX_TUNE_GEMM_PERSISTENT = 7, KX_TUNE_GEMV_VARIANT = 8, KX_TUNE_CACHE_LAYOUT = 9, KX_TUNE_DECODE_STREAM_F32 = 10, KX_TUNE_DECODE_KSPLIT = 11, KX_TUNE_DECODE_PIECES = 12, KX_TUNE_GEMM_PAIRK = 13, KX_TUNE_GEMM_KLOOP = 14, KX_TUNE_GEMM_RULES = 15, KX_TUNE_F16C_CORR = 16, KX_TUNE_SPLITK_COOP = 17, KX_TUNE_OBJECTIVE = 18, KX_TUNE_COUNT = 19 };
+// ---- runtime tuning knobs (kx_set_tuning): the keys and the by-value snapshot live in kx_gemm_plan.h (host-only) ----
+#include "kx_gemm_plan.h"
 int kx_tuning_get(int key);
+KxTuning kx_tuning_snapshot();   // the whole table at one instant
+int kx_cu_count();                // CUs of the current device, cached per device ordinal (256 without a device)
 // number of K slices kx_gemm's automatic choice gives an (M, N, K) problem with `ws_bytes` of split-K scratch (1 = no split)
 int kx_gemm_auto_splits(int64_t M, int64_t N, int64_t K, int prec, size_t ws_bytes);
 
@@ -182,13 +184,13 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
   const float ha = ax * 0.5f, h = x * 0.5f;
   return __builtin_fmaf(ha, erf, h);
 }
-#define KX_ACT_GELU_FAST 3  /* internal: chosen by kx_gemm for KX_ACT_GELU when prec == bf16 */
+// KX_ACT_GELU_FAST (3, kx_gemm_plan.h): internal, chosen by kx_gemm for KX_ACT_GELU in the 16-bit-operand modes
 // GELU without transcendentals for the accumulator-level epilogues of the plain-bf16 256-column kernel, where the matrix
 // pipe idles while the VALU works (v_rcp_f32 / v_exp_f32 issue at a quarter of the fma rate, and every instruction
 // below has a packed two-value form): x * (0.5 + u * Q(u^2)), u = clamp(x, +-3*sqrt2) / (3*sqrt2), Q = degree-8 minimax
 // fit of 0.5 * erf(3u) / u weighted by the error on the GELU output (tools/fit_gelu_poly.py).  |error| <= 5.5e-5 on the
 // output for every x (fp32 Horner included) — a fortieth of bf16's rounding step at 1.0; bf16 outputs only.
-#define KX_ACT_GELU_POLY 4  /* internal: gemm_kernel_p5's lean epilogues, bf16 operands and bf16 output */
+// KX_ACT_GELU_POLY (4, kx_gemm_plan.h): internal, gemm_kernel_p5's lean epilogues, bf16 operands and bf16 output
 __device__ __forceinline__ f32x2_t gelu_poly2(f32x2_t x) {
   constexpr float C = 4.242640495300293f, RC = 0.2357022613286972f;
   f32x2_t u;

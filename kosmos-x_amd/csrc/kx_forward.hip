@@ -36,6 +36,11 @@ extern "C" int kx_last_error(char* buf, size_t n) {
 // a tool flipping a knob from one thread while another thread launches is a data-race-free read of either value.
 static std::atomic<int> g_tuning[KX_TUNE_COUNT];
 int kx_tuning_get(int key) { return (key >= 0 && key < KX_TUNE_COUNT) ? g_tuning[key].load(std::memory_order_relaxed) : 0; }
+KxTuning kx_tuning_snapshot() {
+  KxTuning tn;
+  for (int k = 0; k < KX_TUNE_COUNT; ++k) tn.v[k] = g_tuning[k].load(std::memory_order_relaxed);
+  return tn;
+}
 extern "C" int kx_set_tuning(int key, int value) {
   if (key < 0 || key >= KX_TUNE_COUNT) {
     kx_set_error("kx_set_tuning: unknown key %d", key);
@@ -228,7 +233,7 @@ struct Stage {
   }
 
   // Will kx_gemm's automatic choice split this (M, N, K) problem, i.e. is the row-owning reduce (RowFusion) available?
-  // Same rule as kx_gemm itself; an explicit tile override (A/B runs) keeps the separate kernels.
+  // kx_gemm_auto_splits IS the planner's split rule (kx_gemm_plan.h); an explicit tile override (A/B runs) keeps the separate kernels.
   bool row_reduce_available(int64_t M, int64_t N, int64_t K) const {
     if (kx_tuning_get(KX_TUNE_GEMM_TILE) != 0 || N > 8192 || N % 4 != 0) return false;
     if (prec == KX_PREC_F16C) return kx_gemm_auto_splits(M, N, K, prec, splitk_ws_bytes) > 1;
@@ -236,18 +241,6 @@ struct Stage {
     return kx_gemm_auto_splits(M, N, K * kmul(prec), gp, splitk_ws_bytes) > 1;
   }
 };
-
-static int cu_count() {   // CUs of the current device (cached for device 0..63)
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (n == 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
 
 // tile 16 (weight streaming, bf16, M <= 16) with its prologues — see kx_gemm_args in the header
 struct Gemv16 {
@@ -799,7 +792,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     // part 1 its product to the second; the LayerNorm prologues and the next residual read sum the pair in that order.
     // No cross-workgroup reduction, deterministic.  Tuning key 11 = 1 keeps one workgroup per block (in place: x += ...).
     const bool pair = kx_tuning_get(KX_TUNE_DECODE_KSPLIT) != 1 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 1 &&
-                      D / 16 <= (cu_count() * 3) / 4 && D % 128 == 0 && F % 128 == 0 &&
+                      D / 16 <= (kx_cu_count() * 3) / 4 && D % 128 == 0 && F % 128 == 0 &&
                       M <= 4;   // (five rows and more take the wave-per-row LayerNorm prologue, which walks each row three times: reading a
                                 //  pair there cost more than the idle CUs — B = 8: 1.43 -> 1.55 ms per step in bf16)
     // Block-scaled 16-bit planes, three rows and more: the residual GEMMs multiply fp16 pieces (kx_gemm_args.w_tiled = 3), and what

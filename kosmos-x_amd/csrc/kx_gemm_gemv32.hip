@@ -2,4 +2,4 @@
 // tolerance (its own translation unit: the instantiations compile in parallel with the tile kernels)
 #include "kx_gemm_impl.h"
 
-int kx_gemm_launch_gemv_f32(GemmParams& p, hipStream_t s) { return launch_gemv_fused<float>(p, s); }
+int kx_gemm_launch_gemv_f32(GemmParams& p, const KxTuning& tn, hipStream_t s) { return launch_gemv_fused<float>(p, tn, s); }

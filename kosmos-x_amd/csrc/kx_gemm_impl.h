@@ -1,7 +1,7 @@
 // Kernel templates of the GEMM family (see kx_gemm.hip for the layout decisions).  Header-only so that the
 // instantiations can be compiled in parallel translation units: kx_gemm_tiles.hip (bf16 tile / split-K / weight
 // streaming kernels), kx_gemm_p5.hip (bf16 phased 256-column + 256x128 ring kernels), kx_gemm_f32.hip (exact-f32),
-// kx_gemm_f16c.hip (KX_F16C).  kx_gemm.hip keeps the argument checks and the variant choice.
+// kx_gemm_f16c.hip (KX_F16C).  The argument checks and the variant choice are kx_gemm_plan.h; kx_gemm.hip executes the plan.
 #pragma once
 #include "kx_common.h"
 #include <atomic>
@@ -1619,17 +1619,23 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_p3(const GemmParams p) {
   else store_loop<ACT, WN>(p, cw, WM, lane, m0 + wm * WM, n0 + wn * WN);
 }
 
+// ---- launch tables: from a plan's instantiation (KxGemmPlan, kx_gemm_plan.h) to hipLaunchKernelGGL.  Every decision was taken by
+// the planner; a plan that names an instantiation a table lacks is refused, never replaced by another kernel. ----
+inline int kx_no_kernel(const KxGemmPlan& k) {
+  kx_set_error("kx_gemm: no kernel is built for the planned instantiation (family %d, element %d, %d x %d tiles, ACT %d, EPI %d, NST %d, "
+               "KS2 %d, BAL %d, COOP %d, PHASED %d)", k.family, k.elem, k.BM, k.BN, k.ACT, k.EPI, k.NST, k.KS2, k.BAL, k.COOP, k.PHASED);
+  return KX_ERR_UNSUPPORTED;
+}
+
 template <typename T, bool PHASED>
-int launch_p3(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = (p.N + 127) / 128;
-  const dim3 grid(p.tiles_m * p.tiles_n), block(512);
-  switch (p.act) {
+int launch_p3(const GemmParams& p, const KxGemmPlan& k, hipStream_t s) {
+  const dim3 grid(k.grid_x), block(k.block);
+  switch (k.ACT) {
     case KX_ACT_NONE: hipLaunchKernelGGL((gemm_kernel_p3<T, KX_ACT_NONE, PHASED>), grid, block, 0, s, p); break;
     case KX_ACT_GELU: hipLaunchKernelGGL((gemm_kernel_p3<T, KX_ACT_GELU, PHASED>), grid, block, 0, s, p); break;
     case KX_ACT_GELU_FAST: hipLaunchKernelGGL((gemm_kernel_p3<T, KX_ACT_GELU_FAST, PHASED>), grid, block, 0, s, p); break;
     case KX_ACT_QUICK_GELU: hipLaunchKernelGGL((gemm_kernel_p3<T, KX_ACT_QUICK_GELU, PHASED>), grid, block, 0, s, p); break;
-    default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
+    default: return kx_no_kernel(k);
   }
   KX_CHECK_LAUNCH("kx_gemm(p3)");
   return KX_OK;
@@ -2321,129 +2327,64 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_p5(const GemmParams p) {
   }  // tiles of this workgroup
 }
 
-// one launch site for both K-loop forms of the 256-row kernel (GemmParams.bal; tuning key 14)
+// one table row of the 256-column kernel: launches when the plan names this (ACT, EPI, KS2), in the planned K-loop form (BAL; tuning key 14)
 template <typename T, int ACT, int BM, int EPI, bool KS2 = false>
-void launch_p5k(const GemmParams& p, dim3 grid, dim3 block, hipStream_t s) {
-  if (p.bal) { hipLaunchKernelGGL((gemm_kernel_p5<T, ACT, BM, EPI, KS2, true>), grid, block, 0, s, p); return; }
-  hipLaunchKernelGGL((gemm_kernel_p5<T, ACT, BM, EPI, KS2, false>), grid, block, 0, s, p);
+bool launch_p5k(const GemmParams& p, const KxGemmPlan& k, dim3 grid, dim3 block, hipStream_t s) {
+  if (k.ACT != ACT || k.EPI != EPI || (k.KS2 != 0) != KS2) return false;
+  if (k.BAL) hipLaunchKernelGGL((gemm_kernel_p5<T, ACT, BM, EPI, KS2, true>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((gemm_kernel_p5<T, ACT, BM, EPI, KS2, false>), grid, block, 0, s, p);
+  return true;
 }
 
-template <typename T, int BM, int EPI>
-int launch_p5e(GemmParams& p, hipStream_t s) {
-  const int nwg = p.tiles_m * p.tiles_n;
-  const dim3 grid(p.persistent > 0 ? (nwg < p.persistent ? nwg : p.persistent) : nwg), block(512);
-  // the lean variants are instantiated for the activations the forward uses them with; anything else takes EPI 0
-  if constexpr (EPI == 9) {                 // fp32 output with residual, bias + folded-LN consume at accumulator level (no activation)
-    launch_p5k<T, KX_ACT_NONE, BM, 9>(p, grid, block, s); KX_CHECK_LAUNCH("kx_gemm(p5)"); return KX_OK;
+// The instantiations of gemm_kernel_p5<T, *, BM, ...> this library is built with (the planner's instantiate_p5 chooses among them).
+template <typename T, int BM>
+int launch_p5(const GemmParams& p, const KxGemmPlan& k, hipStream_t s) {
+  const dim3 grid(k.grid_x), block(k.block);
+#define KX_P5(ACTV, EPIV) launch_p5k<T, ACTV, BM, EPIV>(p, k, grid, block, s)
+  bool hit = KX_P5(KX_ACT_NONE, 0) || KX_P5(KX_ACT_GELU, 0) || KX_P5(KX_ACT_GELU_FAST, 0) || KX_P5(KX_ACT_QUICK_GELU, 0) ||   // generic store loops
+             KX_P5(KX_ACT_NONE, 1) || KX_P5(KX_ACT_GELU_FAST, 1) || KX_P5(KX_ACT_GELU_POLY, 1) || KX_P5(KX_ACT_QUICK_GELU, 1) ||   // lean 16-bit tile store
+             KX_P5(KX_ACT_NONE, 9);                                                                                            // fp32 rows with residual
+  if constexpr (BM == 256) {                  // K split over workgroup pairs
+    hit = hit || launch_p5k<T, KX_ACT_NONE, 256, 9, true>(p, k, grid, block, s) || launch_p5k<T, KX_ACT_NONE, 256, 0, true>(p, k, grid, block, s);
   }
-  if constexpr (EPI == 8) {                 // fp32 output, bias + q-scale + XPos at accumulator level (no activation)
-    if (p.act == KX_ACT_NONE) { launch_p5k<T, KX_ACT_NONE, BM, 8>(p, grid, block, s); KX_CHECK_LAUNCH("kx_gemm(p5)"); return KX_OK; }
-    return launch_p5e<T, BM, 0>(p, s);
-  } else
-  if constexpr (EPI == 6 || EPI == 7) {     // KX_F16C output (BM = 256): plain and GELU, with (7) or without (6) produced statistics
-    if constexpr (kIsF16c<T> && BM == 256) {
-      if (p.act == KX_ACT_NONE) { launch_p5k<T, KX_ACT_NONE, BM, EPI>(p, grid, block, s); KX_CHECK_LAUNCH("kx_gemm(p5)"); return KX_OK; }
-      if constexpr (EPI == 7) {             // (GELU without statistics spills 248 B / lane in this form: it keeps the generic loops)
-        if (p.act == KX_ACT_GELU_FAST) { launch_p5k<T, KX_ACT_GELU_FAST, BM, EPI>(p, grid, block, s); KX_CHECK_LAUNCH("kx_gemm(p5)"); return KX_OK; }
-      }
-    }
-    return launch_p5e<T, BM, 0>(p, s);
-  } else
-  if (p.act == KX_ACT_NONE && EPI != 4) launch_p5k<T, KX_ACT_NONE, BM, EPI>(p, grid, block, s);
-  else if (EPI == 5) return launch_p5e<T, BM, 0>(p, s);
-  else if (p.act == KX_ACT_GELU_FAST && (EPI == 0 || EPI == 1 || EPI == 4)) {
-    constexpr int E = (EPI == 1 || EPI == 4) ? EPI : 0;
-    // plain bf16 in, plain bf16 out, accumulator-level epilogue: the transcendental-free packed GELU (KX_ACT_GELU_POLY); round 5:
-    // plain fp16 in / out too (E == 1: the CLIP tower's fc1 in mixed mode — kx_gemm sets gelu_poly for those launches only)
-    if constexpr ((!kIsF16c<T> && E != 0) || (kIsF16c<T> && E == 1)) {
-      if (p.gelu_poly) launch_p5k<T, KX_ACT_GELU_POLY, BM, E>(p, grid, block, s);
-      else launch_p5k<T, KX_ACT_GELU_FAST, BM, E>(p, grid, block, s);
-    } else {
-      launch_p5k<T, KX_ACT_GELU_FAST, BM, E>(p, grid, block, s);
-    }
+  if constexpr (kIsF16c<T>) {
+    if constexpr (BM == 256) hit = hit || KX_P5(KX_ACT_NONE, 6) || KX_P5(KX_ACT_NONE, 7) || KX_P5(KX_ACT_GELU_FAST, 7);   // KX_F16C three-plane store
+    if constexpr (BM == 192) hit = hit || KX_P5(KX_ACT_NONE, 8);                                                      // fp32 q / k / v with XPos
+  } else {
+    // (KX_ACT_NONE, 4) is built and never planned: statistics without an activation take the generic loops
+    hit = hit || KX_P5(KX_ACT_NONE, 4) || KX_P5(KX_ACT_GELU_FAST, 4) || KX_P5(KX_ACT_GELU_POLY, 4) ||   // lean store + produced statistics
+          KX_P5(KX_ACT_NONE, 5);                                                                      // bf16 rows with XPos
   }
-  else if (p.act == KX_ACT_QUICK_GELU && (EPI == 0 || EPI == 1))
-    launch_p5k<T, KX_ACT_QUICK_GELU, BM, EPI == 1 ? 1 : 0>(p, grid, block, s);
-  else if (EPI != 0) return launch_p5e<T, BM, 0>(p, s);
-  else if (p.act == KX_ACT_NONE) launch_p5k<T, KX_ACT_NONE, BM, 0>(p, grid, block, s);
-  else if (p.act == KX_ACT_GELU) launch_p5k<T, KX_ACT_GELU, BM, 0>(p, grid, block, s);
-  else { kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG; }
-  KX_CHECK_LAUNCH("kx_gemm(p5)");
+#undef KX_P5
+  if (!hit) return kx_no_kernel(k);
+  KX_CHECK_LAUNCH(k.KS2 ? "kx_gemm(p5, pair split-K)" : "kx_gemm(p5)");
   return KX_OK;
 }
 
-template <typename T, int BM>
-int launch_p5(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + 255) / 256;
-  if constexpr (BM == 256) {
-    if (p.pairk) {                            // K split over workgroup pairs (kx_gemm checked: no activation / statistics, even nk, tiles % 8 == 0)
-      const dim3 grid(2 * p.tiles_m * p.tiles_n), block(512);
-      if (p.lean_res) launch_p5k<T, KX_ACT_NONE, 256, 9, true>(p, grid, block, s);
-      else launch_p5k<T, KX_ACT_NONE, 256, 0, true>(p, grid, block, s);
-      KX_CHECK_LAUNCH("kx_gemm(p5, pair split-K)");
-      return KX_OK;
-    }
-  }
-  // lean_xpos: 2 = asked for (tuning key 4 = 3), 1 = eligible — taken on the 192-row tiles, where the rotated accumulators fit
-  // the registers (bf16 qkv at M = 3648: 109.6 -> 93.8 us, bit-identical; the 256-row form spills 352 B / lane and measured slower)
-  const bool lx = p.lean_xpos == 2 || (p.lean_xpos == 1 && BM == 192);
-  if (p.lean_res) return launch_p5e<T, BM, 9>(p, s);
-  if constexpr (kIsF16c<T>) {
-    // KX_F16C output on whole 256-column tiles, no residual / XPos: the three-plane lean store (else the generic loops)
-    if (BM == 256 && p.lean_f16c && p.N % 256 == 0) return p.stats_out ? launch_p5e<T, BM, 7>(p, s) : launch_p5e<T, BM, 6>(p, s);
-    if constexpr (BM == 192) {
-      if (lx && !p.c_bf16 && p.N % 256 == 0) return launch_p5e<T, BM, 8>(p, s);      // fp32 q / k / v of the f16c qkv GEMM
-    }
-    // plain fp16 rows out of fp16 / f16c operands (the CLIP tower's qkv and fc1 in mixed mode): the lean tile store, as for bf16 —
-    // these launches took the generic store loops until round 5 (+16 k cycles per tile: tools/epi_probe.py, profiles/r05_f_*)
-    if (p.lean_epilogue && p.c_f16 && !p.stats_out && p.N % 256 == 0) return launch_p5e<T, BM, 1>(p, s);
-    return launch_p5e<T, BM, 0>(p, s);
-  }
-  else if (lx && p.c_bf16 && p.N % 256 == 0) return launch_p5e<T, BM, 5>(p, s);
-  else if (p.lean_epilogue && p.N % 256 == 0) return p.stats_out ? launch_p5e<T, BM, 4>(p, s) : launch_p5e<T, BM, 1>(p, s);
-  return launch_p5e<T, BM, 0>(p, s);
-}
-
-// CUs of the current device, cached per device ordinal (relaxed atomics: racing first calls store the same value)
-int kx_cu_count() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (n == 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-int launch_splitk_reduce(const GemmParams& p, hipStream_t s) {
-  if (p.ln_out || (p.stats_partials && p.splitk > 1 && !p.ln_g)) {          // row-owning reduce with its fusions
-    const dim3 rg((unsigned)p.M), rb(256);
-    // 16-byte column groups per thread: 2 (N <= 2048: operands prefetched, see splitk_reduce_row) or 8; tuning key 4 = 10: always 8 (A/B)
-    const bool nj2 = p.N <= 2048 && kx_tuning_get(KX_TUNE_GEMM_EPILOGUE) != 10;
-#define KX_RR(ACTV) if (nj2) hipLaunchKernelGGL((splitk_reduce_rows_kernel<ACTV, 2>), rg, rb, 0, s, p); \
-                    else hipLaunchKernelGGL((splitk_reduce_rows_kernel<ACTV, 8>), rg, rb, 0, s, p)
-    switch (p.act) {
+int launch_splitk_reduce(const GemmParams& p, const KxGemmPlan& k, hipStream_t s) {
+  if (k.reduce == KX_REDUCE_ROWS) {          // row-owning reduce with its fusions
+    const dim3 rg(k.reduce_grid), rb(256);
+#define KX_RR(ACTV) if (k.reduce_nj == 2) hipLaunchKernelGGL((splitk_reduce_rows_kernel<ACTV, 2>), rg, rb, 0, s, p); \
+                    else if (k.reduce_nj == 8) hipLaunchKernelGGL((splitk_reduce_rows_kernel<ACTV, 8>), rg, rb, 0, s, p); \
+                    else return kx_no_kernel(k)
+    switch (k.reduce_act) {
       case KX_ACT_NONE: KX_RR(KX_ACT_NONE); break;
       case KX_ACT_GELU: KX_RR(KX_ACT_GELU); break;
       case KX_ACT_GELU_FAST: KX_RR(KX_ACT_GELU_FAST); break;
       case KX_ACT_QUICK_GELU: KX_RR(KX_ACT_QUICK_GELU); break;
-      default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
+      default: return kx_no_kernel(k);
     }
 #undef KX_RR
     KX_CHECK_LAUNCH("kx_gemm(split-K row reduce)");
     return KX_OK;
   }
-  const long long work = (long long)p.M * ((p.N + 3) / 4);
-  const dim3 rgrid((unsigned)((work + 255) / 256)), block(256);
-  switch (p.act) {
+  const dim3 rgrid(k.reduce_grid), block(256);
+  switch (k.reduce_act) {
     case KX_ACT_NONE: hipLaunchKernelGGL(splitk_reduce_kernel<KX_ACT_NONE>, rgrid, block, 0, s, p); break;
     case KX_ACT_GELU: hipLaunchKernelGGL(splitk_reduce_kernel<KX_ACT_GELU>, rgrid, block, 0, s, p); break;
     case KX_ACT_GELU_FAST: hipLaunchKernelGGL(splitk_reduce_kernel<KX_ACT_GELU_FAST>, rgrid, block, 0, s, p); break;
     case KX_ACT_QUICK_GELU: hipLaunchKernelGGL(splitk_reduce_kernel<KX_ACT_QUICK_GELU>, rgrid, block, 0, s, p); break;
-    default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
+    default: return kx_no_kernel(k);
   }
   KX_CHECK_LAUNCH("kx_gemm(split-K reduce)");
   return KX_OK;
@@ -3357,10 +3298,11 @@ inline size_t gemv_lds_bytes(int M, int K, int es, bool ln, bool partials, bool 
 // Up to how many rows the fp32 streaming kernel multiplies on the VALU: measured per decode step (same box, round 3; tuning key
 // 8 = 4 keeps the matrix pipe), B = 1: 1.29 -> 1.17 ms (mixed), 1.62 -> 1.53 (fp32); B = 2: 1.35 -> 1.30; B = 3 / 4: 1.50 / 1.55 either
 // way once the residual GEMMs' staged rows are bounded to two workgroups per CU (unbounded, four rows of fc2 = 66 KB of LDS: 1.64).
-inline int kx_valu_rows() { const int t = kx_tuning_get(KX_TUNE_GEMV_VARIANT); return t >= 10 ? t - 10 : 2; }   // (key 8 = 10 + n: up to n rows, A/B)
+inline int kx_valu_rows(const KxTuning& tn) { const int t = tn.v[KX_TUNE_GEMV_VARIANT]; return t >= 10 ? t - 10 : 2; }   // (key 8 = 10 + n: up to n rows, A/B)
 
 template <typename T>
-int launch_gemv_fused(GemmParams& p, hipStream_t s) {
+int launch_gemv_fused(GemmParams& p, const KxTuning& tn, hipStream_t s) {
+  const int gv = tn.v[KX_TUNE_GEMV_VARIANT];
   constexpr int ES = (int)sizeof(T);
   // waves per workgroup: 8 while a wave's K slice is at most 512 values (bf16: 1 KB of row, fp32: 2 KB), else 16.  Two
   // 512-thread workgroups share a CU and overlap their phases: fp32 rows of K = 2048 on 16 waves (every k-step of a slice
@@ -3368,20 +3310,20 @@ int launch_gemv_fused(GemmParams& p, hipStream_t s) {
   // ... and 16 for LayerNorm-prologue launches of 9..16 rows: the row-in-registers prologue keeps one row per wave, so sixteen
   // sequences need sixteen waves (the three-walk prologue they took before: B = 16 2.00 ms / step in bf16 where B = 8 takes 1.29).
   // A/B: tuning key 8 = 7 keeps 8 waves.
-  const bool rows16 = p.ln_g && p.M > 8 && p.M <= 16 && (p.K >> 2) <= 512 && !p.a_add && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 7;
+  const bool rows16 = p.ln_g && p.M > 8 && p.M <= 16 && (p.K >> 2) <= 512 && !p.a_add && gv != 7;
   const int S = (p.K <= 4096 && !rows16) ? 8 : 16;
   const int kw = ((p.K + S - 1) / S + 31) / 32 * 32;
-  const bool v2 = ES == 4 || kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 1;     // (the first form exists in bf16 only)
+  const bool v2 = ES == 4 || gv != 1;     // (the first form exists in bf16 only)
   // second form, a wave's K slice longer than 8 k-steps (fc2: 512): 16 KB per wave in flight, operand rows through LDS
   // (bf16: 8 k-steps = 256 values; fp32 rows are twice as long — four of them at K = 8192 do not fit beside the rest)
-  const bool deep = ES == 2 ? (v2 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 2 && !p.ln_g && kw > 256 && p.M <= 4 && p.K <= 512 * S)
-                            : (!p.ln_g && kw > 128 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 2);   // fp32: 16 KB per wave in flight, rows via L2
+  const bool deep = ES == 2 ? (v2 && gv != 2 && !p.ln_g && kw > 256 && p.M <= 4 && p.K <= 512 * S)
+                            : (!p.ln_g && kw > 128 && gv != 2);   // fp32: 16 KB per wave in flight, rows via L2
   int x_pitch = 0;
   size_t lds = gemv_lds_bytes(p.M, p.K, ES, p.ln_g != nullptr, p.stats_partials != nullptr, deep && ES == 2, S, &x_pitch);
   // fp32 operands, up to four rows: the products on the VALU (see gemv_fused_kernel2, VAL).  The residual GEMMs' operand
   // rows are staged in LDS for it (two float4 per thread and row: K <= 8 * 64 * S).  Tuning key 8 = 4 keeps the MFMA form.
   p.valu = 0;
-  if (ES == 4 && p.M <= kx_valu_rows() && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 4) {
+  if (ES == 4 && p.M <= kx_valu_rows(tn) && gv != 4) {
     if (p.ln_g) p.valu = 1;
     else if ((p.K >> 2) <= 2 * 64 * S && lds + (size_t)p.M * ((size_t)p.K * 4 + 16) <= 80 * 1024) {   // (two workgroups per CU still fit)
       p.valu = 1;
@@ -3390,10 +3332,10 @@ int launch_gemv_fused(GemmParams& p, hipStream_t s) {
     }
   }
   // block-scaled 16-bit planes and more rows than the VALU form takes: fp16 pieces on the fp16 MFMA (tuning key 8 = 5: exact-f32 MFMA)
-  p.hp = ES == 4 && p.w_tiled == 3 && !p.valu && v2 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 5 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 4;
+  p.hp = ES == 4 && p.w_tiled == 3 && !p.valu && v2 && gv != 5 && gv != 4;
   if (p.a_pieces && !(p.hp && !p.ln_g)) {
     kx_set_error("kx_gemm: w_tiled = 4 (KX_F16P activation rows) needs the fp16-pieces launch (M = %d, tuning key 8 = %d)", p.M,
-                 kx_tuning_get(KX_TUNE_GEMV_VARIANT));
+                 gv);
     return KX_ERR_INVALID_ARG;
   }
   // row-in-registers LayerNorm prologue (5..8 rows): gamma | beta go through 8K bytes of LDS when two workgroups still fit a CU
@@ -3442,97 +3384,49 @@ int launch_gemv_fused(GemmParams& p, hipStream_t s) {
   return KX_OK;
 }
 
+// one table row of gemm_kernel: launches when the plan names this (ACT, EPI, NST, COOP)
+template <typename T, int BM, int BN, int ACT, int EPI = 0, int NST = 2, bool COOP = false>
+bool launch_tile_k(const GemmParams& p, const KxGemmPlan& k, dim3 grid, dim3 block, hipStream_t s) {
+  if (k.ACT != ACT || k.EPI != EPI || k.NST != NST || (k.COOP != 0) != COOP) return false;
+  hipLaunchKernelGGL((gemm_kernel<T, BM, BN, ACT, EPI, NST, COOP>), grid, block, 0, s, p);
+  return true;
+}
+
+// The instantiations of gemm_kernel<T, BM, BN, ...> this library is built with (the planner's instantiate_tile chooses among
+// them), followed by the split-K reduce when the plan has one.
 template <typename T, int BM, int BN>
-int launch(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
-  const dim3 grid(p.tiles_m * p.tiles_n, p.splitk), block(256);
-  if (p.splitk > 1) {
-    // skinny problem: the tile kernels only produce partials (activation-free), the reduce kernel owns the epilogue
-    if constexpr (BM == 64 && BN == 64) {
-      if (p.coop) {                      // ... or the launch reduces them itself (GemmParams.coop)
-#define KX_COOP_LAUNCH(NSTV)                                                                                                   \
-  switch (p.act) {                                                                                                             \
-    case KX_ACT_NONE: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, KX_ACT_NONE, 0, NSTV, true>), grid, block, 0, s, p); break;    \
-    case KX_ACT_GELU: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, KX_ACT_GELU, 0, NSTV, true>), grid, block, 0, s, p); break;    \
-    case KX_ACT_GELU_FAST: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, KX_ACT_GELU_FAST, 0, NSTV, true>), grid, block, 0, s, p); break; \
-    case KX_ACT_QUICK_GELU: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, KX_ACT_QUICK_GELU, 0, NSTV, true>), grid, block, 0, s, p); break; \
-    default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;                                  \
-  }
-        if (p.ring) { KX_COOP_LAUNCH(4) }
-        else {
-          if constexpr (kIsF16c<T>) { KX_COOP_LAUNCH(2) }
-          else { kx_set_error("kx_gemm: the in-launch split-K reduction of this precision needs the ring kernel"); return KX_ERR_UNSUPPORTED; }
-        }
-#undef KX_COOP_LAUNCH
-        KX_CHECK_LAUNCH("kx_gemm(split-K, in-launch reduce)");
-        return KX_OK;
-      }
-      if (p.ring) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE, 0, 4>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE>), grid, block, 0, s, p);
-    } else {
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE>), grid, block, 0, s, p);
+int launch(const GemmParams& p, const KxGemmPlan& k, hipStream_t s) {
+  const dim3 grid(k.grid_x, k.grid_y), block(k.block);
+#define KX_TK(...) launch_tile_k<T, BM, BN, __VA_ARGS__>(p, k, grid, block, s)
+  // the activation is a compile-time property of the kernel: a runtime switch costs ~4 scalar branches per value
+  bool hit = KX_TK(KX_ACT_NONE) || KX_TK(KX_ACT_GELU) || KX_TK(KX_ACT_GELU_FAST) || KX_TK(KX_ACT_QUICK_GELU);
+  if constexpr (BM == 128 && BN == 128) hit = hit || KX_TK(KX_ACT_RELU) || KX_TK(KX_ACT_SWISH);     // relu / swish: this kernel only
+  if constexpr (BM == 64 && BN == 64) {
+    hit = hit || KX_TK(KX_ACT_NONE, 0, 4) || KX_TK(KX_ACT_GELU, 0, 4) || KX_TK(KX_ACT_GELU_FAST, 0, 4) || KX_TK(KX_ACT_QUICK_GELU, 0, 4) ||   // 4-stage ring
+          KX_TK(KX_ACT_NONE, 0, 4, true) || KX_TK(KX_ACT_GELU, 0, 4, true) || KX_TK(KX_ACT_GELU_FAST, 0, 4, true) ||                       // ... reducing in the launch
+          KX_TK(KX_ACT_QUICK_GELU, 0, 4, true);
+    if constexpr (kIsF16c<T>) {               // KX_F16C rows reduce in the launch on two stages
+      hit = hit || KX_TK(KX_ACT_NONE, 0, 2, true) || KX_TK(KX_ACT_GELU, 0, 2, true) || KX_TK(KX_ACT_GELU_FAST, 0, 2, true) ||
+            KX_TK(KX_ACT_QUICK_GELU, 0, 2, true);
     }
-    KX_CHECK_LAUNCH("kx_gemm(split-K)");
-    return launch_splitk_reduce(p, s);
+    if constexpr (sizeof(T) == 2 && !kIsF16c<T>) {     // 8-stage ring: one workgroup per tile walks all of K (bf16 rows)
+      hit = hit || KX_TK(KX_ACT_NONE, 0, 8) || KX_TK(KX_ACT_GELU_FAST, 0, 8) || KX_TK(KX_ACT_QUICK_GELU, 0, 8);
+    }
   }
   if constexpr (BM == 160 && sizeof(T) == 2) {     // the ViT's bf16 / fp16-output GEMMs (qkv, fc1): lean epilogue
-    if (p.lean_epilogue && !p.stats_out && p.N % BN == 0) {
-      if (p.act == KX_ACT_NONE) { hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE, 1>), grid, block, 0, s, p); KX_CHECK_LAUNCH("kx_gemm"); return KX_OK; }
-      if (p.act == KX_ACT_QUICK_GELU) { hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_QUICK_GELU, 1>), grid, block, 0, s, p); KX_CHECK_LAUNCH("kx_gemm"); return KX_OK; }
-      if (p.act == KX_ACT_GELU_FAST) { hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU_FAST, 1>), grid, block, 0, s, p); KX_CHECK_LAUNCH("kx_gemm"); return KX_OK; }
-    }
+    hit = hit || KX_TK(KX_ACT_NONE, 1) || KX_TK(KX_ACT_QUICK_GELU, 1) || KX_TK(KX_ACT_GELU_FAST, 1);
   }
-  if constexpr (BM == 64 && BN == 64 && sizeof(T) == 2 && !kIsF16c<T>) {
-    // unsplit skinny launch whose tiles fit one per CU: the 8-stage ring (128 KB of LDS, six K-tiles in flight) walks all of
-    // K in one workgroup — no partials, no reduce launch (the batch-1 qkv GEMMs: 192 / 240 tiles)
-    if (p.ring == 8) {
-      switch (p.act) {
-        case KX_ACT_NONE: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE, 0, 8>), grid, block, 0, s, p); break;
-        case KX_ACT_GELU_FAST: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU_FAST, 0, 8>), grid, block, 0, s, p); break;
-        case KX_ACT_QUICK_GELU: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_QUICK_GELU, 0, 8>), grid, block, 0, s, p); break;
-        default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
-      }
-      KX_CHECK_LAUNCH("kx_gemm");
-      return KX_OK;
-    }
-  }
-  if constexpr (BM == 64 && BN == 64) {
-    if (p.ring) {
-      switch (p.act) {
-        case KX_ACT_NONE: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE, 0, 4>), grid, block, 0, s, p); break;
-        case KX_ACT_GELU: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU, 0, 4>), grid, block, 0, s, p); break;
-        case KX_ACT_GELU_FAST: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU_FAST, 0, 4>), grid, block, 0, s, p); break;
-        case KX_ACT_QUICK_GELU: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_QUICK_GELU, 0, 4>), grid, block, 0, s, p); break;
-        default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
-      }
-      KX_CHECK_LAUNCH("kx_gemm");
-      return KX_OK;
-    }
-  }
-  // the activation is a compile-time property of the kernel: a runtime switch costs ~4 scalar branches per value
-  switch (p.act) {
-    case KX_ACT_NONE: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_NONE>), grid, block, 0, s, p); break;
-    case KX_ACT_GELU: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU>), grid, block, 0, s, p); break;
-    case KX_ACT_GELU_FAST: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_GELU_FAST>), grid, block, 0, s, p); break;
-    case KX_ACT_QUICK_GELU: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_QUICK_GELU>), grid, block, 0, s, p); break;
-    case KX_ACT_RELU:            // relu / swish: the 128 x 128 kernel only (kx_gemm routes them here)
-      if constexpr (BM == 128 && BN == 128) { hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_RELU>), grid, block, 0, s, p); break; }
-      kx_set_error("kx_gemm: relu is offered by the 128 x 128 tile kernel only"); return KX_ERR_UNSUPPORTED;
-    case KX_ACT_SWISH:
-      if constexpr (BM == 128 && BN == 128) { hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KX_ACT_SWISH>), grid, block, 0, s, p); break; }
-      kx_set_error("kx_gemm: swish is offered by the 128 x 128 tile kernel only"); return KX_ERR_UNSUPPORTED;
-    default: kx_set_error("kx_gemm: unknown activation %d", p.act); return KX_ERR_INVALID_ARG;
-  }
-  KX_CHECK_LAUNCH("kx_gemm");
-  return KX_OK;
+#undef KX_TK
+  if (!hit) return kx_no_kernel(k);
+  KX_CHECK_LAUNCH(k.COOP ? "kx_gemm(split-K, in-launch reduce)" : k.reduce ? "kx_gemm(split-K)" : "kx_gemm");
+  return k.reduce ? launch_splitk_reduce(p, k, s) : KX_OK;
 }
 
 }  // namespace
 
-// per-precision launchers, one translation unit each (tile = the variant kx_gemm chose)
-int kx_gemm_launch_tiles_bf16(GemmParams& p, int tile, hipStream_t s);
-int kx_gemm_launch_phased_bf16(GemmParams& p, int tile, hipStream_t s);
-int kx_gemm_launch_f32(GemmParams& p, int tile, hipStream_t s);
-int kx_gemm_launch_gemv_f32(GemmParams& p, hipStream_t s);   // tile 16 on fp32 operands (kx_gemm_gemv32.hip)
-int kx_gemm_launch_f16c(GemmParams& p, int tile, hipStream_t s);
+// per-precision launchers, one translation unit each: from the plan's resolved tile to the launch table of that tile
+int kx_gemm_launch_tiles_bf16(GemmParams& p, const KxGemmPlan& k, const KxTuning& tn, hipStream_t s);
+int kx_gemm_launch_phased_bf16(GemmParams& p, const KxGemmPlan& k, hipStream_t s);
+int kx_gemm_launch_f32(GemmParams& p, const KxGemmPlan& k, const KxTuning& tn, hipStream_t s);
+int kx_gemm_launch_gemv_f32(GemmParams& p, const KxTuning& tn, hipStream_t s);   // tile 16 on fp32 operands (kx_gemm_gemv32.hip)
+int kx_gemm_launch_f16c(GemmParams& p, const KxGemmPlan& k, hipStream_t s);

@@ -198,6 +198,7 @@ SYMBOLS = {
     "kx_struct_bytes": (C.c_size_t, [i32]),
     "kx_layernorm": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, i64, i64, f32, i64, i64, i64, vp]),
     "kx_gemm": (C.c_int, [C.POINTER(GemmArgs), vp]),
+    "kx_gemm_describe": (C.c_int, [C.POINTER(GemmArgs), C.c_int, C.c_char_p, C.c_size_t]),
     "kx_pair_split_errors": (C.c_int, [C.POINTER(C.c_uint)]),
     "kx_attention": (C.c_int, [C.POINTER(AttnArgs), vp]),
     "kx_row_stats_finalize": (C.c_int, [vp, i64, i64, i64, f32, vp, vp]),

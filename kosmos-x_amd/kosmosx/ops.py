@@ -79,6 +79,20 @@ def gemm(a, w, bias=None, residual=None, act="none", out_dtype=torch.float32, qs
     ln_out = (gamma, beta, eps, dtype) with split-K scratch on a skinny problem: also returns LayerNorm(out) (the
     row-owning reduce kernel); the call then returns (out, ln)."""
     _need_cuda(a, w, bias, residual, out)
+    g, out, lnt, lop = _gemm_args(H.ptr, a, w, bias, residual, act, out_dtype, qscale, qcols, xpos, xpos_dim, tile, out, row_stats,
+                                  colsum, stats_out, splitk_ws, splitk, ln, stats_partials, stats_in_seg, stats_eps, stats_out_seg,
+                                  out_x3, ln_out, ln_operand, w_tiled_rows, ksplit, out2, residual2, a_add, out_pieces, a_pieces,
+                                  pair_ws, splitk_flags)
+    H.check(H.load().kx_gemm(C.byref(g), _stream()), "kx_gemm")
+    if lop is not None:
+        return (out,) + lop
+    return out if lnt is None else (out, lnt)
+
+
+def _gemm_args(ptr, a, w, bias, residual, act, out_dtype, qscale, qcols, xpos, xpos_dim, tile, out, row_stats, colsum, stats_out,
+               splitk_ws, splitk, ln, stats_partials, stats_in_seg, stats_eps, stats_out_seg, out_x3, ln_out, ln_operand,
+               w_tiled_rows, ksplit, out2, residual2, a_add, out_pieces, a_pieces, pair_ws, splitk_flags):
+    """kx_gemm_args of a gemm() call and the outputs it allocates; `ptr` turns a tensor into an address (gemm_describe: a fake one)."""
     M, K = a.shape
     N = w_tiled_rows or w.shape[0]                 # w_tiled_rows = N: `w` is tile_weight_rows(W) (tile 16 only)
     prec = H.KX_PREC_BF16 if w.dtype == torch.bfloat16 else H.KX_PREC_F16 if w.dtype == torch.float16 else H.KX_PREC_F32
@@ -87,59 +101,56 @@ def gemm(a, w, bias=None, residual=None, act="none", out_dtype=torch.float32, qs
     if out is None:
         out = torch.empty((M, 3 * N if out_x3 else N), dtype=torch.bfloat16 if out_x3 else out_dtype, device=a.device)
     g = H.GemmArgs()
-    g.A, g.lda, g.W, g.ldw = H.ptr(a), a.stride(0), H.ptr(w), (K if w_tiled_rows else w.stride(0))
+    g.A, g.lda, g.W, g.ldw = ptr(a), a.stride(0), ptr(w), (K if w_tiled_rows else w.stride(0))
     # uint8 tiles: 24-bit planes (tile_weight_rows_w24, 1536-byte blocks) or block-scaled 16-bit weights (_w16, 1088-byte blocks)
     g.w_tiled = ((3 if w.shape[-1] == 1088 else 2) if w.dtype == torch.uint8 else 1) if w_tiled_rows else 0
-    g.C, g.ldc, g.cdt = H.ptr(out), out.stride(0), (H.KX_BF16X3 if out_x3 else H.KX_F16P if out_pieces else _cdt(out.dtype))
+    g.C, g.ldc, g.cdt = ptr(out), out.stride(0), (H.KX_BF16X3 if out_x3 else H.KX_F16P if out_pieces else _cdt(out.dtype))
     if a_pieces:                                   # `a` holds KX_F16P rows (f16_pieces_rows, or a producer's out_pieces output)
         assert g.w_tiled == 3, "a_pieces rides on the block-scaled 16-bit planes"
         g.w_tiled = 4
-    g.bias, g.residual, g.ldr = H.ptr(bias), H.ptr(residual), (residual.stride(0) if residual is not None else 0)
+    g.bias, g.residual, g.ldr = ptr(bias), ptr(residual), (residual.stride(0) if residual is not None else 0)
     g.M, g.N, g.K = M, N, K
     g.act, g.qscale, g.qcols = H.ACTS[act], float(qscale), qcols
     if xpos is not None:
-        g.xq_cs, g.xq_ss, g.xk_cs, g.xk_ss = (H.ptr(t) for t in xpos)
+        g.xq_cs, g.xq_ss, g.xk_cs, g.xk_ss = (ptr(t) for t in xpos)
         g.xpos_T, g.xpos_dim = xpos[0].shape[0], xpos_dim
     g.prec, g.tile = prec, tile
-    g.row_stats, g.colsum, g.stats_out = H.ptr(row_stats), H.ptr(colsum), H.ptr(stats_out)
+    g.row_stats, g.colsum, g.stats_out = ptr(row_stats), ptr(colsum), ptr(stats_out)
     if splitk_ws is not None:
-        g.splitk_ws, g.splitk_ws_bytes, g.splitk = H.ptr(splitk_ws), splitk_ws.numel() * splitk_ws.element_size(), splitk
+        g.splitk_ws, g.splitk_ws_bytes, g.splitk = ptr(splitk_ws), splitk_ws.numel() * splitk_ws.element_size(), splitk
     if pair_ws is not None:         # scratch of the 256x256 kernel's pair split (first 4 KB zero: pair_scratch())
-        g.pair_ws, g.pair_ws_bytes = H.ptr(pair_ws), pair_ws.numel() * pair_ws.element_size()
+        g.pair_ws, g.pair_ws_bytes = ptr(pair_ws), pair_ws.numel() * pair_ws.element_size()
     if splitk_flags is not None:    # >= 2 x CUs int32 words (splitk_flags()): the split-K launch reduces its partials itself
-        g.splitk_flags = H.ptr(splitk_flags)
+        g.splitk_flags = ptr(splitk_flags)
     if ln is not None:
-        g.ln_gamma, g.ln_beta, g.ln_eps = H.ptr(ln[0]), H.ptr(ln[1]), float(ln[2])
+        g.ln_gamma, g.ln_beta, g.ln_eps = ptr(ln[0]), ptr(ln[1]), float(ln[2])
     if stats_partials is not None:
-        g.stats_partials, g.stats_in_nseg = H.ptr(stats_partials), stats_partials.shape[1]
+        g.stats_partials, g.stats_in_nseg = ptr(stats_partials), stats_partials.shape[1]
         g.stats_in_seg, g.stats_eps = stats_in_seg, float(stats_eps)
         if row_stats is not None and tile != 16:      # tile kernels: `row_stats` is the [M, 2] OUTPUT scratch of the finalize pass (ABI 7)
-            g.row_stats, g.row_stats_scratch = None, H.ptr(row_stats)
+            g.row_stats, g.row_stats_scratch = None, ptr(row_stats)
     g.stats_out_seg = stats_out_seg
     # tile 16, the residual stream as a pair (kx_gemm_args.ksplit): out2 receives part 1's product
-    g.ksplit, g.C2, g.residual2, g.a_add = ksplit, H.ptr(out2), H.ptr(residual2), H.ptr(a_add)
+    g.ksplit, g.C2, g.residual2, g.a_add = ksplit, ptr(out2), ptr(residual2), ptr(a_add)
     lnt = None
     if ln_out is not None:
         lnt = torch.empty((M, N), dtype=ln_out[3], device=a.device)
-        g.ln_out, g.ln_out_dt = H.ptr(lnt), _cdt(ln_out[3])
-        g.ln_out_gamma, g.ln_out_beta, g.ln_out_eps = H.ptr(ln_out[0]), H.ptr(ln_out[1]), float(ln_out[2])
+        g.ln_out, g.ln_out_dt = ptr(lnt), _cdt(ln_out[3])
+        g.ln_out_gamma, g.ln_out_beta, g.ln_out_eps = ptr(ln_out[0]), ptr(ln_out[1]), float(ln_out[2])
     lop = None
     if ln_operand is not None:      # dtype of the operand copy: torch.bfloat16 / torch.float16 / "f16c"
-        lop = _ln_operand_buffers(g, ln_operand, M, N, a.device)
-    H.check(H.load().kx_gemm(C.byref(g), _stream()), "kx_gemm")
-    if lop is not None:
-        return (out,) + lop
-    return out if lnt is None else (out, lnt)
+        lop = _ln_operand_buffers(g, ln_operand, M, N, a.device, ptr)
+    return g, out, lnt, lop
 
 
-def _ln_operand_buffers(g, dt, M, N, device):
+def _ln_operand_buffers(g, dt, M, N, device, ptr=H.ptr):
     """Folded pre-LayerNorm producer outputs: (operand copy of the finished rows, partial statistics [M, N/64, 2])."""
     if dt == "f16c":
         cp, g.ln_operand_dt = torch.empty((M, 4 * N), dtype=torch.uint8, device=device), H.KX_F16C
     else:
         cp, g.ln_operand_dt = torch.empty((M, N), dtype=dt, device=device), _cdt(dt)
     st = torch.zeros((M, N // 64, 2), dtype=torch.float32, device=device)
-    g.ln_operand_out, g.ln_operand_stats = H.ptr(cp), H.ptr(st)
+    g.ln_operand_out, g.ln_operand_stats = ptr(cp), ptr(st)
     return cp, st
 
 
@@ -246,37 +257,85 @@ def gemm_f16c(a_rows, w_packed, N, K, bias=None, residual=None, act="none", out_
     (N rows of 4K bytes + N scale bytes, model._operand_f16c).  Output fp32 [M, N] or KX_F16C rows [M, 4N] uint8.
     out_hilo (with xpos): the fp32-shaped output holds KX_F16HL head slots — [64 fp16 hi | 64 fp16 lo] of 2^8 x per 64 columns."""
     _need_cuda(a_rows, w_packed, bias, residual)
+    g, out, lop = _gemm_f16c_args(H.ptr, a_rows, w_packed, N, K, bias, residual, act, out_f16c, qscale, qcols, xpos, xpos_dim, tile,
+                                  row_stats, colsum, stats_out, splitk_ws, splitk, ln_operand, pair_ws, out_hilo, stats_partials,
+                                  stats_in_seg, stats_eps, corr, splitk_flags)
+    H.check(H.load().kx_gemm(C.byref(g), _stream()), "kx_gemm")
+    return out if lop is None else (out,) + lop
+
+
+def _gemm_f16c_args(ptr, a_rows, w_packed, N, K, bias, residual, act, out_f16c, qscale, qcols, xpos, xpos_dim, tile, row_stats,
+                    colsum, stats_out, splitk_ws, splitk, ln_operand, pair_ws, out_hilo, stats_partials, stats_in_seg, stats_eps,
+                    corr, splitk_flags):
+    """kx_gemm_args of a gemm_f16c() call and the outputs it allocates (see _gemm_args)."""
     M = a_rows.shape[0]
     assert a_rows.dtype == torch.uint8 and a_rows.shape[1] == 4 * K and w_packed.numel() >= N * 4 * K + N
     out = (torch.empty((M, 4 * N), dtype=torch.uint8, device=a_rows.device) if out_f16c else
            torch.empty((M, N), dtype=torch.float32, device=a_rows.device))
     g = H.GemmArgs()
-    g.A, g.lda, g.W, g.ldw = H.ptr(a_rows), a_rows.stride(0) // 2, H.ptr(w_packed), 2 * K
-    g.C, g.ldc, g.cdt = H.ptr(out), (2 * N if out_f16c else out.stride(0)), (H.KX_F16C if out_f16c else H.KX_F16HL if out_hilo else H.KX_F32)
-    g.w_scale = w_packed.data_ptr() + N * 4 * K
-    g.bias, g.residual, g.ldr = H.ptr(bias), H.ptr(residual), (residual.stride(0) if residual is not None else 0)
+    g.A, g.lda, g.W, g.ldw = ptr(a_rows), a_rows.stride(0) // 2, ptr(w_packed), 2 * K
+    g.C, g.ldc, g.cdt = ptr(out), (2 * N if out_f16c else out.stride(0)), (H.KX_F16C if out_f16c else H.KX_F16HL if out_hilo else H.KX_F32)
+    g.w_scale = ptr(w_packed) + N * 4 * K
+    g.bias, g.residual, g.ldr = ptr(bias), ptr(residual), (residual.stride(0) if residual is not None else 0)
     g.M, g.N, g.K = M, N, K
     g.act, g.qscale, g.qcols = H.ACTS[act], float(qscale), qcols
     if xpos is not None:
-        g.xq_cs, g.xq_ss, g.xk_cs, g.xk_ss = (H.ptr(t) for t in xpos)
+        g.xq_cs, g.xq_ss, g.xk_cs, g.xk_ss = (ptr(t) for t in xpos)
         g.xpos_T, g.xpos_dim = xpos[0].shape[0], xpos_dim
     g.prec, g.tile = H.KX_PREC_F16C, tile
-    g.row_stats, g.colsum, g.stats_out = H.ptr(row_stats), H.ptr(colsum), H.ptr(stats_out)
+    g.row_stats, g.colsum, g.stats_out = ptr(row_stats), ptr(colsum), ptr(stats_out)
     if stats_partials is not None:      # with row_stats (the OUTPUT scratch, kx_gemm_args.row_stats_scratch): finalised by kx_gemm's own pass
-        g.stats_partials, g.stats_in_nseg = H.ptr(stats_partials), stats_partials.shape[1]
+        g.stats_partials, g.stats_in_nseg = ptr(stats_partials), stats_partials.shape[1]
         g.stats_in_seg, g.stats_eps = stats_in_seg, float(stats_eps)
         if row_stats is not None:
-            g.row_stats, g.row_stats_scratch = None, H.ptr(row_stats)
+            g.row_stats, g.row_stats_scratch = None, ptr(row_stats)
     g.f16c_corr = {"both": 0, "weight": 1, "act": 2, "none": 3}[corr]
     if splitk_ws is not None:
-        g.splitk_ws, g.splitk_ws_bytes, g.splitk = H.ptr(splitk_ws), splitk_ws.numel() * splitk_ws.element_size(), splitk
+        g.splitk_ws, g.splitk_ws_bytes, g.splitk = ptr(splitk_ws), splitk_ws.numel() * splitk_ws.element_size(), splitk
     if pair_ws is not None:
-        g.pair_ws, g.pair_ws_bytes = H.ptr(pair_ws), pair_ws.numel() * pair_ws.element_size()
+        g.pair_ws, g.pair_ws_bytes = ptr(pair_ws), pair_ws.numel() * pair_ws.element_size()
     if splitk_flags is not None:
-        g.splitk_flags = H.ptr(splitk_flags)
-    lop = _ln_operand_buffers(g, ln_operand, M, N, a_rows.device) if ln_operand is not None else None
-    H.check(H.load().kx_gemm(C.byref(g), _stream()), "kx_gemm")
-    return out if lop is None else (out,) + lop
+        g.splitk_flags = ptr(splitk_flags)
+    lop = _ln_operand_buffers(g, ln_operand, M, N, a_rows.device, ptr) if ln_operand is not None else None
+    return g, out, lop
+
+
+def gemm_describe(*args, cu_count=0, **kw):
+    """What kx_gemm would launch for a gemm(...) call — or, with (a_rows, w_packed, N, K, ...), a gemm_f16c(...) call — without
+    launching anything: the same positional and keyword arguments, tensors on any device (`meta` tensors do; no operand is read).
+    cu_count: the CU count to plan for (0 = the current device's, 256 without one).  Returns the parsed lines: a list of launches
+    {"kernel", "args", "grid", "block"} (the finalize and weight-streaming launches carry their family name only) and the
+    dict of the resolved tile and host flags.  A call kx_gemm would refuse raises with the same code and message."""
+    def ptr(t):      # operands are never dereferenced: real addresses where there are any, else one fake 1 MB-aligned address
+        return None if t is None else (t.data_ptr() if t.device.type != "meta" else 1 << 20)
+    import inspect
+    rows = args[0] if args else kw.get("a_rows")             # KX_F16C activation rows are uint8: gemm_f16c's form
+    fn, build = (gemm_f16c, _gemm_f16c_args) if rows is not None and rows.dtype == torch.uint8 else (gemm, _gemm_args)
+    b = inspect.signature(fn).bind(*args, **kw)
+    b.apply_defaults()
+    g = build(ptr, **b.arguments)[0]
+    buf = C.create_string_buffer(4096)
+    H.check(H.load().kx_gemm_describe(C.byref(g), int(cu_count), buf, len(buf)), "kx_gemm_describe")
+    return parse_gemm_description(buf.value.decode())
+
+
+def parse_gemm_description(text):
+    """kx_gemm_describe's text -> (launches, plan)."""
+    import re
+    launches, plan = [], {}
+    for line in text.strip().splitlines():
+        if line.startswith("plan "):
+            plan = {k: int(v) for k, v in (f.split("=") for f in line.split()[1:])}
+            continue
+        m = re.fullmatch(r"(\w+)<(.*)> grid=(\d+)x(\d+) block=(\d+)(?: lds=(\d+))?", line)
+        if m is None:
+            launches.append({"kernel": line})
+        else:
+            launches.append({"kernel": m.group(1), "args": [a.strip() for a in m.group(2).split(",")],
+                             "grid": [int(m.group(3)), int(m.group(4))], "block": int(m.group(5))})
+            if m.group(6) is not None:       # (a kernel trace's static + dynamic bytes: tests/golden/gemm_plan.json)
+                launches[-1]["lds"] = int(m.group(6))
+    return launches, plan
 
 
 def pair_scratch(device="cuda", workgroups=256):

@@ -31,6 +31,9 @@ def _case(kind, M, N, K, seed, epi):
         def call(tile, ws):
             r = res0.clone() if res0 is not None else None
             return ops.gemm_f16c(a, wp, N, K, residual=r, tile=tile, pair_ws=ws, **kw)
+
+        def describe(tile, ws):
+            return ops.gemm_describe(a, wp, N, K, residual=res0, tile=tile, pair_ws=ws, **kw)
     else:
         dt = torch.bfloat16 if kind == "bf16" else torch.float16
         a, wd = x.to(dt), w.to(dt)
@@ -38,6 +41,10 @@ def _case(kind, M, N, K, seed, epi):
         def call(tile, ws):
             r = res0.clone() if res0 is not None else None
             return ops.gemm(a, wd, residual=r, out=r, tile=tile, pair_ws=ws, **kw)
+
+        def describe(tile, ws):
+            return ops.gemm_describe(a, wd, residual=res0, out=res0, tile=tile, pair_ws=ws, **kw)
+    call.describe = describe                          # what the same call would launch (kx_gemm_describe)
     return call
 
 
@@ -81,6 +88,10 @@ def test_pair_split_automatic_choice_and_refusals():
         call = _case(kind, 3648, 2048, K, seed=5, epi="fold")
         auto, pair, ring = call(0, ws).float(), call(1024, ws).float(), call(256, ws).float()
         assert torch.equal(auto, pair) == taken and torch.equal(auto, ring) == (not taken), (kind, K)
+        launches, plan = call.describe(0, ws)         # ... and the plan says so before anything runs
+        assert plan["pairk"] == int(taken) and plan["tile"] == (512 if taken else 256), (kind, K, plan)
+        main = launches[-1]                          # (the fold epilogue's statistics are given: no finalize launch, no reduce)
+        assert main["kernel"] == ("gemm_kernel_p5" if taken else "gemm_kernel_p3") and (not taken or main["args"][4] == "true"), main
     with pytest.raises(RuntimeError, match="pair split"):      # a full round of tiles already: 2 x 240 workgroups do not fit
         _case("bf16", 3648, 4096, 2048, seed=6, epi="plain")(1024, ws)
     with pytest.raises(RuntimeError, match="pair split"):      # no scratch
