@@ -849,6 +849,47 @@ int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int
                      const int64_t* target, float* out, int64_t rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoding rows over a shared, read-only prefix cache plus a private tail cache (added within ABI 7: two functions are appended; no
+ * struct, no existing layout moves and the kx_struct_id list is unchanged, so kx_version() stays 7).
+ *
+ * M rows — the n sampled continuations of each of Bp prompts, say — decode one token each.  A row's first keys are rows of a prefix
+ * cache that a prefill of Bp sequences left and that nobody writes; the keys it produced itself live in a small tail cache of its own.
+ *
+ * kx_attention_decode_prefix: kx_attention_decode_ragged's rows — one query per (row, head) — with three int32 device words per
+ *   row r: t = positions[r] (the number of keys before the new one), c = prefix_seq[r] and P = prefix_len[r].  Row r attends over
+ *   keys 0 .. t: keys 0 .. P - 1 are rows 0 .. P - 1 of sequence c of the prefix caches [Bp, heads, Tmax, 64] (const: the launch has no
+ *   store to them, they are bitwise unchanged), keys P .. t - 1 are rows 0 .. t - P - 1 of sequence r of the tail caches
+ *   [M, heads, Ttail, 64], key t is the new token's, read from the qkv row.  The launch appends the new k / v to tail row t - P of
+ *   sequence r and writes no other tail row.  Several rows may name the same c, with the same or different P; P = 0 reads the tail
+ *   alone.  Same slots, key order and arithmetic on t, only the address a key is loaded from differs: one launch gives, bit for
+ *   bit, the outputs and stats_out of kx_attention_decode_ragged on a private cache whose rows 0 .. P - 1 are the prefix rows and
+ *   rows P .. t - 1 the tail rows, and the appended tail row is that launch's cache row t; every output form (KX_F32, KX_BF16,
+ *   KX_F16C, KX_F16P), both cache dtypes, both layouts (tuning key 9, applied to both caches).  The three words are requested
+ *   together: one scalar round trip before the one vector round trip.  A row with c outside [0, Bp), P < 0, P > Tmax, t < P or
+ *   t - P >= Ttail writes nothing (no output, no statistics, no tail row) and ORs KX_RAGGED_ERR_CACHE into *error_word; the other
+ *   rows are unaffected.  Host checks (KX_ERR_INVALID_ARG, nothing launched): null pointers, M or H empty or over the grid limits
+ *   (65535), Bp / Tmax / Ttail outside 1 .. 2^31 - 1, the precision / output-form pairs of kx_attention_decode.
+ * kx_decoder_decode_step_prefix: kx_decoder_decode_step_ragged with M rows, the const prefix caches [L, Bp, heads, Tmax, 64] and the
+ *   tail caches [L, M, heads, Ttail, 64]: kx_step_prepare on the M tokens and positions (pos_shift as there; the XPos tables
+ *   [Tmax, 32] and max_pos keep their own row counts), the qkv launch with xpos_T = M, kx_attention_decode_prefix in place of the
+ *   ragged attention, everything else row-wise.  Up to 16 rows the step streams the weights, above that it runs the tile GEMMs.
+ *   x [M, 1, dim] and xpos_rows [4, M, 32] scratch zeroed once by the caller; logits [M, vocab]; workspace =
+ *   kx_decoder_workspace_bytes(w, M, 1, prec).
+ * Neither allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int kx_attention_decode_prefix(const void* qkv, const void* kprefix, const void* vprefix, void* ktail, void* vtail, void* out,
+                               int32_t odt, float* stats_out, int64_t M, int64_t H, const int32_t* positions,
+                               const int32_t* prefix_seq, const int32_t* prefix_len, int64_t Bp, int64_t Tmax, int64_t Ttail,
+                               int32_t prec, int32_t* error_word, void* stream);
+int kx_decoder_decode_step_prefix(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                  int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t M,
+                                  const int32_t* positions, const int32_t* prefix_seq, const int32_t* prefix_len, int64_t Bp,
+                                  const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss, float* xpos_rows,
+                                  const void* kprefix, const void* vprefix, int64_t Tmax, void* ktail, void* vtail, int64_t Ttail,
+                                  void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec,
+                                  int32_t* error_word, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chunked prefill: append MANY rows to filled caches in one pass over the forward's tile GEMMs and flash attention (added
  * within ABI 7: functions only).  P is a host scalar, the number of rows every sequence already has in the caches; P = 0 is allowed.
  *

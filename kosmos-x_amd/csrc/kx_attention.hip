@@ -1195,6 +1195,14 @@ struct RaggedParams { const int* positions; int* err; int Tmax; };
 struct BlockParams { int K; };
 // the shared form (a third pack member): candidate z of the launch reads cache sequence cache_seq[z] of Bc and appends nothing
 struct SharedParams { const int* cache_seq; int Bc; };
+// the prefix form (the pack RaggedParams, PrefixParams): row r reads keys 0 .. prefix_len[r] - 1 from sequence prefix_seq[r] of a read-only
+// prefix cache [Bp, heads, Tp, 64] and the keys after them from its own sequence of the tail cache (DecodeParams.kcache / vcache:
+// [M, heads, Ttail, 64], the caches the launch appends to).  batch / head: the prefix caches' element strides; the row stride is the tails'.
+struct PrefixParams {
+  const int* prefix_seq; const int* prefix_len; const char* kprefix; const char* vprefix; long long batch, head; int Bp, Tp, Ttail;
+};
+template <typename... R> struct is_prefix_pack { static constexpr bool value = false; };
+template <> struct is_prefix_pack<RaggedParams, PrefixParams> { static constexpr bool value = true; };
 template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
 template <typename A, typename B2, typename... Rest> __device__ __forceinline__ const B2& second_arg(const A&, const B2& b, const Rest&...) { return b; }
 template <typename A, typename B2, typename C2, typename... Rest> __device__ __forceinline__ const C2& third_arg(const A&, const B2&, const C2& c, const Rest&...) { return c; }
@@ -1216,10 +1224,13 @@ template <> struct Ld4<float> {
 
 // One round of a slot's keys and values, j0 + 16u for u < UK, into kr / vr (slots past the end re-read the last key and drop it).
 // Key t is the new token's, read from the qkv row (knew / vnew) and not back through the cache.
-template <typename T, bool BLOCK>
+// PREFIX: keys j < P come from the prefix caches (kp / vp), keys P .. t - 1 from the tail caches, whose bases kc / vc arrive moved back by
+// P rows — so key j sits at row offset j behind either base, and the one thing PREFIX adds per key is the select of the base.
+template <typename T, bool BLOCK, bool PREFIX = false>
 __device__ __forceinline__ void load_kv_round(typename Ld4<T>::raw (&kr)[Ld4<T>::UK], typename Ld4<T>::raw (&vr)[Ld4<T>::UK], const int j0,
                                               const int t, const int t0, const char* knew, const char* vnew, const char* kc,
-                                              const char* vc, const long long qkv_row, const long long cache_row) {
+                                              const char* vc, const long long qkv_row, const long long cache_row,
+                                              const char* kp = nullptr, const char* vp = nullptr, const int P = 0) {
   typedef typename Ld4<T>::raw raw;
   const long long es = sizeof(T);
 #pragma unroll
@@ -1229,6 +1240,10 @@ __device__ __forceinline__ void load_kv_round(typename Ld4<T>::raw (&kr)[Ld4<T>:
       const long long back = (long long)(t - j) * qkv_row * es;
       kr[u] = *reinterpret_cast<const raw*>(j >= t0 ? knew - back : kc + (long long)j * cache_row * es);
       vr[u] = *reinterpret_cast<const raw*>(j >= t0 ? vnew - back : vc + (long long)j * cache_row * es);
+    } else if constexpr (PREFIX) {
+      const long long off = (long long)j * cache_row * es;
+      kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : (j < P ? kp : kc) + off);
+      vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : (j < P ? vp : vc) + off);
     } else {
       kr[u] = *reinterpret_cast<const raw*>(j == t ? knew : kc + (long long)j * cache_row * es);
       vr[u] = *reinterpret_cast<const raw*>(j == t ? vnew : vc + (long long)j * cache_row * es);
@@ -1262,10 +1277,21 @@ __device__ __forceinline__ void load_kv_round(typename Ld4<T>::raw (&kr)[Ld4<T>:
 // append: the caches are read only, so candidates of one sequence never meet.  cache_seq[z] is requested with the two position words
 // (still one scalar round trip) and checked with them, bitwise; what BLOCK computes on `t`, `t0` and the cache base is untouched,
 // hence the bits of the block launch on a cache replicated per candidate.  Everything SHARED adds sits under `if constexpr (SHARED)`.
+// PREFIX (R = RaggedParams, PrefixParams; kx_attention_decode_prefix): RAGGED's rows — grid (H, M), one row per workgroup at
+// t = positions[r] — whose keys 0 .. P - 1 (P = prefix_len[r]) are rows of sequence prefix_seq[r] of a read-only prefix cache that
+// several rows may name, and whose keys P .. t - 1 are rows 0 .. t - P - 1 of the row's own sequence of a small tail cache; key t is
+// the qkv row's and is appended to tail row t - P.  The three words are requested together (one scalar round trip) and checked
+// together, bitwise: a row with prefix_seq outside [0, Bp), P outside [0, Tp], t < P or t - P >= Ttail writes nothing and sets
+// KX_RAGGED_ERR_CACHE.  Slots, key order and the arithmetic on `t` are RAGGED's — only the address a key is loaded from differs —
+// hence the bits of the ragged launch on a private cache assembled from the prefix rows and the tail rows.  No store addresses the
+// prefix caches.  Everything PREFIX adds sits under `if constexpr (PREFIX)`.
+// gfx950 resource usage of the two PREFIX instantiations (-Rpass-analysis=kernel-resource-usage): bf16 cache 140 VGPRs, 3 waves / SIMD;
+// fp32 cache 120 VGPRs, 4 waves / SIMD; no scratch, no spill in either — the occupancy of the ragged instantiations (155 / 122 VGPRs).
 template <typename T, typename... R>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, const R... r) {
   constexpr bool RAGGED = sizeof...(R) != 0;
-  constexpr bool BLOCK = sizeof...(R) >= 2;
+  constexpr bool PREFIX = is_prefix_pack<R...>::value;
+  constexpr bool BLOCK = sizeof...(R) >= 2 && !PREFIX;
   constexpr bool SHARED = sizeof...(R) == 3;
   __shared__ float sm_m[16], sm_l[16], sm_o[16][64];
   typedef typename Ld4<T>::raw raw;
@@ -1276,7 +1302,19 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   int b = blockIdx.y;                                       // the launch's row (BLOCK: set below)
   int t = p.t;
   int cb = b, t0 = 0;                                       // BLOCK: the cache sequence of row b and its first position
-  if constexpr (BLOCK) {                                    // grid (H, K, B): row b = sequence z's y-th; both positions are requested together
+  [[maybe_unused]] int pc = 0, P = 0;                       // PREFIX: the row's prefix sequence and its number of prefix keys
+  if constexpr (PREFIX) {                                   // the row's three words: one scalar round trip
+    const RaggedParams& rp = first_arg(r...);
+    const PrefixParams& pp = second_arg(r...);
+    t = rp.positions[b];
+    pc = pp.prefix_seq[b];
+    P = pp.prefix_len[b];
+    // (one condition on the three words, bitwise and in 64 bits: evaluated after ALL loads are back; uniform over the workgroup)
+    if ((pc < 0) | (pc >= pp.Bp) | (P < 0) | (P > pp.Tp) | (t < P) | ((long long)t - P >= (long long)pp.Ttail)) {
+      if (tid == 0) atomicOr(rp.err, KX_RAGGED_ERR_CACHE);
+      return;
+    }
+  } else if constexpr (BLOCK) {                                    // grid (H, K, B): row b = sequence z's y-th; both positions are requested together
     const RaggedParams& rp = first_arg(r...);
     const int jr = blockIdx.y;
     cb = blockIdx.z;
@@ -1308,11 +1346,22 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   char* vc = p.vcache + ((long long)cb * p.cache_batch + (long long)h * p.cache_head + 4 * li) * es;
   const char* knew = qrow + (long long)p.D * es;          // the new token (key t): k | v of the qkv row
   const char* vnew = qrow + 2ll * p.D * es;
+  [[maybe_unused]] const char *kp = nullptr, *vp = nullptr;
+  if constexpr (PREFIX) {                                   // tail bases moved back by P rows (as integers: the moved base is no object's address)
+    const PrefixParams& pp = second_arg(r...);
+    const long long poff = ((long long)pc * pp.batch + (long long)h * pp.head + 4 * li) * es;
+    kp = pp.kprefix + poff;
+    vp = pp.vprefix + poff;
+    const long long backP = (long long)P * p.cache_row * es;
+    kc = reinterpret_cast<char*>(reinterpret_cast<uintptr_t>(kc) - (uintptr_t)backP);
+    vc = reinterpret_cast<char*>(reinterpret_cast<uintptr_t>(vc) - (uintptr_t)backP);
+  }
   const int nkeys = t + 1;
   const int slot = wave * 4 + grp;
   const raw qr = *reinterpret_cast<const raw*>(qrow);
   raw kr[UK], vr[UK];
-  load_kv_round<T, BLOCK>(kr, vr, slot, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);
+  if constexpr (PREFIX) load_kv_round<T, false, true>(kr, vr, slot, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row, kp, vp, P);
+  else load_kv_round<T, BLOCK>(kr, vr, slot, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);
   if constexpr (!SHARED) {
     if (wave == 0 && grp < 2) {                            // append row t: 64 k + 64 v elements per head
       const raw nv = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
@@ -1323,7 +1372,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeParams p, 
   Ld4<T>::unpack(qr, q);
   float m = -INFINITY, l = 0.f, o[4] = {0.f, 0.f, 0.f, 0.f};
   for (int j0 = slot; j0 < nkeys; j0 += 16 * UK) {
-    if (j0 != slot) load_kv_round<T, BLOCK>(kr, vr, j0, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);   // contexts beyond the first round: one more round trip each
+    if (j0 != slot) {                                       // contexts beyond the first round: one more round trip each
+      if constexpr (PREFIX) load_kv_round<T, false, true>(kr, vr, j0, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row, kp, vp, P);
+      else load_kv_round<T, BLOCK>(kr, vr, j0, t, t0, knew, vnew, kc, vc, p.qkv_row, p.cache_row);
+    }
 #pragma unroll
     for (int u = 0; u < UK; ++u) {
       if (j0 + 16 * u < nkeys) {
@@ -1587,4 +1639,43 @@ extern "C" int kx_attention_decode_shared(const void* qkv, const void* kcache, c
   // (the kernel's shared form has no store to the caches: the append is compiled out)
   return attention_decode_impl("kx_attention_decode_shared", qkv, const_cast<void*>(kcache), const_cast<void*>(vcache), out, odt, stats_out,
                                C * K, H, 0, positions, error_word, Tmax, prec, stream, K, cache_seq, Bc);
+}
+
+// The prefix launch: M rows, row r at positions[r] over prefix_len[r] rows of prefix sequence prefix_seq[r] and its own tail sequence
+// (see attn_decode_kernel, PREFIX).  Tuning key 9 lays out both caches.
+extern "C" int kx_attention_decode_prefix(const void* qkv, const void* kprefix, const void* vprefix, void* ktail, void* vtail, void* out,
+                                          int32_t odt, float* stats_out, int64_t M, int64_t H, const int32_t* positions,
+                                          const int32_t* prefix_seq, const int32_t* prefix_len, int64_t Bp, int64_t Tmax, int64_t Ttail,
+                                          int32_t prec, int32_t* error_word, void* stream) {
+  const char* fn = "kx_attention_decode_prefix";
+  KX_REQUIRE(qkv && kprefix && vprefix && ktail && vtail && out, "%s: null pointer", fn);
+  KX_REQUIRE(positions && prefix_seq && prefix_len && error_word, "%s: null positions / prefix_seq / prefix_len / error_word", fn);
+  KX_REQUIRE(M > 0 && H > 0 && M < 65536 && H < 65536, "%s: M=%lld rows of H=%lld heads are empty or exceed the grid limits", fn,
+             (long long)M, (long long)H);
+  KX_REQUIRE(Bp > 0 && Bp <= 0x7fffffffll, "%s: Bp=%lld prefix sequences", fn, (long long)Bp);
+  KX_REQUIRE(Tmax > 0 && Tmax <= 0x7fffffffll && Ttail > 0 && Ttail <= 0x7fffffffll,
+             "%s: Tmax=%lld / Ttail=%lld outside the 32-bit positions", fn, (long long)Tmax, (long long)Ttail);
+  KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "%s: bad precision", fn);
+  KX_REQUIRE((odt == KX_F16C) == (prec == KX_PREC_F16C) || odt == KX_F32,
+             "%s: KX_PREC_F16C (fp32 q / cache, exact softmax) writes KX_F16C rows or fp32", fn);
+  KX_REQUIRE(odt != KX_F16P || (prec == KX_PREC_F32 && ((uintptr_t)out & 15) == 0), "%s: KX_F16P rows come from the fp32 step, 16-byte aligned", fn);
+  const int64_t D = H * 64;
+  const bool head_major = kx_tuning_get(KX_TUNE_CACHE_LAYOUT) != 1;
+  DecodeParams p;
+  p.qkv = (const char*)qkv; p.qkv_row = 3 * D;
+  p.kcache = (char*)ktail; p.vcache = (char*)vtail; p.cache_batch = Ttail * D;
+  p.cache_head = head_major ? Ttail * 64 : 64; p.cache_row = head_major ? 64 : D;
+  p.out = out; p.out_row = odt == KX_F16C ? 2 * D : D; p.o_bf16 = odt == KX_BF16; p.o_f16c = odt == KX_F16C; p.stats_out = stats_out;
+  p.o_pieces = odt == KX_F16P;
+  p.H = (int)H; p.D = (int)D; p.t = 0;
+  const RaggedParams r{positions, error_word, (int)Tmax};
+  const PrefixParams pp{prefix_seq, prefix_len, (const char*)kprefix, (const char*)vprefix, Tmax * D, head_major ? Tmax * 64 : 64,
+                        (int)Bp, (int)Tmax, (int)Ttail};
+  hipStream_t s = (hipStream_t)stream;
+  KxProfScope prof(prec == KX_PREC_BF16 ? KX_K_ATTN_BF16 : KX_K_ATTN_F32, M * H, 1, Tmax, s);
+  const dim3 grid((unsigned)H, (unsigned)M);
+  if (prec == KX_PREC_BF16) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, RaggedParams, PrefixParams>), grid, dim3(256), 0, s, p, r, pp);
+  else hipLaunchKernelGGL((attn_decode_kernel<float, RaggedParams, PrefixParams>), grid, dim3(256), 0, s, p, r, pp);
+  KX_CHECK_LAUNCH(fn);
+  return KX_OK;
 }

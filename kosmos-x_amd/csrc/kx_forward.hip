@@ -736,13 +736,22 @@ extern "C" int kx_decoder_extend_ragged(const kx_decoder_weights* w, const int64
 // hold B / K sequences.  Everything but the attention is row-wise and does not know.
 // cache_seq != nullptr (the score step): the B / K groups of K rows are candidates, group c reads cache sequence cache_seq[c] of the
 // Bc the caches hold and nothing is appended (kx_attention_decode_shared).
+// prefix_seq != nullptr (the prefix step): the ragged step's B rows, row r reading prefix_len[r] rows of sequence prefix_seq[r] of the
+// Bc sequences the (const) caches hold and appending to sequence r of the tail caches [L, B, heads, Ttail, 64] (kx_attention_decode_prefix).
 struct StepRows {
   int64_t t; const int32_t* positions; int32_t* error_word; int64_t K; const int32_t* cache_seq; int64_t Bc;
+  const int32_t* prefix_seq; const int32_t* prefix_len; void* ktail; void* vtail; int64_t Ttail;
 };
 
 // the step's attention over one layer's caches: the public entry point of the form `r` describes (B rows)
+// (`layer`: the prefix step's tail caches are addressed here, B sequences of Ttail rows per layer)
 static int step_attention(const StepRows& r, const void* qkv, void* kc, void* vc, void* out, int32_t odt, float* stats_out, int64_t B,
-                          int64_t H, int64_t Tmax, int32_t prec, void* stream) {
+                          int64_t H, int64_t Tmax, int32_t prec, void* stream, int64_t layer) {
+  if (r.prefix_seq) {
+    const size_t tail_bytes = (size_t)layer * B * r.Ttail * H * 64 * qes(prec);
+    return kx_attention_decode_prefix(qkv, kc, vc, (char*)r.ktail + tail_bytes, (char*)r.vtail + tail_bytes, out, odt, stats_out, B, H,
+                                      r.positions, r.prefix_seq, r.prefix_len, r.Bc, Tmax, r.Ttail, prec, r.error_word, stream);
+  }
   if (r.cache_seq)
     return kx_attention_decode_shared(qkv, kc, vc, out, odt, stats_out, B / r.K, r.K, H, r.positions, r.cache_seq, r.Bc, Tmax, prec,
                                       r.error_word, stream);
@@ -779,7 +788,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
   KX_TRY(st.clear_words());
   const int ct = cdt(prec);
   const size_t es = esz(prec);
-  const size_t layer_bytes = (size_t)(r.cache_seq ? r.Bc : r.K > 0 ? B / r.K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
+  const size_t layer_bytes = (size_t)(r.cache_seq || r.prefix_seq ? r.Bc : r.K > 0 ? B / r.K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
   // One token per sequence, up to 16 sequences: the step is 120 dependent launches of weight-streaming work, and launches
   // are what it costs (~6 us each) — tile 16 does each GEMM in one launch and takes the LayerNorm and
   // statistics-finalize kernels in as prologues: 5 launches per layer instead of 13.  bf16 operands, or fp32 operands on the
@@ -817,7 +826,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
       q.W_tiled = L.wqkv_t; q.tiled_fmt = tfmt; q.prec = prec;
       KX_TRY(gemv16(q, s));
       KX_TRY(step_attention(r, d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, pieces ? KX_F16P : ct,
-                            w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream));
+                            w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream, i));
       float *qa = pair ? d.ya : pa, *qb = pair ? d.yb : nullptr;   // what out_proj writes
       Gemv16 o{d.att, D, L.wo, D, qa, D, KX_F32, M, D};
       o.bias = L.bo; o.residual = pa; o.residual2 = pb; o.eps = w->eps;
@@ -853,7 +862,7 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
     if (w->xpos) { q.xT = xT; q.xdim = D; }
     KX_TRY(st.gemm(q));
     KX_TRY(step_attention(r, d.qkv, (char*)kcache + i * layer_bytes, (char*)vcache + i * layer_bytes, d.att, ct,
-                          w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream));
+                          w->subln ? d.partials : nullptr, B, w->heads, Tmax, prec, stream, i));
     // sub-LN: the folded inner_attn_ln / ffn_layernorm statistics are finalised by a launch of their own here
     Gemm o{d.att, D, L.wo, D, x, D, KX_F32, M, D};
     o.bias = L.bo; o.residual = x; o.family = FAM_OUT_PROJ;
@@ -959,4 +968,25 @@ extern "C" int kx_decoder_score_step(const kx_decoder_weights* w, const int64_t*
   return device_step("kx_decoder_score_step", cache_seq != nullptr, range, w, tokens, embed, pos, vocab, max_pos, pos_shift, x, C,
                      StepRows{0, positions, error_word, K, cache_seq, Bc}, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows,
                      const_cast<void*>(kcache), const_cast<void*>(vcache), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
+}
+
+extern "C" int kx_decoder_decode_step_prefix(const kx_decoder_weights* w, const int64_t* tokens, const float* embed, const float* pos,
+                                             int64_t vocab, int64_t max_pos, int64_t pos_shift, float* x, int64_t M,
+                                             const int32_t* positions, const int32_t* prefix_seq, const int32_t* prefix_len, int64_t Bp,
+                                             const float* xq_cs, const float* xq_ss, const float* xk_cs, const float* xk_ss,
+                                             float* xpos_rows, const void* kprefix, const void* vprefix, int64_t Tmax, void* ktail,
+                                             void* vtail, int64_t Ttail, void* logits, int32_t ldt, void* workspace,
+                                             size_t workspace_bytes, int32_t prec, int32_t* error_word, void* stream) {
+  auto range = [&] {
+    KX_REQUIRE(M > 0 && M < 65536, "kx_decoder_decode_step_prefix: M=%lld rows are empty or exceed the grid limits", (long long)M);
+    KX_REQUIRE(Bp > 0 && Bp <= 0x7fffffffll && Tmax > 0 && Tmax <= 0x7fffffffll && Ttail > 0 && Ttail <= 0x7fffffffll,
+               "kx_decoder_decode_step_prefix: Bp=%lld / Tmax=%lld / Ttail=%lld outside the 32-bit range", (long long)Bp, (long long)Tmax,
+               (long long)Ttail);
+    return KX_OK;
+  };
+  // (the prefix attention has no store to the prefix caches)
+  StepRows r{0, positions, error_word, 0, nullptr, Bp, prefix_seq, prefix_len, ktail, vtail, Ttail};
+  return device_step("kx_decoder_decode_step_prefix", prefix_seq && prefix_len && kprefix && vprefix && ktail && vtail, range, w, tokens, embed, pos, vocab,
+                     max_pos, pos_shift, x, M, r, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows, const_cast<void*>(kprefix),
+                     const_cast<void*>(vprefix), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
 }

@@ -33,7 +33,13 @@ token, the last one sampled and never fed — are appended at every row's own de
 (kx_decoder_extend_ragged via Decoder._extend_ragged), then the same loop runs on; the host reads the error word and the rows'
 valid token counts once per turn.
 
-Not offered: sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
+Parallel sampling (``num_return_sequences`` = n > 1 with ``do_sample`` and no beams, parallel_loop): the prefill runs once at B rows;
+the B * n samples then run the ragged loop, every row reading its prompt's cache rows — shared and read only — and appending its own
+tokens' keys to a private tail cache of ``max_new_tokens`` rows (kx_decoder_decode_step_prefix).  Row b * n + i is sample i of prompt b,
+drawn from the Philox stream ``sequence_ids[b * n + i]``: the tokens of the same call on the prompt repeated n times.
+
+Not offered: beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
+sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
 """
@@ -96,7 +102,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         row = logits[:, 0] if gathered else logits[torch.arange(B, device=dev), last]   # [B, V]
         positions = torch.tensor(lengths, dtype=torch.int32, device=dev)
         state.update(positions=positions, pos_max=max(lengths))
-        decoder._ragged_scratch(state, dev)                               # (before the first sampler launch: no fill between steps)
+        decoder._ragged_scratch(state, dev, rows=B)                       # (before the first sampler launch: no fill between steps)
         err = state["error"]                                              # the step kernels' sticky error word
     else:
         row = logits[:, -1]                                               # [B, V] view, row stride T * V
@@ -219,9 +225,12 @@ def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_seq
         raise ValueError(f"num_beams must be a positive integer, got {num_beams!r}")
     if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or num_return_sequences < 1:
         raise ValueError(f"num_return_sequences must be a positive integer, got {num_return_sequences!r}")
-    if num_return_sequences > num_beams:
+    if num_return_sequences > num_beams and (num_beams > 1 or beam_path):
         raise ValueError(f"num_return_sequences = {num_return_sequences} exceeds num_beams = {num_beams}")
     if not (num_beams > 1 or beam_path):
+        if num_return_sequences > 1 and not do_sample:         # (with sampling: parallel_loop, see check_parallel_args)
+            raise ValueError(f"num_return_sequences = {num_return_sequences} without beams draws that many samples per prompt: it needs "
+                             "do_sample=True (greedy copies of one prompt would all be equal)")
         for name, on in (("output_scores", output_scores), ("output_trace", output_trace)):
             if on:
                 raise ValueError(f"{name} is an output of beam search: it needs num_beams > 1")
@@ -314,6 +323,52 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
         res.append(dict(logits=kept[:n], parent=parent[:n], token=token[:n], score=score[:n], pool_score=pool[0], pool_end=pool[1],
                         pool_parent=pool[2], pool_count=pool[3], done=done))
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def check_parallel_args(*, num_return_sequences=1, beams=False, prompt_lookup_num_tokens=0, return_session=False) -> int:
+    """ValueError (naming ``num_return_sequences``) for what generate() refuses of parallel sampling, before the device check and any
+    launch; after check_beam_args, which validated the number and asked for ``do_sample``.  Returns n, the samples per prompt that
+    parallel_loop draws (1: the call runs the loops it always ran)."""
+    n = num_return_sequences
+    if beams or n == 1:
+        return 1
+    for name, on in (("prompt-lookup speculation (prompt_lookup_num_tokens)", prompt_lookup_num_tokens not in (0, None)),
+                     ("sessions (return_session)", bool(return_session))):
+        if on:
+            raise ValueError(f"num_return_sequences = {n} is not offered together with {name}: the samples share their prompt's cache "
+                             "rows, which neither of them reads; see DESIGN.md §8")
+    return n
+
+
+def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
+                  num_return_sequences: int, lengths=None, text_lengths=None, prompt_rows=None, **loop):
+    """n = ``num_return_sequences`` sampled continuations of each of the B prefilled prompts: ``state``, ``logits``, ``prompt_tokens``,
+    ``lengths``, ``text_lengths`` and ``prompt_rows`` as generate_loop takes them after a prefill at B rows, ``loop`` its further
+    keyword arguments.  The state's caches become the read-only prefix caches of B * n rows (state["prefix"]): row b * n + i reads the
+    len_b cache rows of sequence b and appends to its own sequence of the [L, B * n, heads, max_new_tokens, 64] tail caches.  The rows
+    then run generate_loop's ragged branch — the first logits row, the prompt tokens and the lengths repeated n times, the positions
+    on the device — so row b * n + i gets what row b * n + i of generate_loop on the caches repeated per sample gets, bit for bit.
+    Returns what generate_loop returns, at B * n rows."""
+    n, N = int(num_return_sequences), int(max_new_tokens)
+    B, T, V = logits.shape
+    if prompt_rows is not None:
+        T = prompt_rows
+    dev = logits.device
+    plens = [T] * B if lengths is None else list(lengths)
+    tlens = [prompt_tokens.shape[1]] * B if lengths is None else list(plens if text_lengths is None else text_lengths)
+    if prompt_rows is not None:
+        first = logits[:, 0]
+    else:
+        first = logits[torch.arange(B, device=dev), torch.tensor([l - 1 for l in plens], dtype=torch.int64, device=dev)]
+    kc = state["kcache"]
+    L, _, nh, _, hd = kc.shape
+    seq = [b for b in range(B) for _ in range(n)]
+    state["prefix"] = dict(ktail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
+                           vtail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
+                           prefix_seq=torch.tensor(seq, dtype=torch.int32, device=dev),
+                           prefix_len=torch.tensor([plens[b] for b in seq], dtype=torch.int32, device=dev))
+    return generate_loop(decoder, prec, state, first.repeat_interleave(n, dim=0).unsqueeze(1), prompt_tokens.repeat_interleave(n, dim=0),
+                         N, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T, **loop)
 
 
 MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
@@ -630,6 +685,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
         "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
         "output_scores", "output_trace"))
+    samples = check_parallel_args(beams=beams, **pick("num_return_sequences", "prompt_lookup_num_tokens", "return_session"))
     check_constraint_args(vocab, num_beams=kw["num_beams"] if beams else None, **pick(*constraints, "eos_token_id"))
     drafts = check_lookup_args(tokens.shape[0] if tokens.dim() else 0, draft_from=kw["_draft_from"], **pick(
         "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
@@ -653,6 +709,10 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
             return beam_loop(decoder, prec, state, logits, max_new_tokens, **common, **pick(
                 "num_beams", "length_penalty", "early_stopping", "num_return_sequences", "output_scores", "output_trace",
                 "bad_words_ids", "min_new_tokens"))
+        if samples > 1:
+            return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
+                                 lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
+                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", *constraints))
         return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
                              lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
                              **pick(*sampling, "seed", "sequence_ids", "output_logits", *constraints))

@@ -928,6 +928,11 @@ class Decoder(_PackedMixin, nn.Module):
         Score steps (score()): ``state["score"]`` = (K, cache_seq) with ``cache_seq`` an int32 [C] device tensor makes the step C
         candidates of K rows over the B cache sequences, candidate c reading sequence cache_seq[c] and nobody appending
         (kx_decoder_score_step); ``next_token`` and ``state["positions"]`` are [C * K].  Returns [C * K, 1, V].
+        Prefix steps (generate(num_return_sequences=n) with sampling): ``state["prefix"]`` = dict(ktail, vtail, prefix_seq, prefix_len)
+        makes the ragged state step M = len(prefix_seq) rows over the B-sequence caches, which are then read only: row r reads its
+        first prefix_len[r] keys from cache sequence prefix_seq[r] and the rest from sequence r of the tail caches
+        [L, M, heads, Ttail, 64], to which it appends (kx_decoder_decode_step_prefix); ``next_token``, ``state["positions"]``,
+        ``prefix_seq`` and ``prefix_len`` are [M] (the last two int32 device tensors).  Returns [M, 1, V].
         ``state["xpos_centre"]`` (first call only; chunked prefill): the sequence length the XPos tables are centred on when the
         first call holds only the prompt's first rows; default: the first call's own length."""
         prec = self._incremental_precision(prec)
@@ -976,6 +981,11 @@ class Decoder(_PackedMixin, nn.Module):
         rows = B * block if block else B                   # the rows of the step's GEMMs
         if score is not None:
             rows = score[1].shape[0] * score[0]
+        prefix = state.get("prefix") if positions is not None else None
+        if prefix is not None:
+            if block or score is not None:
+                raise ValueError("a prefix state (state['prefix']) steps one row per sample: no block or score step")
+            rows = prefix["prefix_seq"].shape[0]
         if state["prec"] != prec:
             raise RuntimeError("precision changed between incremental steps")
         if t >= Tmax or t + 2 >= pos.shape[0]:
@@ -1001,7 +1011,7 @@ class Decoder(_PackedMixin, nn.Module):
             self._pack_decode_tiles(sprec)                 # first decode step: the streaming copy of the weights
         if positions is not None:
             return self._device_step(state, w, sprec, emb, pos, next_token, positions, pos_shift, block if score is None else score[0],
-                                     None if score is None else score[1], logits_out)
+                                     None if score is None else score[1], logits_out, prefix)
         if passed_x is not None:
             _require_cuda(passed_x, "passed_x")
             x = passed_x[:, -1:].to(torch.float32).clone(memory_format=torch.contiguous_format)
@@ -1043,14 +1053,27 @@ class Decoder(_PackedMixin, nn.Module):
             state["x_step"] = torch.zeros((B, 1, D), dtype=torch.float32, device=dev)
             state["xpos_rows"] = None if state["xpos"][0] is None else torch.zeros((4, B, 32), dtype=torch.float32, device=dev)
 
-    def _device_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K=0, cache_seq=None, logits_out=None) -> torch.Tensor:
+    def _device_step(self, state, w, sprec, emb, pos, next_token, positions, pos_shift, K=0, cache_seq=None, logits_out=None,
+                     prefix=None) -> torch.Tensor:
         """One decode step with every row at its own device-resident position (see _forward_incremental).  K = 0: the ragged step,
         one row per sequence.  K > 0: the block step, K rows per sequence at consecutive positions.  ``cache_seq`` [C]: the score
-        step, C candidates of K rows, candidate c on top of cache sequence cache_seq[c]; the caches are read only."""
+        step, C candidates of K rows, candidate c on top of cache sequence cache_seq[c]; the caches are read only.  ``prefix`` (K = 0): the prefix step,
+        M = len(prefix["prefix_seq"]) rows over the read-only caches and the tail caches prefix["ktail"] / prefix["vtail"]."""
         lib = H.load()
         _require_cuda(next_token, "next_token")
         B, Tmax = state["batch"], state["max_len"]
         M = (B if cache_seq is None else cache_seq.shape[0]) * max(K, 1)
+        if prefix is not None:
+            M = prefix["prefix_seq"].shape[0]
+            kt, vt = prefix["ktail"], prefix["vtail"]
+            want = (self.num_layers, M, state["kcache"].shape[2])
+            if (kt.shape != vt.shape or kt.dim() != 5 or tuple(kt.shape[:3]) != want or kt.shape[4] != 64 or kt.dtype != state["kcache"].dtype
+                    or vt.dtype != kt.dtype or not (kt.is_contiguous() and vt.is_contiguous()) or kt.device != state["kcache"].device):
+                raise ValueError("state['prefix']: ktail / vtail are contiguous [layers, M, heads, Ttail, 64] tensors of the caches' dtype")
+            for name in ("prefix_seq", "prefix_len"):
+                tw = prefix[name]
+                if tw.dtype != torch.int32 or tuple(tw.shape) != (M,) or not tw.is_contiguous() or tw.device != kt.device:
+                    raise ValueError(f"state['prefix']: {name} is a contiguous int32 [{M}] device tensor")
         if next_token.shape[0] != M or positions.shape[0] != M:
             raise ValueError("batch size changed between incremental steps" if cache_seq is None else
                              "the score step's tokens and positions are [candidates * rows per candidate]")
@@ -1064,7 +1087,12 @@ class Decoder(_PackedMixin, nn.Module):
         pid = _step_prec_id(w, sprec)
         need = lib.kx_decoder_workspace_bytes(C.byref(w), M, 1, pid)
         buf = self._ws.get(need, dev)
-        if cache_seq is not None:
+        caches = (state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax)
+        if prefix is not None:
+            fn, rows = "kx_decoder_decode_step_prefix", (M, positions.data_ptr(), prefix["prefix_seq"].data_ptr(),
+                                                         prefix["prefix_len"].data_ptr(), B)
+            caches += (kt.data_ptr(), vt.data_ptr(), kt.shape[3])
+        elif cache_seq is not None:
             fn, rows = "kx_decoder_score_step", (M // K, K, positions.data_ptr(), cache_seq.data_ptr(), B)
         elif K:
             fn, rows = "kx_decoder_decode_step_block", (B, K, positions.data_ptr())
@@ -1073,8 +1101,7 @@ class Decoder(_PackedMixin, nn.Module):
         H.check(getattr(lib, fn)(
             C.byref(w), next_token.data_ptr(), emb.data_ptr(), pos.data_ptr(), emb.shape[0], pos.shape[0], int(pos_shift),
             state["x_step"].data_ptr(), *rows, *(H.ptr(tb) for tb in state["xpos"]), H.ptr(state["xpos_rows"]),
-            state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(),
-            buf.numel(), pid, state["error"].data_ptr(), _stream()), fn)
+            *caches, logits_out.data_ptr(), H.KX_F32, buf.data_ptr(), buf.numel(), pid, state["error"].data_ptr(), _stream()), fn)
         if not K:
             state["pos_max"] += 1
         return logits_out.view(M, 1, w.vocab)
@@ -1317,6 +1344,13 @@ class Kosmos(nn.Module):
         ``prompt_lengths`` (B ints or an integer tensor): a ragged batch — row b's prompt is ``text_tokens[b, :prompt_lengths[b]]``
         (at least 2 tokens: the image is spliced after two), the columns after it are right padding and are ignored whatever
         they hold.  Each row generates what it would generate alone, with the same seed and ``sequence_ids[b]``.
+        ``num_return_sequences`` = n > 1 with ``do_sample`` and no beams: n sampled continuations of every prompt, int64 [B * n, G]
+        with row b * n + i sample i of prompt b (``output_logits``: [B * n, G, V]).  The prompt — tower and resampler included — is
+        prefilled once at B rows; the samples read its KV-cache rows, shared and read only, and append to private tail caches of
+        ``max_new_tokens`` rows (kosmosx.generation.parallel_loop).  Sample (b, i) is drawn from the Philox stream
+        ``sequence_ids[b * n + i]`` (default b * n + i; a given ``sequence_ids`` is [B * n]): what the same call on the prompt
+        repeated n times draws.  It composes with ``prompt_lengths``, the filters, the penalty, the constraints and
+        ``prefill_chunk``; without ``do_sample``, or with ``prompt_lookup_num_tokens`` or ``return_session``, ValueError.
         ``num_beams`` W in 2..16: beam search with W live beams per batch row (kosmosx.generation.beam_loop) -> the best
         hypothesis of every row, int64 [B, n], or the ``num_return_sequences`` = R <= W best, [B, R, n], best first, each
         padded with ``pad_token_id`` after its EOS.  A hypothesis of n generated tokens (its EOS included) scores
@@ -1527,7 +1561,8 @@ class KosmosLanguage(nn.Module):
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
                  session_capacity=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
-        (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_beams`` and the
+        (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
+        with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
         arguments that go with it: beam search, as there; ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_new_tokens`` and
         ``stop_sequences``: the constraints, as there; ``prompt_lookup_num_tokens``, ``max_matching_ngram_size`` and
         ``output_acceptance``: speculative decoding by prompt lookup, as there; ``prefill_chunk``: the prompt prefilled that many

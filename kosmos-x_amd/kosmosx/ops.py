@@ -682,6 +682,35 @@ def attention_decode_shared(qkv, kcache, vcache, positions, cache_seq, error_wor
     return out
 
 
+def attention_decode_prefix(qkv, kprefix, vprefix, ktail, vtail, positions, prefix_seq, prefix_len, error_word, *, out_dtype="f32",
+                            stats_out=None, layout="head_major"):
+    """Kernel-level wrapper of kx_attention_decode_prefix (include/kosmosx_hip.h, "Decoding rows over a shared, read-only prefix
+    cache"): ops.attention_decode's ragged rows, row r reading keys 0 .. prefix_len[r] - 1 from sequence prefix_seq[r] of the prefix
+    caches and the keys after them from sequence r of the tail caches, to which the new k / v are appended at row
+    positions[r] - prefix_len[r].  qkv [M, 3 * H * 64] fp32 or bf16; kprefix / vprefix [Bp, H, Tmax, 64] (left untouched) and ktail /
+    vtail [M, H, Ttail, 64] of the same dtype ([.., T, H, 64] with ``layout`` "row_major", as ops.attention_decode); positions,
+    prefix_seq and prefix_len [M] int32 on the device; error_word int32 [1] (sticky: KX_RAGGED_ERR_CACHE for a row whose prefix
+    sequence, prefix length or tail row is outside its cache — that row writes nothing).  The bits of the ragged launch on a private
+    cache assembled from the prefix and tail rows.  Returns the output rows [M, ...]."""
+    _need_cuda(qkv, kprefix, vprefix, ktail, vtail, positions, prefix_seq, prefix_len, error_word, stats_out)
+    fn = "attention_decode_prefix"
+    M, Hh, Ttail, _, odt, out, prec = _decode_attention_args(fn, qkv, ktail, vtail, layout, out_dtype, positions, error_word)
+    Bp, a, b, hd = kprefix.shape
+    Tmax, Hp = (a, b) if layout == "row_major" else (b, a)
+    if hd != 64 or Hp != Hh or vprefix.shape != kprefix.shape or not (kprefix.is_contiguous() and vprefix.is_contiguous()):
+        raise ValueError(f"{fn}: prefix caches [Bp, H, Tmax, 64] ([Bp, Tmax, H, 64] row-major) with the tails' H, contiguous")
+    if kprefix.dtype != qkv.dtype or vprefix.dtype != qkv.dtype:
+        raise TypeError(f"{fn}: qkv and the caches share one dtype, fp32 or bf16")
+    for name, w in (("prefix_seq", prefix_seq), ("prefix_len", prefix_len)):
+        if w.dtype != torch.int32 or tuple(w.shape) != (M,) or not w.is_contiguous():
+            raise TypeError(f"{fn}: {name} must be a contiguous int32 [{M}] tensor")
+    H.check(H.load().kx_attention_decode_prefix(qkv.data_ptr(), kprefix.data_ptr(), vprefix.data_ptr(), ktail.data_ptr(),
+                                                vtail.data_ptr(), out.data_ptr(), odt, H.ptr(stats_out), M, Hh, positions.data_ptr(),
+                                                prefix_seq.data_ptr(), prefix_len.data_ptr(), Bp, Tmax, Ttail, prec,
+                                                error_word.data_ptr(), _stream()), "kx_attention_decode_prefix")
+    return out
+
+
 def attention_extend(qkv, kcache, vcache, P, *, out_dtype="f32", stats_out=None, layout="head_major", f16c=False):
     """Kernel-level wrapper of kx_attention_extend (include/kosmosx_hip.h, "Chunked prefill"): Tn new rows per sequence on top of
     caches that hold ``P`` rows (a host int, the same for every sequence).  qkv [B * Tn, 3 * H * 64] fp32 or bf16, row b * Tn + i the
