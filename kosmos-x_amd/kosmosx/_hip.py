@@ -21,6 +21,7 @@ KX_ACT_NONE, KX_ACT_GELU, KX_ACT_QUICK_GELU = 0, 1, 2
 KX_ATTN_FULL, KX_ATTN_CAUSAL = 0, 1
 KX_RAGGED_ERR_TABLE, KX_RAGGED_ERR_CACHE = 1, 2
 KX_RAGGED_ERR_GATHER = 4
+KX_TUNE_LN_VARIANT = 0   # kx_set_tuning key (csrc/kx_gemm_plan.h): 0 shipped rule, 1 workgroup-per-row kernel, else wave-per-row kernel
 KX_ACT_RELU, KX_ACT_SWISH = 5, 6
 ACTS = {"none": KX_ACT_NONE, "gelu": KX_ACT_GELU, "quick_gelu": KX_ACT_QUICK_GELU, "relu": KX_ACT_RELU, "swish": KX_ACT_SWISH}
 PRECS = {"bf16": KX_PREC_BF16, "fp32": KX_PREC_F32, "bf16x3": KX_PREC_BF16X3, "f16c": KX_PREC_F16C, "f16": KX_PREC_F16}

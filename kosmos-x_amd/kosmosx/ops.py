@@ -425,6 +425,19 @@ def embed_splice(tokens, embed, pos, img=None, u1_alias=True, splice_at=2, pos_o
     return out
 
 
+def token_range(tokens, out=None):
+    """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
+    kx_token_range: (min, max) of the int64 ``tokens`` on the device -> int64 [2] (``out``: a buffer to reuse; the launcher
+    initialises it)."""
+    _need_cuda(tokens, out)
+    if tokens.dtype != torch.int64 or not tokens.is_contiguous():
+        raise TypeError("token_range: tokens must be a contiguous int64 tensor")
+    if out is None:
+        out = torch.empty(2, dtype=torch.int64, device=tokens.device)
+    H.check(H.load().kx_token_range(tokens.data_ptr(), tokens.numel(), out.data_ptr(), _stream()), "kx_token_range")
+    return out
+
+
 def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
                   position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
                   pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0):
