@@ -849,6 +849,31 @@ int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int
                      const int64_t* target, float* out, int64_t rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-token log-probs of a generation step (added within ABI 7: one function is appended; no struct, no existing layout moves and
+ * the kx_struct_id list is unchanged, so kx_version() stays 7).
+ *
+ * kx_step_logprobs: one launch, one 256-thread workgroup per row b = 0 .. B - 1 of the fp32 logits (x = logits[b * ld + 0 .. V),
+ *   any V >= 1, ld >= V, no alignment asked of a row), after the sampler has left the row's token in token[b] (device):
+ *     token_logprob[b, out_col] = (x[t] - max) - log(sum exp(x - max)),  t = token[b]
+ *   kx_token_logprob's device code, so the same bits.  t outside [0, V): 0.0 exactly, nothing read through t.
+ *   With top_n > 0 also the row's top_n entries by value descending, the lowest id first among exactly equal values (-0 == +0):
+ *     top_id[b, out_col, j] = the j-th entry's id,  top_logprob[b, out_col, j] = (x[id] - max) - log(sum)   — the same formula,
+ *   so slot j holds what kx_token_logprob gives for that id.  -inf entries sort last and give -inf; with V < top_n the trailing slots
+ *   hold id -1 and -inf.  A NaN in the row: the log-probs are NaN as in kx_token_logprob, the ids unspecified but in [-1, V).
+ *   token_logprob is [B, out_ld] fp32, top_logprob / top_id are [B, out_ld, top_n] fp32 / int64; the launch writes column out_col
+ *   of them and nothing else.  skip [B] uint8 (device) or NULL: a row with skip[b] != 0 reads nothing of its logits and gets exact
+ *   zeros — token_logprob 0.0, every top_logprob slot 0.0, every top_id slot -1 — what score() leaves at padded slots.
+ *   The ids are selected by integer comparisons on (value, id) alone and the sums run in kx_token_logprob's fixed order: the result
+ *   does not depend on B, on the row's index or on how threads split the row; two calls give identical bits.  top_n == 0 runs
+ *   kx_token_logprob's two passes and no selection.
+ *   Host checks (KX_ERR_INVALID_ARG, nothing launched): null logits / token / token_logprob, B < 1, V < 1, ld < V, out_col outside
+ *   [0, out_ld), top_n outside 0..16, top_n > 0 with a null top_logprob or top_id.  Does not allocate or synchronise.
+ * ------------------------------------------------------------------------------------------ */
+int kx_step_logprobs(const float* logits, int64_t ld, int64_t B, int64_t V, const int64_t* token, const uint8_t* skip,
+                     float* token_logprob, int64_t out_ld, int64_t out_col, int32_t top_n, float* top_logprob, int64_t* top_id,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Decoding rows over a shared, read-only prefix cache plus a private tail cache (added within ABI 7: two functions are appended; no
  * struct, no existing layout moves and the kx_struct_id list is unchanged, so kx_version() stays 7).
  *

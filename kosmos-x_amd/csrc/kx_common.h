@@ -296,20 +296,37 @@ __device__ __forceinline__ float wave_max(float v) {
 // kx_cross_entropy and kx_token_logprob take their log-sum-exp from: log-prob = (x[target] - max) - log(sum), not
 // x[target] - (max + log(sum)), which rounds the sum to an ulp of |max| first.  Ends on a barrier-free read of `red`: a caller
 // that reuses `red` synchronises first.
-__device__ __forceinline__ void block_max_sumexp(const float* __restrict__ lr, int V, float* red, float& mx, float& s) {
-  mx = -INFINITY;
-  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, lr[c]);
+// Its two halves, for a caller that fuses other work into the pass over the row that finds the maximum (kx_step_logprobs): the
+// threads' own maxima -> the row's (exact in any order), and the sum pass given the row's maximum.
+__device__ __forceinline__ float block_max_finish(float mx, float* red) {
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
-  s = 0.f;
-  for (int c = threadIdx.x; c < V; c += 256) s += expf(lr[c] - mx);
+  return mx;
+}
+__device__ __forceinline__ float block_sumexp(const float* __restrict__ lr, int V, float* red, float mx) {
+  float s = 0.f;
+  int c = threadIdx.x;
+  for (; c < V - 7 * 256; c += 8 * 256) {             // eight loads in flight, then the adds in the order of the plain loop:
+    float v[8];                                       // the same sum, bit for bit, without a memory round trip per element
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = lr[c + i * 256];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += expf(v[i] - mx);
+  }
+  for (; c < V; c += 256) s += expf(lr[c] - mx);
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  s = (red[0] + red[1]) + (red[2] + red[3]);
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ void block_max_sumexp(const float* __restrict__ lr, int V, float* red, float& mx, float& s) {
+  mx = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, lr[c]);
+  mx = block_max_finish(mx, red);
+  s = block_sumexp(lr, V, red, mx);
 }
 
 // ---- internal launchers shared between translation units ----

@@ -4,6 +4,7 @@
 // statistics with wave-64 shuffles + one LDS hop.  They are bound by HBM bandwidth, never by VALU.
 #include "kx_common.h"
 #include "kx_gelu_load.h"
+#include "kx_select.h"
 
 namespace {
 
@@ -354,7 +355,134 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restr
   if (threadIdx.x == 0) out[r] = (lr[tg] - mx) - logf(s);
 }
 
+// A generation step's log-probs (kx_step_logprobs): token_logprob_kernel's arithmetic on row b for the token the sampler has just
+// left in token[b], and the row's top_n (value, id) pairs, value descending, the lowest id first among equal values.
+// Pass 1 finds the maximum as block_max_sumexp does and keeps, per thread, the CAP >= top_n best of the ids it strides over: a
+// list sorted best first, held in registers (every index below is a compile-time constant).  A thread meets its ids in ascending
+// order, so an equal key never displaces a held one.  The key is f2key of the value with -0 folded into +0: unsigned order = value
+// order, -inf above the empty slot's 0.  Then top_n rounds of a workgroup arg-max over the lists' heads on (key << 32 | ~id), the
+// sampler's pair; the thread that held the winner pops it.  Integer comparisons only: the ids depend on the row's values alone,
+// not on how the threads split it.  Pass 2 is block_sumexp, so slot j's log-prob is bit for bit what token_logprob_kernel gives
+// for that id.  A skipped row leaves before any barrier (uniform over the workgroup) with exact zeros and ids -1.
+template <int CAP>
+__global__ __launch_bounds__(256) void step_logprobs_kernel(const float* __restrict__ logits, long long ld, int V,
+                                                            const long long* __restrict__ token,
+                                                            const unsigned char* __restrict__ skip,
+                                                            float* __restrict__ token_logprob, long long out_ld, long long out_col,
+                                                            int top_n, float* __restrict__ top_logprob,
+                                                            long long* __restrict__ top_id) {
+  __shared__ float red[4];
+  __shared__ unsigned long long wred[4];
+  __shared__ int win[CAP > 0 ? CAP : 1];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const long long o = b * out_ld + out_col;
+  if (skip && skip[b]) {
+    if (tid == 0) token_logprob[o] = 0.f;
+    if (tid < top_n) { top_logprob[o * top_n + tid] = 0.f; top_id[o * top_n + tid] = -1; }
+    return;
+  }
+  const float* lr = logits + b * ld;
+  unsigned key[CAP > 0 ? CAP : 1];
+  int id[CAP > 0 ? CAP : 1];
+#pragma unroll
+  for (int j = 0; j < CAP; ++j) { key[j] = 0u; id[j] = -1; }
+  float mx = -INFINITY;
+  auto consider = [&](float v, int c) {
+    mx = fmaxf(mx, v);
+    if constexpr (CAP > 0) {
+      const unsigned k = f2key(v + 0.0f);
+      if (k > key[CAP - 1]) {                         // insert in front of the first held key below k, the rest move down one
+        bool gt[CAP];
+#pragma unroll
+        for (int j = 0; j < CAP; ++j) gt[j] = k > key[j];
+#pragma unroll
+        for (int j = CAP - 1; j > 0; --j) {
+          key[j] = gt[j - 1] ? key[j - 1] : (gt[j] ? k : key[j]);
+          id[j] = gt[j - 1] ? id[j - 1] : (gt[j] ? c : id[j]);
+        }
+        key[0] = gt[0] ? k : key[0];
+        id[0] = gt[0] ? c : id[0];
+      }
+    }
+  };
+  int c = tid;
+  for (; c < V - 7 * 256; c += 8 * 256) {             // eight loads in flight; the ids still met in ascending order
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = lr[c + i * 256];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) consider(v[i], c + i * 256);
+  }
+  for (; c < V; c += 256) consider(lr[c], c);
+  mx = block_max_finish(mx, red);
+  if constexpr (CAP > 0) {
+    for (int r = 0; r < top_n; ++r) {                 // (uniform: every thread runs every round's barriers)
+      const unsigned long long pk = ((unsigned long long)key[0] << 32) | (0xffffffffu - (unsigned)id[0]);   // empty head: 0
+      unsigned long long best = pk;
+#pragma unroll
+      for (int x = 32; x > 0; x >>= 1) {
+        const unsigned long long t = __shfl_xor(best, x, 64);
+        best = t > best ? t : best;
+      }
+      if ((tid & 63) == 0) wred[tid >> 6] = best;
+      __syncthreads();
+      best = wred[0];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) best = wred[w] > best ? wred[w] : best;
+      __syncthreads();
+      const bool pop = (pk == best) & (best != 0ull);  // ids are distinct: one thread at the most
+#pragma unroll
+      for (int j = 0; j < CAP - 1; ++j) { key[j] = pop ? key[j + 1] : key[j]; id[j] = pop ? id[j + 1] : id[j]; }
+      key[CAP - 1] = pop ? 0u : key[CAP - 1];
+      id[CAP - 1] = pop ? -1 : id[CAP - 1];
+      if (tid == 0) win[r] = best ? (int)(0xffffffffu - (unsigned)best) : -1;   // nothing left (V < top_n): id -1
+    }
+  }
+  const float s = block_sumexp(lr, V, red, mx);       // (its barriers also publish `win`)
+  if (tid == 0) {
+    const long long tg = token[b];
+    token_logprob[o] = ((tg < 0) | (tg >= V)) ? 0.f : (lr[tg] - mx) - logf(s);
+  }
+  if constexpr (CAP > 0) {
+    if (tid < top_n) {
+      const int w = win[tid];
+      top_id[o * top_n + tid] = w;
+      top_logprob[o * top_n + tid] = w < 0 ? -INFINITY : (lr[w] - mx) - logf(s);
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int kx_step_logprobs(const float* logits, int64_t ld, int64_t B, int64_t V, const int64_t* token, const uint8_t* skip,
+                                float* token_logprob, int64_t out_ld, int64_t out_col, int32_t top_n, float* top_logprob,
+                                int64_t* top_id, void* stream) {
+  KX_REQUIRE(logits, "kx_step_logprobs: logits is null");
+  KX_REQUIRE(token, "kx_step_logprobs: token is null");
+  KX_REQUIRE(token_logprob, "kx_step_logprobs: token_logprob is null");
+  KX_REQUIRE(B >= 1 && B <= 0x7fffffffll, "kx_step_logprobs: B=%lld (B >= 1)", (long long)B);
+  KX_REQUIRE(V >= 1 && V <= 0x7fffffffll, "kx_step_logprobs: V=%lld (V >= 1)", (long long)V);
+  KX_REQUIRE(ld >= V, "kx_step_logprobs: ld=%lld is less than V=%lld", (long long)ld, (long long)V);
+  KX_REQUIRE(out_col >= 0 && out_col < out_ld, "kx_step_logprobs: out_col=%lld outside [0, out_ld=%lld)", (long long)out_col,
+             (long long)out_ld);
+  KX_REQUIRE(top_n >= 0 && top_n <= 16, "kx_step_logprobs: top_n=%d outside 0..16", (int)top_n);
+  KX_REQUIRE(top_n == 0 || top_logprob, "kx_step_logprobs: top_logprob is null with top_n=%d", (int)top_n);
+  KX_REQUIRE(top_n == 0 || top_id, "kx_step_logprobs: top_id is null with top_n=%d", (int)top_n);
+  hipStream_t s = (hipStream_t)stream;
+  KxProfScope prof(KX_K_MISC, B, V, 32, s);
+  const dim3 grid((unsigned)B), block(256);
+#define KX_STEP_LOGPROBS(CAP)                                                                                              \
+  hipLaunchKernelGGL(step_logprobs_kernel<CAP>, grid, block, 0, s, logits, (long long)ld, (int)V, (const long long*)token, skip, \
+                     token_logprob, (long long)out_ld, (long long)out_col, (int)top_n, top_logprob, (long long*)top_id)
+  if (top_n == 0) KX_STEP_LOGPROBS(0);                // no selection: token_logprob_kernel's two passes and nothing else
+  else if (top_n <= 4) KX_STEP_LOGPROBS(4);
+  else if (top_n <= 8) KX_STEP_LOGPROBS(8);
+  else KX_STEP_LOGPROBS(16);
+#undef KX_STEP_LOGPROBS
+  KX_CHECK_LAUNCH("kx_step_logprobs");
+  return KX_OK;
+}
 
 extern "C" int kx_token_logprob(const float* logits, int64_t rows_available, int64_t V, int64_t ld, const int32_t* row_index,
                                 const int64_t* target, float* out, int64_t rows, void* stream) {

@@ -237,6 +237,7 @@ SYMBOLS = {
     "kx_decoder_score_step": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, vp, vp,
                                         vp, vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),
     "kx_token_logprob": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, vp]),
+    "kx_step_logprobs": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, i64, i32, vp, vp, vp]),
     "kx_attention_decode_prefix": (C.c_int, [vp] * 6 + [i32, vp, i64, i64, vp, vp, vp, i64, i64, i64, i32, vp, vp]),
     "kx_decoder_decode_step_prefix": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, i64,
                                                 vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),

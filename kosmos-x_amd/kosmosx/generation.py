@@ -38,7 +38,12 @@ the B * n samples then run the ragged loop, every row reading its prompt's cache
 tokens' keys to a private tail cache of ``max_new_tokens`` rows (kx_decoder_decode_step_prefix).  Row b * n + i is sample i of prompt b,
 drawn from the Philox stream ``sequence_ids[b * n + i]``: the tokens of the same call on the prompt repeated n times.
 
-Not offered: beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
+Log-probs (``output_logprobs``, ``top_logprobs`` = k; generate_loop and everything that runs it): one kx_step_logprobs launch after
+each sampler launch writes the log-prob of the token just drawn under the model's own logits — kx_token_logprob's arithmetic — and
+the row's k most likely (log-prob, id) pairs into column g of buffers allocated before the loop; rows that entered the sampler launch
+finished keep exact zeros.  No logits row is kept and the host reads nothing more.
+
+Not offered: log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
 sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
@@ -57,7 +62,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
-                  prompt_rows=None, pad_launches=None):
+                  prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -74,7 +79,15 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     ``pad_launches`` (sessions; ragged batches only): an int32 [B] device tensor, zero on entry.  Before every sampler launch — after
     the step's constraint launch — the ``finished`` bytes are added to it, so that row b entered n - pad_launches[b] of the n
     sampler launches unfinished: its valid tokens, an EOS or the last token of a stop sequence included.  It is read back once,
-    after the loop, in the same copy as the step kernels' error word, and left in state["turn"] = (n, [pad launches per row])."""
+    after the loop, in the same copy as the step kernels' error word, and left in state["turn"] = (n, [pad launches per row]).
+    ``output_logprobs`` / ``top_logprobs`` = k (check_logprob_args): one kx_step_logprobs launch after each sampler launch writes
+    column g of token_logprobs [B, max_new_tokens] — the log-prob of the token just drawn under the model's own logits, the rows
+    ``output_logits`` returns — and with k > 0 of top_logprobs / top_ids [B, max_new_tokens, k].  On a step with a constraint launch
+    the raw row is a clone taken before it (the one ``output_logits`` keeps, when on).  A row that enters the sampler launch finished
+    emits a pad: the ``finished`` bytes of that moment (what ``pad_launches`` counts) are snapshotted into a uint8 buffer and passed
+    as the launch's ``skip``, its slots stay 0.0 / -1; when nothing can finish a row no snapshot is taken.
+    Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits``; then with ``output_logprobs`` the fp32
+    [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
     B, T, V = logits.shape
     gathered = prompt_rows is not None
     if gathered:
@@ -93,6 +106,15 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     if sequence_ids is not None:
         sequence_ids = sequence_ids.to(device=dev, dtype=torch.int64).contiguous()
     kept = []
+    k = int(top_logprobs)
+    lp = top_lp = top_ids = snap = None
+    if output_logprobs:                                                   # every buffer before the first step
+        lp = torch.zeros((B, max_new_tokens), dtype=torch.float32, device=dev)
+        if k > 0:
+            top_lp = torch.zeros((B, max_new_tokens, k), dtype=torch.float32, device=dev)
+            top_ids = torch.full((B, max_new_tokens, k), -1, dtype=torch.int64, device=dev)
+        if eos_token_id is not None or (cons is not None and cons["stop"]):
+            snap = torch.empty(B, dtype=torch.uint8, device=dev)          # ``finished`` as the sampler launch met it
     positions = None
     if lengths is not None:
         # Row b's first token comes from logits[b, lengths[b] - 1]; from here on its position lives on the device.  The padded
@@ -113,15 +135,22 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
             plens = torch.tensor(lengths if text_lengths is None else text_lengths, dtype=torch.int32, device=dev)
     n = 0
     for g in range(max_new_tokens):
+        constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
+        raw = row
         if output_logits:
             kept.append(row.clone())                                      # the model's own logits: before any ban (the sampler only reads the row)
-        if cons is not None and (cons["every_step"] or g < cons["min_new"]):
+            raw = kept[-1]
+        elif output_logprobs and constrained:
+            raw = row.clone()                                             # (the constraint launch edits the row in place)
+        if constrained:
             ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
                                  no_repeat_ngram_size=cons["ngram"], bad_words=bad, stop_sequences=stop,
                                  min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
         if pad_launches is not None:
             pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
+        if snap is not None:
+            snap.copy_(finished)
         if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
@@ -132,6 +161,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                               do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
                               hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                               out=nxt, out_tokens=out, out_col=g)
+        if output_logprobs:
+            ops.step_logprobs(raw, nxt, out=lp, col=g, skip=snap, top_n=k, top_out=top_lp, top_ids=top_ids)
         n = g + 1
         if n == max_new_tokens:
             break
@@ -156,10 +187,14 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         state["turn"] = (n, pads)
     elif positions is not None:
         _raise_position_error(int(err.item()), state)                     # device positions are validated by the kernels, not here
-    out = out[:, :n]
+    res = [out[:, :n]]
     if output_logits:
-        return out, torch.stack(kept, dim=1)
-    return out
+        res.append(torch.stack(kept, dim=1))
+    if output_logprobs:
+        res.append(lp[:, :n])
+        if k > 0:
+            res += [top_lp[:, :n], top_ids[:, :n]]
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 MAX_BEAMS = 16
@@ -214,6 +249,28 @@ def check_constraint_args(vocab: int, *, no_repeat_ngram_size=0, bad_words_ids=N
     reads = bool(no_repeat_ngram_size or stop or any(len(s) > 1 for s in bad))
     return dict(ngram=no_repeat_ngram_size, bad=bad, stop=stop, min_new=min_new_tokens, reads_history=reads,
                 every_step=bool(no_repeat_ngram_size or bad or stop))
+
+
+MAX_TOP_LOGPROBS = 16                   # kx_step_logprobs' top_n limit
+
+
+def check_logprob_args(vocab: int, *, output_logprobs=False, top_logprobs=0, beams=False, drafts=0) -> int:
+    """ValueError (naming the argument) for what generate() refuses of the log-prob arguments, before the device check and any
+    launch.  ``beams``: the call runs beam search; ``drafts``: its prompt-lookup drafts per step.  Returns ``top_logprobs``."""
+    k = top_logprobs
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}, got {k!r}")
+    if k > vocab:
+        raise ValueError(f"top_logprobs = {k} exceeds the vocabulary of {vocab}")
+    if k > 0 and not output_logprobs:
+        raise ValueError(f"top_logprobs = {k} lists the alternatives next to each token's log-prob: it needs output_logprobs=True")
+    if output_logprobs and beams:
+        raise ValueError("output_logprobs is not offered together with beam search (num_beams > 1): beams report output_scores; "
+                         "see DESIGN.md §8")
+    if output_logprobs and drafts:
+        raise ValueError(f"output_logprobs is not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = {drafts}): "
+                         "a verify step emits a varying number of tokens per row; see DESIGN.md §8")
+    return k
 
 
 def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
@@ -690,6 +747,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     drafts = check_lookup_args(tokens.shape[0] if tokens.dim() else 0, draft_from=kw["_draft_from"], **pick(
         "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
         "sequence_ids", *constraints, "eos_poll"))
+    check_logprob_args(vocab, beams=beams, drafts=drafts, **pick("output_logprobs", "top_logprobs"))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
                                                                               "prompt_lookup_num_tokens"))
@@ -699,7 +757,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
             return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
-                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", *constraints)))
+                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints)))
         common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
@@ -712,10 +770,10 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         if samples > 1:
             return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
                                  lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", *constraints))
+                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints))
         return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
                              lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                             **pick(*sampling, "seed", "sequence_ids", "output_logits", *constraints))
+                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints))
 
 
 def run_score(model, prompt: dict, continuations, kw: dict):
@@ -944,7 +1002,7 @@ class Session:
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, prompt_lengths=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
-                 prefill_chunk=None):
+                 prefill_chunk=None, output_logprobs=False, top_logprobs=0):
         """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
         at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
         session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
@@ -956,6 +1014,7 @@ class Session:
         vocab = self._model.embed.weight.shape[0]
         check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                               min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
+        check_logprob_args(vocab, output_logprobs=output_logprobs, top_logprobs=top_logprobs)
         chunk = check_prefill_chunk(prefill_chunk)
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
@@ -973,7 +1032,8 @@ class Session:
                     do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                     seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
                     output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                    min_new_tokens=min_new_tokens, stop_sequences=stop_sequences))
+                    min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, output_logprobs=output_logprobs,
+                    top_logprobs=top_logprobs))
             finally:
                 self._state["pos_max"] = max(self._cached)
             out = res[0] if isinstance(res, tuple) else res

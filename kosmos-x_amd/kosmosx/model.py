@@ -1333,7 +1333,7 @@ class Kosmos(nn.Module):
                  early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
-                 prefill_chunk=None, return_session=False, session_capacity=None):
+                 prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1383,7 +1383,19 @@ class Kosmos(nn.Module):
         ``session_capacity`` rows per sequence (default: the position table's rows) — whose ``generate(x, max_new_tokens, ...)`` and
         ``append(x)`` take further, text-only turns: only the new ids are run, appended at every row's own position in one ragged
         pass (kx_decoder_extend_ragged).  Row b then behaves like a fresh ragged generate() over its whole logical sequence.  Not
-        offered together with ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0 (ValueError)."""
+        offered together with ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0 (ValueError).
+        ``output_logprobs``: also ``token_logprobs`` fp32 [B, n_new], the log-probability of every generated token under the model's
+        own distribution — log softmax of the logits ``output_logits`` returns, before bans, the repetition penalty, the temperature
+        and the filters: what ``score()`` gives for the same tokens — taken on the device by one launch per step
+        (kx_step_logprobs), no logits row kept.  ``top_logprobs`` = k in 1..16 (needs ``output_logprobs``): also the k most likely
+        ids of every step, ``top_logprobs`` fp32 [B, n_new, k] and ``top_ids`` int64 [B, n_new, k], most likely first, the lowest id
+        first among equal logits; a banned id can appear among them.  A row's EOS, or the last token of its stop sequence, is a
+        token and has its log-prob; the slots after a row's end hold exactly 0.0 (ids -1), as ``score()`` leaves padded slots.
+        Return order: tokens, the logits (``output_logits``), token_logprobs, top_logprobs and top_ids (k > 0), the session
+        (``return_session``).  It composes with sampling, ``prompt_lengths``, ``num_return_sequences`` (rows b * n + i), the
+        constraints, ``prefill_chunk`` and sessions; with ``num_beams`` > 1 (beams have ``output_scores``) or
+        ``prompt_lookup_num_tokens`` > 0, with ``top_logprobs`` outside 0..16 or above the vocabulary, or ``top_logprobs`` > 0
+        without ``output_logprobs``: ValueError."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1395,7 +1407,8 @@ class Kosmos(nn.Module):
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity))
+            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
+            output_logprobs=output_logprobs, top_logprobs=top_logprobs))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1559,7 +1572,7 @@ class KosmosLanguage(nn.Module):
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
-                 session_capacity=None):
+                 session_capacity=None, output_logprobs=False, top_logprobs=0):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1567,7 +1580,8 @@ class KosmosLanguage(nn.Module):
         ``stop_sequences``: the constraints, as there; ``prompt_lookup_num_tokens``, ``max_matching_ngram_size`` and
         ``output_acceptance``: speculative decoding by prompt lookup, as there; ``prefill_chunk``: the prompt prefilled that many
         rows at a time, as there; ``return_session`` and ``session_capacity``: the call also returns a Session that takes
-        further turns on the kept KV cache, as there)."""
+        further turns on the kept KV cache, as there; ``output_logprobs`` and ``top_logprobs``: every generated token's log-prob
+        and the most likely alternatives, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1579,7 +1593,8 @@ class KosmosLanguage(nn.Module):
             output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity))
+            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
+            output_logprobs=output_logprobs, top_logprobs=top_logprobs))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):

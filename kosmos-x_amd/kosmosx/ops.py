@@ -799,6 +799,40 @@ def token_logprob(logits, target, *, row_index=None, vocab=None, out=None):
     return out
 
 
+def step_logprobs(logits, token, *, out, col, skip=None, top_n=0, top_out=None, top_ids=None):
+    """Kernel-level wrapper of kx_step_logprobs (include/kosmosx_hip.h, "Per-token log-probs of a generation step"): one launch
+    writes out[b, col] = log softmax(logits[b])[token[b]] and, with ``top_n`` > 0, the row's top_n (log-prob, id) pairs — value
+    descending, the lowest id first among equal values — into top_out[b, col] / top_ids[b, col].  logits fp32 [B, V] with unit
+    column stride (any row pitch >= V); token int64 [B]; ``out`` fp32 [B, N] contiguous, ``col`` in [0, N); ``skip`` uint8 [B] or
+    None: rows that get exact zeros (ids -1) and read no logits; ``top_out`` fp32 / ``top_ids`` int64 [B, N, top_n] contiguous.
+    A token outside [0, V) gives exactly 0.0.  Nothing but column ``col`` is written.  Returns ``out``."""
+    _need_cuda(logits, token, out, skip, top_out, top_ids)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise TypeError("step_logprobs: logits is a non-empty fp32 [B, V] tensor with unit column stride")
+    B, V = logits.shape
+    if B > 1 and logits.stride(0) < V:
+        raise TypeError(f"step_logprobs: logits rows overlap (row stride {logits.stride(0)} < V = {V})")
+    if token.dtype != torch.int64 or tuple(token.shape) != (B,) or not token.is_contiguous():
+        raise TypeError(f"step_logprobs: token is a contiguous int64 [{B}] tensor")
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or not out.is_contiguous():
+        raise TypeError(f"step_logprobs: out is a contiguous fp32 [{B}, N] tensor")
+    N = out.shape[1]
+    if isinstance(col, bool) or not isinstance(col, int) or not 0 <= col < N:
+        raise ValueError(f"step_logprobs: col = {col!r} is outside the {N} columns of out")
+    if skip is not None and (skip.dtype != torch.uint8 or tuple(skip.shape) != (B,) or not skip.is_contiguous()):
+        raise TypeError(f"step_logprobs: skip is a contiguous uint8 [{B}] tensor")
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= 16:
+        raise ValueError(f"step_logprobs: top_n = {top_n!r} is outside 0..16")
+    if top_n > 0:
+        for name, t, dt in (("top_out", top_out, torch.float32), ("top_ids", top_ids, torch.int64)):
+            if t is None or t.dtype != dt or tuple(t.shape) != (B, N, top_n) or not t.is_contiguous():
+                raise TypeError(f"step_logprobs: {name} is a contiguous {dt} [{B}, {N}, {top_n}] tensor")
+    H.check(H.load().kx_step_logprobs(logits.data_ptr(), logits.stride(0) if B > 1 else max(logits.stride(0), V), B, V,
+                                      token.data_ptr(), H.ptr(skip), out.data_ptr(), N, col, top_n,
+                                      H.ptr(top_out) if top_n else 0, H.ptr(top_ids) if top_n else 0, _stream()), "kx_step_logprobs")
+    return out
+
+
 def spec_accept(picked, *, fed=None, rows_per_sequence, positions, prefill_len=0, history, hist_len, out_tokens, n_out, finished,
                 next_tokens, max_new_tokens, step, ngram_max=2, eos_token_id=None, pad_token_id=1, out_src=None, emitted=None,
                 draft_from=None):
