@@ -294,13 +294,20 @@ __global__ __launch_bounds__(256) void ln_bwd_row_kernel(const float* __restrict
   for (int c = lane; c < cols; c += 64) { const float d = xr[c] - mean; q += d * d; }
   const float rstd = rsqrtf(wave_sum(q) / (float)cols + eps);
   float a = 0.f, b = 0.f;
+  // g is pinned as the ROUNDED product in both loops (as gelu4_rounded pins its results; the kernels below keep g in registers):
+  // left to the compiler, the second loop's g - a becomes fma(dy, gamma, -a), and a single-column row gets rstd times the
+  // product's rounding residual instead of 0
   for (int c = lane; c < cols; c += 64) {
-    const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
+    float g = gr[c] * gamma[c];
+    asm volatile("" : "+v"(g));
+    const float xh = (xr[c] - mean) * rstd;
     a += g; b += g * xh;
   }
   a = wave_sum(a) / (float)cols; b = wave_sum(b) / (float)cols;
   for (int c = lane; c < cols; c += 64) {
-    const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
+    float g = gr[c] * gamma[c];
+    asm volatile("" : "+v"(g));
+    const float xh = (xr[c] - mean) * rstd;
     float v = rstd * (g - a - xh * b);
     if (dres) v += dres[row * cols + c];
     dx[row * cols + c] = v;
@@ -465,7 +472,10 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_fused_kernel(const float* __re
     float mean = 0.f;
 #pragma unroll
     for (int k = 0; k < NW; ++k) mean += red[0][k][0];
-    mean *= 1.0f / (float)COLS;
+    // a true division, as in the two row kernels above: `mean *= 1.0f / COLS` is contracted into the centring below (x - sum * inv
+    // as one fma), which keeps the reciprocal's rounding error un-rounded for 3072 and 6144 columns (1 / 3 is not an fp32 value):
+    // a row of equal values then centres to -2^-25 x instead of 0, and rstd = 1 / sqrt(eps) makes 3e-5 of it in xhat and dgamma
+    mean = mean / (float)COLS;
     float q = 0.f, a = 0.f, b = 0.f;
     float4 gv[NV];
 #pragma unroll

@@ -12,6 +12,14 @@ def _ws(nbytes: int, dev) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 4096), dtype=torch.uint8, device=dev)
 
 
+def _need_dense(*ts):
+    """The entry points that take no row pitch read and write their matrices as dense rows: a strided view would be taken for
+    a dense one and give a plausible wrong result, so it is refused here, before anything is launched."""
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"tensor of shape {tuple(t.shape)} and strides {tuple(t.stride())} must be contiguous: the kernel takes no row pitch")
+
+
 def transpose(x: torch.Tensor, pad_to: int = 1) -> torch.Tensor:
     """[R,C] -> [C,Rp] (fp32 or bf16), Rp = R rounded up to a multiple of pad_to, the padding columns zero —
     the K dimension of a GEMM operand has to be a multiple of 32 (fp32) / 64 (bf16)."""
@@ -100,6 +108,7 @@ def colsum(x: torch.Tensor, out: torch.Tensor | None = None, accumulate: bool = 
 
 def layernorm_backward(x, gamma, dy, eps=1e-5, dres=None, want_param_grads=True, dgamma_out=None, dbeta_out=None):
     """-> (dx, dgamma, dbeta); dres (optional) is added to dx (gradient arriving through the residual branch)."""
+    _need_dense(x, gamma, dy, dres, dgamma_out, dbeta_out)
     _need_cuda(x, gamma, dy, dres, dgamma_out, dbeta_out)
     R, Cc = x.shape
     dx = torch.empty_like(x)
@@ -126,6 +135,7 @@ def gelu_layernorm(pre, gamma, beta, eps=1e-5, out_dtype=torch.float32):
 def gelu_layernorm_backward(pre, gamma, dy, eps=1e-5, dres=None, dgamma_out=None, dbeta_out=None):
     """layernorm_backward with x = gelu(pre) rebuilt on load (dx = the gradient at the activation); widths the one-pass kernel
     is not built for write the activation first."""
+    _need_dense(pre, gamma, dy, dres, dgamma_out, dbeta_out)
     _need_cuda(pre, gamma, dy, dres, dgamma_out, dbeta_out)
     R, Cc = pre.shape
     lib = H.load()
