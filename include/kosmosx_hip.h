@@ -1199,6 +1199,60 @@ int kx_dropout_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, int32_t si
 int kx_set_tuning(int key, int value);
 
 /* ------------------------------------------------------------------------------------------
+ * Token-automaton constrained decoding (added within ABI 7: one struct and one function are appended; no existing layout moves
+ * and the kx_struct_id list is unchanged — kx_automaton_args carries its own struct_bytes, which kx_automaton_step checks, as
+ * kx_spec_args does — so kx_version() stays 7).
+ *
+ * Where kx_constrain_logits bans ids by the row's history, kx_automaton_step bans them by the row's STATE in an automaton over
+ * token ids that the caller compiled (a set of answers, a whitelist, a regular expression or a schema over ids).  The state lives
+ * on the device and advances from the token kx_sample_logits or kx_beam_step just left there.  One launch, issued BEFORE the
+ * sampler or the beam step (after the step's kx_constrain_logits launch, if any) on the fp32 rows logits [B, V] (any ld >= V) that
+ * kernel is about to read; a banned id's logit becomes -inf and nothing else is written, so neither kernel changes and the mask
+ * commutes with the other bans and with the repetition penalty.  The logits are never read.
+ *
+ * The automaton is four device tables in CSR form, uploaded once per generate() call; S states and E edges are host scalars:
+ *   edge_off     int32 [S + 1]   state s owns edges [edge_off[s], edge_off[s + 1])
+ *   edge_tok     int32 [E]       the id an edge is taken on, strictly ascending within a state
+ *   edge_next    int32 [E]       the next state, or -1: this id is banned here
+ *   default_next int32 [S]       where an id the state does not list leads, or -1: every unlisted id is banned
+ * (sparse-allow states: default -1 and a few edges; sparse-deny states: a default and a few -1 edges; no S x V table.)
+ * state_in int32 [B_in], state_out int32 [B] (must not overlap: KX_ERR_INVALID_ARG, nothing launched — a loop alternates two
+ * buffers, which is what lets several workgroups work on one row), src_row int32 [B] or NULL (beams: kx_beam_step's src_row, the row
+ * of state_in each row descends from; NULL needs B_in == B), last_token int64 [B] or NULL (NULL at step 0), finished uint8 [B] or
+ * NULL (read only).  Per row b, in order:
+ *   1. s = state_in[src_row ? src_row[b] : b]; a src_row entry outside [0, B_in) or an s outside [0, S) is the dead state -1;
+ *   2. finished[b] != 0: state_out[b] = s and the row is left untouched;
+ *   3. last_token != NULL and s >= 0: advance on t = last_token[b] — a listed edge gives s = its edge_next (maybe -1), an unlisted
+ *      t in [0, V) gives s = default_next[s], a t outside [0, V) gives -1;
+ *   4. state_out[b] = s;
+ *   5. mask: in the dead state the whole row becomes -inf; otherwise id v is allowed iff it is listed with next >= 0, or unlisted
+ *      with default_next[s] >= 0.  Allowed entries keep their bit pattern, NaN included;
+ *   6. range: offsets are clamped into [0, E] and a state whose offsets are out of order has no edges; an edge_tok outside [0, V)
+ *      is skipped; an edge_next or default_next outside [-1, S) is read as -1; ids are compared as values and never used as an index
+ *      without the range check: memory safety does not depend on the device data.
+ * A row in which every id is banned falls under the sampler's rule 6: it emits pad_id and becomes finished — a state with no way
+ * out is how a grammar without an EOS ends a row.  Under beams such a state only kills the beam: a hypothesis ends by eos_id alone.
+ * 256-thread workgroups, one per (row, slice of 4096 ids): each repeats the row's advance (a binary search over the state's
+ * edges), the row's first writes state_out[b]; the slice's allowed set is a 512-byte bitmap in LDS filled from the default and
+ * edited per edge with LDS atomics, then consecutive lanes store -inf to consecutive banned ids.
+ * Limits (KX_ERR_UNSUPPORTED, before any launch): V <= 2^23 (kx_sample_logits' own limit; the bitmap covers a slice, not the row);
+ * 1 <= S < 2^31, E < 2^31; B x ceil(V / 4096) < 2^31 workgroups.  Argument errors name the argument.  Never allocates, never
+ * synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_automaton_args) of the caller ("stale binding" otherwise) */
+  int32_t reserved;
+  float* logits; int64_t ld; int64_t B; int64_t V;
+  const int32_t* edge_off; const int32_t* edge_tok; const int32_t* edge_next; const int32_t* default_next;
+  int64_t S; int64_t E;
+  const int32_t* state_in; int64_t B_in;
+  int32_t* state_out;
+  const int32_t* src_row;                     /* [B] or NULL */
+  const int64_t* last_token;                  /* [B] or NULL */
+  const uint8_t* finished;                    /* [B] or NULL, read only */
+} kx_automaton_args;
+int kx_automaton_step(const kx_automaton_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process kernel timing (bench.py's roofline leg; the reference's own ad-hoc equivalents are the
  * wall-clock fences of /root/reference/tests/test_benchmarking.py:68-95,192-196).
  * When enabled, every kernel launch made through this library is bracketed by hipEventRecord on

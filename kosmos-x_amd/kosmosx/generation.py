@@ -43,7 +43,15 @@ each sampler launch writes the log-prob of the token just drawn under the model'
 the row's k most likely (log-prob, id) pairs into column g of buffers allocated before the loop; rows that entered the sampler launch
 finished keep exact zeros.  No logits row is kept and the host reads nothing more.
 
-Not offered: log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
+Token automata (``token_automaton``, ``automaton_start``; every loop but lookup_loop): every row carries a state of a
+kosmosx.automaton.TokenAutomaton in device memory; one kx_automaton_step launch in front of the sampler (or the beam step), after
+the constraint launch, advances it on the token just emitted — under beams through the beam step's src_row, so the states follow the
+backpointers — and sets the logits of the ids the new state bans to -inf.  Two state buffers alternate.  A state with no way out bans
+the whole row: the sampler pads and finishes it, so the stop poll also runs whenever an automaton is given.  Without one: no
+buffer, no launch, no further host read.
+
+Not offered: token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
+that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
 sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
 (n-grams, multi-token bad words, stop sequences).
@@ -62,7 +70,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
-                  prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0):
+                  prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0, token_automaton=None,
+                  automaton_start=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -86,6 +95,15 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     the raw row is a clone taken before it (the one ``output_logits`` keeps, when on).  A row that enters the sampler launch finished
     emits a pad: the ``finished`` bytes of that moment (what ``pad_launches`` counts) are snapshotted into a uint8 buffer and passed
     as the launch's ``skip``, its slots stay 0.0 / -1; when nothing can finish a row no snapshot is taken.
+    ``token_automaton`` / ``automaton_start`` (check_automaton_args): two [B] int32 state buffers, the first holding the start states,
+    are allocated before the loop and alternate; one kx_automaton_step launch per token on the row the sampler is about to read — after
+    the step's constraint launch, so a row a stop sequence just finished is left alone — advances the states on ``nxt`` (step 0: no
+    advance) and bans what the new state does not allow.  The bans add up with the constraints'; the raw row ``output_logits`` and
+    ``output_logprobs`` use is taken before both.  A state with no way out bans the whole row: the sampler emits a pad and finishes
+    the row (its rule 6), so rows end without an EOS and the stop poll runs whenever an automaton is given.  That pad is no token of
+    the row: a row that the sampler launch finished on a token other than the EOS is counted in ``pad_launches`` and added to the
+    launch's ``skip`` of ``output_logprobs`` (three small torch launches per step, only with an automaton and one of the two).
+    Without an automaton: no buffer, no launch, no further host read.
     Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits``; then with ``output_logprobs`` the fp32
     [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
     B, T, V = logits.shape
@@ -95,6 +113,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     dev = logits.device
     cons = check_constraint_args(V, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                                  min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
+    auto = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
+    can_finish = eos_token_id is not None or (cons is not None and cons["stop"]) or auto is not None
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(B, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -113,8 +133,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if k > 0:
             top_lp = torch.zeros((B, max_new_tokens, k), dtype=torch.float32, device=dev)
             top_ids = torch.full((B, max_new_tokens, k), -1, dtype=torch.int64, device=dev)
-        if eos_token_id is not None or (cons is not None and cons["stop"]):
+        if can_finish:
             snap = torch.empty(B, dtype=torch.uint8, device=dev)          # ``finished`` as the sampler launch met it
+    if auto is not None and pad_launches is not None and snap is None:
+        snap = torch.empty(B, dtype=torch.uint8, device=dev)
     positions = None
     if lengths is not None:
         # Row b's first token comes from logits[b, lengths[b] - 1]; from here on its position lives on the device.  The padded
@@ -133,6 +155,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         plens = None
         if lengths is not None:
             plens = torch.tensor(lengths if text_lengths is None else text_lengths, dtype=torch.int32, device=dev)
+    if auto is not None:                                                  # the one upload: the automaton's tables and the start states
+        table = ops.AutomatonTable(*token_automaton.tables(), dev)
+        states = (torch.tensor(auto, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        not_eos = -1 if eos_token_id is None else int(eos_token_id)
     n = 0
     for g in range(max_new_tokens):
         constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
@@ -140,13 +166,15 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if output_logits:
             kept.append(row.clone())                                      # the model's own logits: before any ban (the sampler only reads the row)
             raw = kept[-1]
-        elif output_logprobs and constrained:
-            raw = row.clone()                                             # (the constraint launch edits the row in place)
+        elif output_logprobs and (constrained or auto is not None):
+            raw = row.clone()                                             # (the constraint and automaton launches edit the row in place)
         if constrained:
             ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
                                  no_repeat_ngram_size=cons["ngram"], bad_words=bad, stop_sequences=stop,
                                  min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
+        if auto is not None:
+            ops.automaton_step(row, table, states[g & 1], states[1 - (g & 1)], last_token=nxt if g else None, finished=finished)
         if pad_launches is not None:
             pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
         if snap is not None:
@@ -161,12 +189,19 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                               do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
                               hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                               out=nxt, out_tokens=out, out_col=g)
+        if auto is not None and snap is not None:
+            # a row this launch finished on a token other than the EOS had no candidate: what it emitted is a pad, no token of the row
+            dead = (finished - snap) * (nxt != not_eos)
+            if pad_launches is not None:
+                pad_launches.add_(dead)
+            if output_logprobs:
+                snap.add_(dead)                                           # (its log-prob slots stay 0.0 / -1)
         if output_logprobs:
             ops.step_logprobs(raw, nxt, out=lp, col=g, skip=snap, top_n=k, top_out=top_lp, top_ids=top_ids)
         n = g + 1
         if n == max_new_tokens:
             break
-        if (eos_token_id is not None or (cons is not None and cons["stop"])) and eos_poll > 0 and n % eos_poll == 0:
+        if can_finish and eos_poll > 0 and n % eos_poll == 0:
             if positions is None:
                 if bool(finished.all()):
                     break                                                 # the loop's only device-to-host read
@@ -273,6 +308,46 @@ def check_logprob_args(vocab: int, *, output_logprobs=False, top_logprobs=0, bea
     return k
 
 
+def check_automaton_args(vocab: int, batch: int, *, token_automaton=None, automaton_start=None, prompt_lookup_num_tokens=0):
+    """ValueError (naming ``token_automaton`` or ``automaton_start``) for what generate() refuses of the automaton arguments, before
+    the device check and any launch.  ``batch``: the prompts of the call.  Returns None without an automaton (no buffer, no launch),
+    else the host list of the rows' start states [batch]."""
+    from .automaton import TokenAutomaton
+    if token_automaton is None:
+        if automaton_start is not None:
+            raise ValueError("automaton_start gives every row's start state in a token_automaton: it needs one")
+        return None
+    if not isinstance(token_automaton, TokenAutomaton):
+        raise ValueError(f"token_automaton must be a kosmosx.automaton.TokenAutomaton (or None), got {type(token_automaton).__name__}")
+    try:
+        token_automaton.check_vocab(vocab)
+    except ValueError as e:
+        raise ValueError(f"token_automaton: {e}") from None
+    if prompt_lookup_num_tokens not in (0, None):
+        raise ValueError(f"token_automaton is not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
+                         f"{prompt_lookup_num_tokens}): a verify step emits a varying number of tokens per row, the state would have to "
+                         "advance by as many; see DESIGN.md §8")
+    S = token_automaton.num_states
+    if automaton_start is None:
+        return [token_automaton.start] * batch
+    if isinstance(automaton_start, torch.Tensor):
+        t = automaton_start
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
+            raise ValueError(f"automaton_start must be {batch} integers, got a {t.dtype} tensor of shape {tuple(t.shape)}")
+        starts = t.tolist()                                # (the one read of a device tensor)
+    else:
+        try:
+            starts = [operator.index(s) for s in automaton_start]
+        except TypeError:
+            raise ValueError(f"automaton_start must be a sequence of {batch} integers or an integer tensor, got {automaton_start!r}") from None
+    if len(starts) != batch:
+        raise ValueError(f"automaton_start must have {batch} entries (one per row), got {len(starts)}")
+    for b, s in enumerate(starts):
+        if not 0 <= s < S:
+            raise ValueError(f"automaton_start[{b}] = {s} is outside the automaton's {S} states")
+    return starts
+
+
 def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
                     top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lengths=None, sequence_ids=None, output_logits=False,
                     output_scores=False, output_trace=False, beam_path=False) -> bool:
@@ -309,7 +384,8 @@ def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_seq
 
 def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tokens: int, *, num_beams: int, pos_shift: int = 0,
               length_penalty=1.0, early_stopping=False, num_return_sequences=1, eos_token_id=None, pad_token_id=1, eos_poll=8,
-              output_scores=False, output_trace=False, bad_words_ids=None, min_new_tokens=0, prompt_rows=None):
+              output_scores=False, output_trace=False, bad_words_ids=None, min_new_tokens=0, prompt_rows=None, token_automaton=None,
+              automaton_start=None):
     """Beam search after the prefill: ``logits`` [B, T, V] and ``state`` as for generate_loop (the prefill ran once per batch row;
     ``prompt_rows`` as there: ``logits`` [B, 1, V] holds the last position alone).
     Per token: kx_beam_step on the rows the last step wrote (step 0: the B prefill rows, one input beam each), kx_kv_cache_gather
@@ -318,6 +394,12 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
     and the gather's error word after the loop, nothing else.
     ``bad_words_ids`` (single ids only) and ``min_new_tokens``: one kx_constrain_logits launch on the rows before the beam step,
     with no history — and before the ``output_trace`` copy, so the trace holds what the beam step ranked.
+    ``token_automaton`` / ``automaton_start`` (check_automaton_args): one kx_automaton_step launch after it, before the trace copy too.
+    Step 0 masks the B prefill rows from the start states (one input beam each); step g >= 1 runs at B * W rows, reads the state
+    buffer step g - 1 wrote through that step's ``src_row`` — the states follow the backpointers — and advances on token[g - 1].  Two
+    [B * W] buffers alternate.  A frozen row's or an unfilled slot's pad token leads wherever it leads, usually to the dead state:
+    such beams offer no candidates anyway.  A hypothesis ends only by ``eos_token_id``; a state with no way out kills the beam, so a
+    grammar for beams ends in an EOS edge (TokenAutomaton.from_choices(..., eos_token_id=...)).
     Returns tokens int64 [B, n] (R = 1) or [B, R, n], then the fp32 [B, R] scores with ``output_scores``, then the trace dict
     with ``output_trace`` (the contract: include/kosmosx_hip.h, "Beam search on the device")."""
     B, T, V = logits.shape
@@ -347,10 +429,21 @@ def beam_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tok
     cons = check_constraint_args(V, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, eos_token_id=eos_token_id,
                                  num_beams=W)
     bad = ops.SequenceTable(cons["bad"], dev) if cons is not None and cons["bad"] else None
+    auto = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
+    if auto is not None:
+        table = ops.AutomatonTable(*token_automaton.tables(), dev)
+        start = torch.tensor(auto, dtype=torch.int32, device=dev)
+        states = tuple(torch.empty(BW, dtype=torch.int32, device=dev) for _ in range(2))
     n = 0
     for g in range(N):
         if cons is not None and (cons["every_step"] or g < cons["min_new"]):
             ops.constrain_logits(row, new_tokens=g, bad_words=bad, min_new_tokens=cons["min_new"], eos_token_id=eos_token_id)
+        if auto is not None:
+            if g == 0:
+                ops.automaton_step(row, table, start, states[0][:B])
+            else:                                                            # (src_row still holds step g - 1's rows)
+                ops.automaton_step(row, table, states[1 - (g & 1)][:B] if g == 1 else states[1 - (g & 1)], states[g & 1],
+                                   src_row=src_row, last_token=token[g - 1])
         if kept is not None:
             (kept[0].view(B, W, V)[:, 0] if g == 0 else kept[g]).copy_(row)
         ops.beam_step(row, zeros if g == 0 else score[g - 1], num_beams=W, step=g, pool=pool, done=done, scores_out=score[g],
@@ -398,12 +491,14 @@ def check_parallel_args(*, num_return_sequences=1, beams=False, prompt_lookup_nu
 
 
 def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
-                  num_return_sequences: int, lengths=None, text_lengths=None, prompt_rows=None, **loop):
+                  num_return_sequences: int, lengths=None, text_lengths=None, prompt_rows=None, token_automaton=None,
+                  automaton_start=None, **loop):
     """n = ``num_return_sequences`` sampled continuations of each of the B prefilled prompts: ``state``, ``logits``, ``prompt_tokens``,
     ``lengths``, ``text_lengths`` and ``prompt_rows`` as generate_loop takes them after a prefill at B rows, ``loop`` its further
     keyword arguments.  The state's caches become the read-only prefix caches of B * n rows (state["prefix"]): row b * n + i reads the
     len_b cache rows of sequence b and appends to its own sequence of the [L, B * n, heads, max_new_tokens, 64] tail caches.  The rows
-    then run generate_loop's ragged branch — the first logits row, the prompt tokens and the lengths repeated n times, the positions
+    then run generate_loop's ragged branch — the first logits row, the prompt tokens, the lengths and the start states of
+    ``token_automaton`` / ``automaton_start`` ([B]: prompt b's start goes to its n samples) repeated n times, the positions
     on the device — so row b * n + i gets what row b * n + i of generate_loop on the caches repeated per sample gets, bit for bit.
     Returns what generate_loop returns, at B * n rows."""
     n, N = int(num_return_sequences), int(max_new_tokens)
@@ -420,12 +515,14 @@ def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     kc = state["kcache"]
     L, _, nh, _, hd = kc.shape
     seq = [b for b in range(B) for _ in range(n)]
+    starts = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
     state["prefix"] = dict(ktail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            vtail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            prefix_seq=torch.tensor(seq, dtype=torch.int32, device=dev),
                            prefix_len=torch.tensor([plens[b] for b in seq], dtype=torch.int32, device=dev))
     return generate_loop(decoder, prec, state, first.repeat_interleave(n, dim=0).unsqueeze(1), prompt_tokens.repeat_interleave(n, dim=0),
-                         N, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T, **loop)
+                         N, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T,
+                         token_automaton=token_automaton, automaton_start=None if starts is None else [starts[b] for b in seq], **loop)
 
 
 MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
@@ -739,6 +836,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     decoder, prec, vocab, tokens = model.decoder, model.precision, model.embed.weight.shape[0], prompt["tokens"]
     sampling = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
     constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
+    automaton = ("token_automaton", "automaton_start")
     beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
         "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
         "output_scores", "output_trace"))
@@ -748,6 +846,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
         "sequence_ids", *constraints, "eos_poll"))
     check_logprob_args(vocab, beams=beams, drafts=drafts, **pick("output_logprobs", "top_logprobs"))
+    check_automaton_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*automaton, "prompt_lookup_num_tokens"))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
                                                                               "prompt_lookup_num_tokens"))
@@ -757,7 +856,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
             return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
-                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints)))
+                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton)))
         common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
@@ -766,14 +865,14 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         if beams:
             return beam_loop(decoder, prec, state, logits, max_new_tokens, **common, **pick(
                 "num_beams", "length_penalty", "early_stopping", "num_return_sequences", "output_scores", "output_trace",
-                "bad_words_ids", "min_new_tokens"))
+                "bad_words_ids", "min_new_tokens", *automaton))
         if samples > 1:
             return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
                                  lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints))
+                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton))
         return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
                              lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints))
+                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton))
 
 
 def run_score(model, prompt: dict, continuations, kw: dict):
@@ -1002,19 +1101,22 @@ class Session:
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, prompt_lengths=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
-                 prefill_chunk=None, output_logprobs=False, top_logprobs=0):
+                 prefill_chunk=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None):
         """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
         at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
         session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
         constraints see the text ids of the whole conversation.  A turn that does not fit — the longest row's cached rows + the
         padded block's width + ``max_new_tokens`` > capacity — raises IndexError before any launch and leaves the session where it
         was.  An error after the first launch (an id outside the vocabulary) leaves it where it was too: the rows the turn wrote
-        lie at or after every row's valid length."""
+        lie at or after every row's valid length.
+        ``token_automaton`` / ``automaton_start``: this turn's own automaton, every row beginning in its start state — the states of
+        an earlier turn are not kept, and the automaton reads the turn's output only."""
         lens = self._check_turn(x, prompt_lengths)
         vocab = self._model.embed.weight.shape[0]
         check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                               min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
         check_logprob_args(vocab, output_logprobs=output_logprobs, top_logprobs=top_logprobs)
+        check_automaton_args(vocab, self.batch, token_automaton=token_automaton, automaton_start=automaton_start)
         chunk = check_prefill_chunk(prefill_chunk)
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
@@ -1033,7 +1135,7 @@ class Session:
                     seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
                     output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                     min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, output_logprobs=output_logprobs,
-                    top_logprobs=top_logprobs))
+                    top_logprobs=top_logprobs, token_automaton=token_automaton, automaton_start=automaton_start))
             finally:
                 self._state["pos_max"] = max(self._cached)
             out = res[0] if isinstance(res, tuple) else res

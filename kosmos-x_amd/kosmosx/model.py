@@ -1333,7 +1333,8 @@ class Kosmos(nn.Module):
                  early_stopping=False, num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
-                 prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0):
+                 prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
+                 token_automaton=None, automaton_start=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1395,7 +1396,20 @@ class Kosmos(nn.Module):
         (``return_session``).  It composes with sampling, ``prompt_lengths``, ``num_return_sequences`` (rows b * n + i), the
         constraints, ``prefill_chunk`` and sessions; with ``num_beams`` > 1 (beams have ``output_scores``) or
         ``prompt_lookup_num_tokens`` > 0, with ``top_logprobs`` outside 0..16 or above the vocabulary, or ``top_logprobs`` > 0
-        without ``output_logprobs``: ValueError."""
+        without ``output_logprobs``: ValueError.
+        ``token_automaton`` (a kosmosx.automaton.TokenAutomaton): the output must follow a token-level automaton — one of a set of
+        answers (``TokenAutomaton.from_choices``), a whitelist (``from_allowed``) or a grammar the caller compiled to ids.  Every
+        row's state lives on the device; one kx_automaton_step launch in front of the sampler (or the beam step) advances it on the
+        token just emitted and sets the logits of the ids the new state bans to -inf, after the other constraints' launch: the bans
+        add up.  ``automaton_start`` (B ints or an integer tensor; default: the automaton's ``start``): every row's start state —
+        with ``TokenAutomaton.union`` rows can follow different grammars; under ``num_return_sequences`` prompt b's start goes to
+        its n samples.  A state with no way out ends the row: it is padded from there on and the loop ends at the poll, with or
+        without an ``eos_token_id``.  Under beams a hypothesis ends by ``eos_token_id`` alone and a state with no way out only kills
+        the beam, so grammars for beams end in an EOS edge (``from_choices(..., eos_token_id=...)``).  ``output_logits`` and
+        ``output_logprobs`` keep returning the model's own distribution.  It composes with sampling, ``prompt_lengths``,
+        ``num_return_sequences``, beams, the constraints, ``prefill_chunk`` and sessions (every turn takes its own automaton and starts
+        from its start state); a value that is not a TokenAutomaton, an id above the vocabulary, a bad ``automaton_start`` or
+        ``prompt_lookup_num_tokens`` > 0 with it: ValueError."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1408,7 +1422,8 @@ class Kosmos(nn.Module):
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
-            output_logprobs=output_logprobs, top_logprobs=top_logprobs))
+            output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
+            automaton_start=automaton_start))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1572,7 +1587,7 @@ class KosmosLanguage(nn.Module):
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
-                 session_capacity=None, output_logprobs=False, top_logprobs=0):
+                 session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1581,7 +1596,8 @@ class KosmosLanguage(nn.Module):
         ``output_acceptance``: speculative decoding by prompt lookup, as there; ``prefill_chunk``: the prompt prefilled that many
         rows at a time, as there; ``return_session`` and ``session_capacity``: the call also returns a Session that takes
         further turns on the kept KV cache, as there; ``output_logprobs`` and ``top_logprobs``: every generated token's log-prob
-        and the most likely alternatives, as there)."""
+        and the most likely alternatives, as there; ``token_automaton`` and ``automaton_start``: the output follows a token-level
+        automaton whose state lives on the device, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1594,7 +1610,8 @@ class KosmosLanguage(nn.Module):
             min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
-            output_logprobs=output_logprobs, top_logprobs=top_logprobs))
+            output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
+            automaton_start=automaton_start))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):

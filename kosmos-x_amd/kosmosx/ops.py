@@ -560,6 +560,65 @@ def constrain_logits(logits, *, history=None, hist_len=0, prompt_width=0, prompt
     H.check(H.load().kx_constrain_logits(C.byref(a), _stream()), "kx_constrain_logits")
 
 
+class AutomatonTable:
+    """A token automaton in the CSR form kx_automaton_step reads, the counterpart of SequenceTable: ``edge_off`` int32 [S + 1],
+    ``edge_tok`` / ``edge_next`` int32 [E] and ``default_next`` int32 [S] on the device (TokenAutomaton.tables() makes them; raw
+    arrays are taken as they are — the kernel range-checks what it reads).  Built once per generate() call (the one upload), passed
+    to every ops.automaton_step of the loop."""
+
+    def __init__(self, edge_off, edge_tok, edge_next, default_next, device):
+        host = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu() for t in (edge_off, edge_tok, edge_next, default_next)]
+        self.S, self.E = int(host[3].numel()), int(host[1].numel())
+        if self.S < 1:
+            raise ValueError("AutomatonTable: default_next is empty: an automaton has at least one state")
+        if host[0].numel() != self.S + 1:
+            raise ValueError(f"AutomatonTable: edge_off must have {self.S + 1} entries (states + 1), got {host[0].numel()}")
+        if host[2].numel() != self.E:
+            raise ValueError(f"AutomatonTable: edge_next must have {self.E} entries (one per edge_tok), got {host[2].numel()}")
+        # (an empty tensor has no storage to point at: one unused word keeps the pointers valid; E stays 0)
+        self.edge_off, self.edge_tok, self.edge_next, self.default_next = (
+            (t if t.numel() else torch.zeros(1, dtype=torch.int32)).to(device).contiguous() for t in host)
+
+
+def automaton_step(logits, table, state_in, state_out, *, src_row=None, last_token=None, finished=None):
+    """Advance every row's automaton state and ban what the new state does not allow in fp32 `logits` [B, V] (row stride >= V) IN
+    PLACE, by one launch, before ops.sample_logits or ops.beam_step reads them (kx_automaton_step in include/kosmosx_hip.h): a
+    banned id's logit becomes -inf, nothing else is written.
+
+    ``table``: AutomatonTable.  state_in int32 [B_in] / state_out int32 [B]: two buffers that do not overlap.  src_row int32 [B]:
+    row b comes from state_in[src_row[b]] (beams); without it B_in == B.  last_token int64 [B]: the token the state advances on
+    (None at step 0: mask only).  finished uint8 [B] (read only): finished rows carry their state over and keep their logits.
+    Returns None."""
+    if not isinstance(table, AutomatonTable):
+        raise TypeError(f"automaton_step: table must be an ops.AutomatonTable, got {type(table).__name__}")
+    _need_cuda(logits, state_in, state_out, src_row, last_token, finished, table.edge_off, table.edge_tok, table.edge_next,
+               table.default_next)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("automaton_step: logits must be fp32 [B, V] with unit column stride")
+    for name, t, dt in (("state_in", state_in, torch.int32), ("state_out", state_out, torch.int32), ("src_row", src_row, torch.int32),
+                        ("last_token", last_token, torch.int64), ("finished", finished, torch.uint8)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"automaton_step: {name} must be a contiguous {dt} tensor")
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t is None:
+            raise TypeError(f"automaton_step: {name} must be a contiguous {torch.int32} tensor, got None")
+    B, V = logits.shape
+    for name, t in (("state_out", state_out), ("src_row", src_row), ("last_token", last_token), ("finished", finished)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"automaton_step: {name} must have shape [{B}]")
+    if state_in.dim() != 1 or state_in.shape[0] < 1 or (src_row is None and state_in.shape[0] != B):
+        raise ValueError(f"automaton_step: state_in must have shape [{B}]" + (" (any length >= 1 with a src_row)" if src_row is not None else "")
+                         + f", got {tuple(state_in.shape)}")
+    a = H.AutomatonArgs()
+    a.logits, a.ld, a.B, a.V = logits.data_ptr(), (logits.stride(0) if B > 1 else max(logits.stride(0), V)), B, V
+    a.edge_off, a.edge_tok, a.edge_next, a.default_next = (t.data_ptr() for t in (table.edge_off, table.edge_tok, table.edge_next,
+                                                                                  table.default_next))
+    a.S, a.E = table.S, table.E
+    a.state_in, a.B_in, a.state_out = state_in.data_ptr(), state_in.shape[0], state_out.data_ptr()
+    a.src_row, a.last_token, a.finished = H.ptr(src_row), H.ptr(last_token), H.ptr(finished)
+    H.check(H.load().kx_automaton_step(C.byref(a), _stream()), "kx_automaton_step")
+
+
 def embed_step(tokens, embed, pos, pos_a, pos_b=-1):
     """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
     kx_embed_step: [B, d] fp32 rows embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b]) for int64 ``tokens`` [B] on the device."""
