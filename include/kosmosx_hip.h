@@ -1253,6 +1253,62 @@ typedef struct {
 int kx_automaton_step(const kx_automaton_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Logit shaping: logit bias, presence / frequency penalties and min-p (added within ABI 7: one struct and two functions are
+ * appended; no existing layout moves and the kx_struct_id list is unchanged — kx_shape_args carries its own struct_bytes, which
+ * kx_shape_logits checks, as kx_automaton_args does; kx_sample_args is untouched — so kx_version() stays 7).
+ *
+ * Order per row and step: kx_constrain_logits' bans, kx_automaton_step's bans, kx_shape_logits, then the sampler; inside the
+ * sampler min-p comes after top-p.
+ *
+ * kx_shape_logits: one launch on the fp32 rows logits [B, V] (any ld >= V) the sampler is about to read, edited in place.
+ *   bias_off  int32 [B + 1] or NULL   row b owns the bias entries [bias_off[b], bias_off[b + 1]) (CSR; n_bias entries in all)
+ *   bias_ids  int32 [n_bias]          the ids, strictly ascending within a row
+ *   bias_val  fp32  [n_bias]          finite, or -inf: a ban
+ *   counts    int32 [B, V] in/out, or NULL when both penalties are 0: c_i = how often THIS call has emitted id i for the row so
+ *             far — the caller zeroes it once before the first step; the prompt does not count
+ *   frequency f, presence p           finite host floats, negative allowed
+ *   last_token int64 [B] or NULL      the sampler's next_token of the previous step (NULL at step 0)
+ *   finished  uint8 [B] or NULL       read only
+ * Per row b, in order:
+ *   1. finished[b] != 0: the row is left alone, its logits and its counts (the pads of a finished row do not count);
+ *   2. count: counts[b, last_token[b]] += 1; a last_token outside [0, V) is ignored;
+ *   3. bias: every listed id gets l = l + value, one IEEE fp32 add;
+ *   4. penalty: where c_i > 0, l = (l - f * (float)c_i) - p — three separate IEEE fp32 operations, never contracted into an FMA,
+ *      so a numpy float32 restatement matches bit for bit; where c_i == 0 the logit is untouched;
+ *   5. a logit that is -inf or NaN when step 3 or step 4 meets it keeps its bit pattern: a bias never revives a banned id;
+ *   6. range: offsets are clamped into [0, n_bias] and a row whose offsets are out of order has no entries; a bias id outside
+ *      [0, V) is skipped; ids and the last token are compared as values and never used as an index without the range check: a
+ *      malformed table changes what is shaped, never what is addressed.
+ * The shaping comes before the sampler's own repetition penalty (its rule 1).
+ * 256-thread workgroups, one per (row, slice of 4096 ids), with no hand-off between workgroups: the thread that owns element i is
+ * the only one that reads or writes counts[b, i] and logits[b, i] — the count is c = stored + (i == last), stored back by that
+ * owner; the bias entries are applied by the workgroup that owns their slice, before a barrier and the penalty pass.
+ * Limits (KX_ERR_UNSUPPORTED, before any launch): V <= 2^23 (kx_sample_logits' own limit), n_bias < 2^31, B x ceil(V / 4096) <
+ * 2^31 workgroups.  Argument errors (a non-finite penalty, a penalty without counts, neither a bias table nor counts) name the
+ * argument.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_shape_args) of the caller ("stale binding" otherwise) */
+  int32_t reserved;
+  float* logits; int64_t ld; int64_t B; int64_t V;
+  const int32_t* bias_off;                    /* [B + 1] or NULL */
+  const int32_t* bias_ids; const float* bias_val; int64_t n_bias;
+  int32_t* counts;                            /* [B, V] in/out, or NULL */
+  float frequency; float presence;
+  const int64_t* last_token;                  /* [B] or NULL */
+  const uint8_t* finished;                    /* [B] or NULL, read only */
+} kx_shape_args;
+int kx_shape_logits(const kx_shape_args* args, void* stream);
+
+/* kx_sample_logits_min_p: kx_sample_logits (positions == NULL; advance is unused) or kx_sample_logits_ragged (positions != NULL)
+ * with one more filter, min_p = m in [0, 1] (0 = off: the launch of the other two entry points).  The `transformers` order —
+ * temperature -> top-k -> top-p -> min-p: after top-k and top-p have fixed their threshold on x = penalised logit / T, the kept
+ * set is additionally restricted to x_i >= x_max + lm, one fp32 add and a compare, with lm = (float)log((double)m) computed once
+ * on the host: p_i >= m p_max.  Top-p's mass stays renormalised over what top-k kept, not over what min-p keeps.  The arg max is
+ * always kept; m = 1 keeps exactly the ties at the maximum.  Under greedy it is ignored, as top-k is.  kx_sample_args is unchanged.
+ * An m outside [0, 1] (NaN included): KX_ERR_INVALID_ARG naming min_p, before any launch. */
+int kx_sample_logits_min_p(const kx_sample_args* args, int32_t* positions, int64_t advance, float min_p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process kernel timing (bench.py's roofline leg; the reference's own ad-hoc equivalents are the
  * wall-clock fences of /root/reference/tests/test_benchmarking.py:68-95,192-196).
  * When enabled, every kernel launch made through this library is bracketed by hipEventRecord on

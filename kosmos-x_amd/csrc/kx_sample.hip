@@ -49,7 +49,7 @@ __device__ __forceinline__ float load_x(const SampleParams& a, const float* __re
 // Returns false (key untouched) when the whole weight stays below target.
 // (OWNER: one instantiation per kernel that calls it, so that each stays a single-caller function the compiler folds into its
 // kernel exactly as it did when there was one kernel)
-template <bool MASS, bool OWNER>
+template <bool MASS, bool OWNER, bool MINP = false>
 __device__ bool radix_select(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, float m,
                              unsigned limit, unsigned long long target, unsigned long long* hist,
                              unsigned long long* gsum, unsigned long long* sel, unsigned& key_out) {
@@ -126,12 +126,20 @@ __device__ bool radix_select(const SampleParams& a, const float* __restrict__ ro
 // with advance != 0 thread 0 stores it back after the draw — the same launch moves the row on.  Nothing else differs.
 // The ragged launch passes one more kernel argument (R = RaggedPos); the uniform launch has an empty pack, i.e. the signature and
 // kernel-argument layout it always had.
+// MINP (kx_sample_logits_min_p): one more kernel argument behind it (MinP: lm = log(min_p), taken on the host) and one more
+// threshold after top-p, x_i >= x_max + lm.  The empty and the RaggedPos-only pack stay the kernels they always were.
 struct RaggedPos { int* positions; int advance; };
+struct MinP { float lm; };
 template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
+template <typename A, typename... Rest> __device__ __forceinline__ const auto& last_arg(const A& a, const Rest&... rest) {
+  if constexpr (sizeof...(Rest) == 0) return a; else return last_arg(rest...);
+}
+template <typename T, typename... R> constexpr bool pack_has = (std::is_same_v<T, R> || ...);
 
 template <typename... R>
 __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const R... r) {
-  constexpr bool RAGGED = sizeof...(R) != 0;
+  constexpr bool RAGGED = pack_has<RaggedPos, R...>;    // (first of the pack)
+  constexpr bool MINP = pack_has<MinP, R...>;           // (last of the pack)
   __shared__ unsigned long long hist[BINS];
   __shared__ unsigned long long red[SW];
   __shared__ unsigned long long gsum[BINS / 64];
@@ -185,7 +193,7 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
       unsigned tau = KEY_MIN_VALID;
       if (a.k > 0 && a.k < a.V) {
         unsigned kk;
-        if (radix_select<false, RAGGED>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
+        if (radix_select<false, RAGGED, MINP>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
       }
       if (a.p < 1.0f) {
         unsigned long long z = 0;                     // mass of what top-k kept
@@ -198,7 +206,11 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
         // keep iff (mass strictly above) < p Z; the masses are integers, so "< p Z" is "< ceil(p Z)"
         const unsigned long long target = (unsigned long long)ceil((double)a.p * (double)z);
         unsigned kp;
-        if (radix_select<true, RAGGED>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
+        if (radix_select<true, RAGGED, MINP>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
+      }
+      if constexpr (MINP) {                             // min-p, after top-p: x_i >= x_max + lm (keys order as the values do)
+        const unsigned km = f2key(m + last_arg(r...).lm);
+        tau = km > tau ? km : tau;
       }
       // Gumbel arg max over the kept set {key >= tau}; Philox block `base / 4` serves elements base .. base + 3, so here
       // (and only here) a thread owns four consecutive elements
@@ -322,7 +334,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const long long* __rest
 
 }  // namespace
 
-static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream) {
+static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream, const float* log_min_p = nullptr) {
   KX_REQUIRE(args != nullptr, "kx_sample_logits: null args");
   KX_REQUIRE(args->struct_bytes == sizeof(kx_sample_args),
              "kx_sample_logits: stale binding — caller declares kx_sample_args as %u bytes, this library (ABI %d) as %zu",
@@ -368,7 +380,11 @@ static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t a
   p.kept_count = args->kept_count; p.keep_mask = args->keep_mask;
   const size_t lds = p.pen ? (size_t)((args->V + 31) / 32) * 4 : 0;
   KxProfScope prof(KX_K_MISC, args->B, args->V, 0, (hipStream_t)stream);
-  if (positions) hipLaunchKernelGGL(sample_kernel<RaggedPos>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+  if (log_min_p && positions)
+    hipLaunchKernelGGL((sample_kernel<RaggedPos, MinP>), dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+                       RaggedPos{(int*)positions, (int)advance}, MinP{*log_min_p});
+  else if (log_min_p) hipLaunchKernelGGL(sample_kernel<MinP>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p, MinP{*log_min_p});
+  else if (positions) hipLaunchKernelGGL(sample_kernel<RaggedPos>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
                                     RaggedPos{(int*)positions, (int)advance});
   else hipLaunchKernelGGL(sample_kernel<>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p);
   KX_CHECK_LAUNCH("kx_sample_logits");
@@ -381,6 +397,16 @@ extern "C" int kx_sample_logits_ragged(const kx_sample_args* args, int32_t* posi
   KX_REQUIRE(positions != nullptr, "kx_sample_logits_ragged: null positions");
   KX_REQUIRE(advance >= 0 && advance <= 0x7fffffffll, "kx_sample_logits_ragged: advance=%lld must be >= 0", (long long)advance);
   return sample_impl(args, positions, advance, stream);
+}
+
+// min_p == 0: the launches of the two entry points above.  Otherwise lm = log(min_p) in double, rounded once to fp32 (m = 1: +0).
+extern "C" int kx_sample_logits_min_p(const kx_sample_args* args, int32_t* positions, int64_t advance, float min_p, void* stream) {
+  KX_REQUIRE(min_p >= 0.0f && min_p <= 1.0f, "kx_sample_logits_min_p: min_p=%g must be in [0, 1]", (double)min_p);
+  KX_REQUIRE(positions == nullptr || (advance >= 0 && advance <= 0x7fffffffll), "kx_sample_logits_min_p: advance=%lld must be >= 0",
+             (long long)advance);
+  if (min_p == 0.0f) return sample_impl(args, positions, positions ? advance : 0, stream);
+  const float lm = (float)log((double)min_p);
+  return sample_impl(args, positions, positions ? advance : 0, stream, &lm);
 }
 
 // span == 1: kx_step_prepare's launch.  span > 1: B counts the rows, `span` consecutive ones per entry of positions (see the kernel).

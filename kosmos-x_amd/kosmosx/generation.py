@@ -50,7 +50,15 @@ backpointers — and sets the logits of the ids the new state bans to -inf.  Two
 the whole row: the sampler pads and finishes it, so the stop poll also runs whenever an automaton is given.  Without one: no
 buffer, no launch, no further host read.
 
-Not offered: token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
+Logit shaping (``logit_bias``, ``presence_penalty``, ``frequency_penalty``, ``min_p``; generate_loop and everything that runs it): the
+request fields a completion API passes through.  One kx_shape_logits launch in front of the sampler, after the constraint and
+automaton launches, counts the token just emitted in an int32 [B, V] table that starts at zero with every call (and every turn of a
+session), adds the per-id biases (-inf = a ban) and subtracts frequency * count + presence where the count is positive — single fp32
+operations an outside reference can restate bit for bit.  ``min_p`` is one more threshold inside the sampler, after top-p
+(kx_sample_logits_min_p).  With the four at their defaults: no buffer, no launch, the sampler's old entry points.
+
+Not offered: the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
+turn, typical-p / epsilon / eta sampling; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
 that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
 sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
@@ -71,7 +79,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
                   prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0, token_automaton=None,
-                  automaton_start=None):
+                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -104,6 +112,14 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     the row: a row that the sampler launch finished on a token other than the EOS is counted in ``pad_launches`` and added to the
     launch's ``skip`` of ``output_logprobs`` (three small torch launches per step, only with an automaton and one of the two).
     Without an automaton: no buffer, no launch, no further host read.
+    ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p`` (check_shape_args; the biases are given for the B rows of
+    this call): the bias table is uploaded and the int32 [B, V] counts are zeroed once before the loop (the counts only with a
+    penalty); one kx_shape_logits launch per token on the row the sampler is about to read — after the constraint and automaton
+    launches, before ``pad_launches`` is taken — counts ``nxt`` (step 0: nothing to count; finished rows are left alone, so pads do
+    not count), adds the biases and applies the penalties over what THIS call emitted for the row: the prompt does not count, and a
+    session's turn starts from zero.  ``min_p`` goes to the sampler launch (kx_sample_logits_min_p), after top-p.  The raw row
+    ``output_logits`` and ``output_logprobs`` use is taken before the launch.  With the four at their defaults: no buffer, no
+    launch, the sampler's old entry points.
     Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits``; then with ``output_logprobs`` the fp32
     [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
     B, T, V = logits.shape
@@ -115,6 +131,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                                  min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
     auto = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
     can_finish = eos_token_id is not None or (cons is not None and cons["stop"]) or auto is not None
+    shape = check_shape_args(V, B, logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                             min_p=min_p)
+    shaping = shape is not None and shape["launch"]
+    min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(B, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -159,6 +179,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         table = ops.AutomatonTable(*token_automaton.tables(), dev)
         states = (torch.tensor(auto, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
         not_eos = -1 if eos_token_id is None else int(eos_token_id)
+    if shaping:                                                           # the one upload: the bias table; the counts start at zero
+        bias = ops.BiasTable(shape["bias"], dev) if shape["bias"] is not None else None
+        penalised = shape["frequency"] != 0.0 or shape["presence"] != 0.0
+        counts = torch.zeros((B, V), dtype=torch.int32, device=dev) if penalised else None
     n = 0
     for g in range(max_new_tokens):
         constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
@@ -166,8 +190,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if output_logits:
             kept.append(row.clone())                                      # the model's own logits: before any ban (the sampler only reads the row)
             raw = kept[-1]
-        elif output_logprobs and (constrained or auto is not None):
-            raw = row.clone()                                             # (the constraint and automaton launches edit the row in place)
+        elif output_logprobs and (constrained or auto is not None or shaping):
+            raw = row.clone()                                             # (the constraint, automaton and shaping launches edit the row in place)
         if constrained:
             ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
@@ -175,6 +199,9 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                                  min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
         if auto is not None:
             ops.automaton_step(row, table, states[g & 1], states[1 - (g & 1)], last_token=nxt if g else None, finished=finished)
+        if shaping:
+            ops.shape_logits(row, bias=bias, counts=counts, frequency_penalty=shape["frequency"], presence_penalty=shape["presence"],
+                             last_token=nxt if g else None, finished=finished)
         if pad_launches is not None:
             pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
         if snap is not None:
@@ -183,12 +210,12 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
                               history=history, hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, out=nxt, out_tokens=out, out_col=g)
+                              pad_token_id=pad_token_id, out=nxt, out_tokens=out, out_col=g, **min_p)
         else:
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
                               hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                              out=nxt, out_tokens=out, out_col=g)
+                              out=nxt, out_tokens=out, out_col=g, **min_p)
         if auto is not None and snap is not None:
             # a row this launch finished on a token other than the EOS had no candidate: what it emitted is a pad, no token of the row
             dead = (finished - snap) * (nxt != not_eos)
@@ -348,6 +375,59 @@ def check_automaton_args(vocab: int, batch: int, *, token_automaton=None, automa
     return starts
 
 
+def check_shape_args(vocab: int, batch: int, *, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, num_beams=1,
+                     prompt_lookup_num_tokens=0):
+    """ValueError (naming ``logit_bias``, ``presence_penalty``, ``frequency_penalty`` or ``min_p``) for what generate() refuses of
+    the shaping arguments, before the device check and any launch.  ``batch``: the rows the biases are given for.  Returns None
+    with everything at its default (no buffer, no launch, the sampler's old entry points), else a dict: ``bias`` (None, or
+    ``batch`` lists of (id, value) sorted by id — one dict is repeated for every row), ``frequency``, ``presence``, ``min_p``
+    (floats) and ``launch`` (whether a bias or a penalty asks for the kx_shape_logits launch; min_p alone does not)."""
+    import math
+    out = dict(bias=None)
+    for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty), ("min_p", min_p)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(v) <= 3.4028234663852886e38:
+            raise ValueError(f"{name} must be a finite number (in fp32), got {v!r}")
+        out[name.split("_")[0] if name != "min_p" else name] = float(v)
+    if not 0.0 <= out["min_p"] <= 1.0:
+        raise ValueError(f"min_p = {min_p!r} must be in [0, 1] (0 = off)")
+    if logit_bias is not None:
+        rows = [logit_bias] * batch if hasattr(logit_bias, "items") else list(logit_bias)
+        if len(rows) != batch:
+            raise ValueError(f"logit_bias must be one dict {{id: value}} or a sequence of {batch} dicts (one per row), got {len(rows)}")
+        bias = []
+        for b, r in enumerate(rows):
+            if not hasattr(r, "items"):
+                raise ValueError(f"logit_bias[{b}] must be a dict {{id: value}}, got {type(r).__name__}")
+            ent = {}
+            for i, v in r.items():
+                try:
+                    i, v = operator.index(i), float(v)
+                except (TypeError, ValueError):
+                    raise ValueError(f"logit_bias[{b}]: {i!r}: {v!r} is no (integer id, number) pair") from None
+                if not 0 <= i < vocab:
+                    raise ValueError(f"logit_bias[{b}]: id {i} is outside the vocabulary of {vocab}")
+                if i in ent:
+                    raise ValueError(f"logit_bias[{b}]: id {i} is listed twice")
+                if not (v == -math.inf or abs(v) <= 3.4028234663852886e38):
+                    raise ValueError(f"logit_bias[{b}][{i}] = {v} must be finite (in fp32) or -inf (a ban)")
+                ent[i] = v
+            bias.append(sorted(ent.items()))
+        if any(bias):
+            out["bias"] = bias
+    names = [n for n, on in (("logit_bias", out["bias"] is not None), ("presence_penalty", out["presence"] != 0.0),
+                             ("frequency_penalty", out["frequency"] != 0.0), ("min_p", out["min_p"] != 0.0)) if on]
+    if not names:
+        return None
+    if num_beams not in (1, None):
+        raise ValueError(f"{', '.join(names)}: not offered together with num_beams = {num_beams}: beams rank log-probs, and how a "
+                         "bias or a penalty enters that score is a decision of its own; see DESIGN.md §8")
+    if prompt_lookup_num_tokens not in (0, None):
+        raise ValueError(f"{', '.join(names)}: not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
+                         f"{prompt_lookup_num_tokens}): a verify step emits a varying number of tokens per row; see DESIGN.md §8")
+    out["launch"] = names != ["min_p"]
+    return out
+
+
 def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
                     top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lengths=None, sequence_ids=None, output_logits=False,
                     output_scores=False, output_trace=False, beam_path=False) -> bool:
@@ -492,13 +572,14 @@ def check_parallel_args(*, num_return_sequences=1, beams=False, prompt_lookup_nu
 
 def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
                   num_return_sequences: int, lengths=None, text_lengths=None, prompt_rows=None, token_automaton=None,
-                  automaton_start=None, **loop):
+                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, **loop):
     """n = ``num_return_sequences`` sampled continuations of each of the B prefilled prompts: ``state``, ``logits``, ``prompt_tokens``,
     ``lengths``, ``text_lengths`` and ``prompt_rows`` as generate_loop takes them after a prefill at B rows, ``loop`` its further
     keyword arguments.  The state's caches become the read-only prefix caches of B * n rows (state["prefix"]): row b * n + i reads the
     len_b cache rows of sequence b and appends to its own sequence of the [L, B * n, heads, max_new_tokens, 64] tail caches.  The rows
     then run generate_loop's ragged branch — the first logits row, the prompt tokens, the lengths and the start states of
-    ``token_automaton`` / ``automaton_start`` ([B]: prompt b's start goes to its n samples) repeated n times, the positions
+    ``token_automaton`` / ``automaton_start`` ([B]: prompt b's start goes to its n samples) and the per-prompt dicts of
+    ``logit_bias`` (prompt b's go to its n samples; every sample has its own counts) repeated n times, the positions
     on the device — so row b * n + i gets what row b * n + i of generate_loop on the caches repeated per sample gets, bit for bit.
     Returns what generate_loop returns, at B * n rows."""
     n, N = int(num_return_sequences), int(max_new_tokens)
@@ -516,13 +597,17 @@ def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     L, _, nh, _, hd = kc.shape
     seq = [b for b in range(B) for _ in range(n)]
     starts = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
+    check_shape_args(V, B, logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p)
+    if logit_bias is not None and not hasattr(logit_bias, "items"):
+        logit_bias = [list(logit_bias)[b] for b in seq]
     state["prefix"] = dict(ktail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            vtail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            prefix_seq=torch.tensor(seq, dtype=torch.int32, device=dev),
                            prefix_len=torch.tensor([plens[b] for b in seq], dtype=torch.int32, device=dev))
     return generate_loop(decoder, prec, state, first.repeat_interleave(n, dim=0).unsqueeze(1), prompt_tokens.repeat_interleave(n, dim=0),
                          N, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T,
-                         token_automaton=token_automaton, automaton_start=None if starts is None else [starts[b] for b in seq], **loop)
+                         token_automaton=token_automaton, automaton_start=None if starts is None else [starts[b] for b in seq],
+                         logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, **loop)
 
 
 MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
@@ -837,6 +922,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     sampling = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
     constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
     automaton = ("token_automaton", "automaton_start")
+    shaping = ("logit_bias", "presence_penalty", "frequency_penalty", "min_p")
     beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
         "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
         "output_scores", "output_trace"))
@@ -847,6 +933,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         "sequence_ids", *constraints, "eos_poll"))
     check_logprob_args(vocab, beams=beams, drafts=drafts, **pick("output_logprobs", "top_logprobs"))
     check_automaton_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*automaton, "prompt_lookup_num_tokens"))
+    check_shape_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*shaping, "num_beams", "prompt_lookup_num_tokens"))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
                                                                               "prompt_lookup_num_tokens"))
@@ -856,7 +943,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
             return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
-                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton)))
+                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping)))
         common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
@@ -869,10 +956,10 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         if samples > 1:
             return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
                                  lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton))
+                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
         return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
                              lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton))
+                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
 
 
 def run_score(model, prompt: dict, continuations, kw: dict):
@@ -1101,7 +1188,8 @@ class Session:
     def generate(self, x: torch.Tensor, max_new_tokens: int, *, prompt_lengths=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
-                 prefill_chunk=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None):
+                 prefill_chunk=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
+                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
         """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
         at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
         session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
@@ -1110,13 +1198,17 @@ class Session:
         was.  An error after the first launch (an id outside the vocabulary) leaves it where it was too: the rows the turn wrote
         lie at or after every row's valid length.
         ``token_automaton`` / ``automaton_start``: this turn's own automaton, every row beginning in its start state — the states of
-        an earlier turn are not kept, and the automaton reads the turn's output only."""
+        an earlier turn are not kept, and the automaton reads the turn's output only.
+        ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p``: as in generate(); the penalties count what THIS turn
+        emitted — every turn starts from zero counts, and neither the prompt nor an earlier turn's output counts."""
         lens = self._check_turn(x, prompt_lengths)
         vocab = self._model.embed.weight.shape[0]
         check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                               min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
         check_logprob_args(vocab, output_logprobs=output_logprobs, top_logprobs=top_logprobs)
         check_automaton_args(vocab, self.batch, token_automaton=token_automaton, automaton_start=automaton_start)
+        check_shape_args(vocab, self.batch, logit_bias=logit_bias, presence_penalty=presence_penalty,
+                         frequency_penalty=frequency_penalty, min_p=min_p)
         chunk = check_prefill_chunk(prefill_chunk)
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
@@ -1135,7 +1227,8 @@ class Session:
                     seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
                     output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                     min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, output_logprobs=output_logprobs,
-                    top_logprobs=top_logprobs, token_automaton=token_automaton, automaton_start=automaton_start))
+                    top_logprobs=top_logprobs, token_automaton=token_automaton, automaton_start=automaton_start,
+                    logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p))
             finally:
                 self._state["pos_max"] = max(self._cached)
             out = res[0] if isinstance(res, tuple) else res

@@ -1334,7 +1334,7 @@ class Kosmos(nn.Module):
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
                  prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
-                 token_automaton=None, automaton_start=None):
+                 token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1409,7 +1409,22 @@ class Kosmos(nn.Module):
         ``output_logprobs`` keep returning the model's own distribution.  It composes with sampling, ``prompt_lengths``,
         ``num_return_sequences``, beams, the constraints, ``prefill_chunk`` and sessions (every turn takes its own automaton and starts
         from its start state); a value that is not a TokenAutomaton, an id above the vocabulary, a bad ``automaton_start`` or
-        ``prompt_lookup_num_tokens`` > 0 with it: ValueError."""
+        ``prompt_lookup_num_tokens`` > 0 with it: ValueError.
+        ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p``: the request fields of a completion API, applied on
+        the device.  ``logit_bias``: a dict {id: value} for every row or a sequence of B such dicts; every listed id gets l + value
+        (one fp32 add; -inf bans the id, +inf and NaN are refused; ids inside the vocabulary, distinct per row); a logit that is
+        already -inf or NaN stays so.  ``frequency_penalty`` f and ``presence_penalty`` p (finite floats, negative allowed): with c_i
+        the number of times THIS call has emitted id i for the row — the prompt does not count, the pads of a finished row do not
+        count, a session's turn starts from zero — every id with c_i > 0 gets (l - f * c_i) - p, after the bias and before the
+        sampler's own ``repetition_penalty``.  The three run in one kx_shape_logits launch per token after the constraints' and the
+        automaton's, in front of the sampler.  ``min_p`` = m in [0, 1] (0 = off; only when sampling, ignored under greedy as
+        ``top_k`` is): after ``top_k`` and ``top_p`` — the `transformers` order — the kept set is restricted to the tokens whose
+        probability is at least m times the most likely one's (x_i >= x_max + log m); top-p's mass stays renormalised over what
+        top-k kept; the arg max is always kept and m = 1 keeps exactly the ties at the maximum.  ``output_logits`` and
+        ``output_logprobs`` keep returning the model's own distribution.  They compose with sampling, ``prompt_lengths``,
+        ``num_return_sequences`` (prompt b's biases go to its n samples, each with its own counts), the constraints, automata,
+        ``prefill_chunk``, log-probs and sessions; with ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0, or with a bad value:
+        ValueError naming the argument.  With the four at their defaults nothing is added."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1423,7 +1438,8 @@ class Kosmos(nn.Module):
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
             output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
-            automaton_start=automaton_start))
+            automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
+            frequency_penalty=frequency_penalty, min_p=min_p))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1587,7 +1603,8 @@ class KosmosLanguage(nn.Module):
                  num_return_sequences=1, output_scores=False, output_trace=False, _beam_path=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
-                 session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None):
+                 session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
+                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1597,7 +1614,8 @@ class KosmosLanguage(nn.Module):
         rows at a time, as there; ``return_session`` and ``session_capacity``: the call also returns a Session that takes
         further turns on the kept KV cache, as there; ``output_logprobs`` and ``top_logprobs``: every generated token's log-prob
         and the most likely alternatives, as there; ``token_automaton`` and ``automaton_start``: the output follows a token-level
-        automaton whose state lives on the device, as there)."""
+        automaton whose state lives on the device, as there; ``logit_bias``, ``presence_penalty``, ``frequency_penalty`` and
+        ``min_p``: the completion-API request fields, applied on the device, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1611,7 +1629,8 @@ class KosmosLanguage(nn.Module):
             max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
             output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
-            automaton_start=automaton_start))
+            automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
+            frequency_penalty=frequency_penalty, min_p=min_p))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):

@@ -440,7 +440,7 @@ def token_range(tokens, out=None):
 
 def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
                   position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
-                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0):
+                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0, min_p=0.0):
     """Next token of every row of fp32 `logits` [B, V] (row stride >= V), drawn on the device by one launch
     (kx_sample_logits in include/kosmosx_hip.h: repetition penalty -> temperature -> top-k -> top-p -> Gumbel-max draw
     addressed by (seed, sequence id, position); greedy when ``do_sample`` is false or ``temperature`` is 0).
@@ -450,6 +450,8 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     becomes finished.  out [B] int64 / out_tokens [B, n] int64 with ``out_col``: caller-owned places for the result.
     positions [B] int32 (device, in/out): the ragged form (kx_sample_logits_ragged) — row b draws at Philox position
     ``positions[b] + advance`` and, when ``advance`` is not 0, leaves that value in ``positions[b]``; ``position`` is unused.
+    min_p in [0, 1] (0 = off: the two entry points above are called as before): after top-p, keep only x_i >= x_max + log(min_p)
+    (kx_sample_logits_min_p, either form); ignored under greedy.
     Returns next_token [B] int64 (and kept_count [B] int32, keep_mask [B, V] uint8 with ``return_debug``)."""
     _need_cuda(logits, sequence_ids, history, finished, out, out_tokens, positions)
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
@@ -484,7 +486,15 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
         kept = torch.empty(B, dtype=torch.int32, device=logits.device)
         mask = torch.empty((B, V), dtype=torch.uint8, device=logits.device)
         a.kept_count, a.keep_mask = kept.data_ptr(), mask.data_ptr()
-    if positions is not None:
+    min_p = float(min_p)
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"sample_logits: min_p = {min_p} must be in [0, 1]")
+    if min_p != 0.0:
+        if positions is not None:
+            a.position = 0
+        H.check(H.load().kx_sample_logits_min_p(C.byref(a), H.ptr(positions), int(advance) if positions is not None else 0, min_p,
+                                                _stream()), "kx_sample_logits_min_p")
+    elif positions is not None:
         a.position = 0
         H.check(H.load().kx_sample_logits_ragged(C.byref(a), positions.data_ptr(), int(advance), _stream()), "kx_sample_logits_ragged")
     else:
@@ -617,6 +627,74 @@ def automaton_step(logits, table, state_in, state_out, *, src_row=None, last_tok
     a.state_in, a.B_in, a.state_out = state_in.data_ptr(), state_in.shape[0], state_out.data_ptr()
     a.src_row, a.last_token, a.finished = H.ptr(src_row), H.ptr(last_token), H.ptr(finished)
     H.check(H.load().kx_automaton_step(C.byref(a), _stream()), "kx_automaton_step")
+
+
+SHAPE_SLICE = 4096                      # ids per workgroup of kx_shape_logits (what its tests place their edges at)
+
+
+class BiasTable:
+    """Per-row logit biases in the CSR form kx_shape_logits reads, the counterpart of SequenceTable / AutomatonTable: ``off`` int32
+    [B + 1], ``ids`` int32 ascending within a row and ``val`` fp32 on the device.  ``rows``: B sequences of (id, value) pairs (a
+    dict's items() will do; they are sorted by id here).  Raw arrays are taken as they are with ``BiasTable.raw`` — the kernel
+    range-checks what it reads.  Built once per generate() call (the one upload), passed to every ops.shape_logits of the loop."""
+
+    def __init__(self, rows, device):
+        rows = [sorted((int(i), float(v)) for i, v in (r.items() if hasattr(r, "items") else r)) for r in rows]
+        off = [0]
+        for r in rows:
+            off.append(off[-1] + len(r))
+        self._set(off, [i for r in rows for i, _ in r], [v for r in rows for _, v in r], device)
+
+    def _set(self, off, ids, val, device):
+        host = (torch.as_tensor(off, dtype=torch.int32).reshape(-1).cpu(), torch.as_tensor(ids, dtype=torch.int32).reshape(-1).cpu(),
+                torch.as_tensor(val, dtype=torch.float32).reshape(-1).cpu())
+        if host[0].numel() < 2:
+            raise ValueError("BiasTable: off must have B + 1 >= 2 entries")
+        if host[1].numel() != host[2].numel():
+            raise ValueError(f"BiasTable: {host[1].numel()} ids but {host[2].numel()} values")
+        self.B, self.n = int(host[0].numel()) - 1, int(host[1].numel())
+        # (an empty tensor has no storage to point at: one unused word keeps the pointers valid; n stays 0)
+        self.off, self.ids, self.val = ((t if t.numel() else torch.zeros(1, dtype=t.dtype)).to(device).contiguous() for t in host)
+
+    @classmethod
+    def raw(cls, off, ids, val, device):
+        t = cls.__new__(cls)
+        t._set(off, ids, val, device)
+        return t
+
+
+def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, presence_penalty=0.0, last_token=None, finished=None):
+    """Logit bias and presence / frequency penalties on every row of fp32 `logits` [B, V] (row stride >= V) IN PLACE, by one launch,
+    after ops.constrain_logits / ops.automaton_step and before ops.sample_logits reads them (kx_shape_logits in
+    include/kosmosx_hip.h): counts[b, last_token[b]] += 1, then l = l + bias for the listed ids, then where the count c is
+    positive l = (l - frequency_penalty * c) - presence_penalty, each a single fp32 operation; -inf and NaN logits stay.
+
+    ``bias``: BiasTable of B rows (or None).  counts int32 [B, V] (in/out; None when both penalties are 0): how often this call
+    emitted each id, zeroed by the caller before the first step.  last_token int64 [B]: the sampler's token of the previous step
+    (None at step 0).  finished uint8 [B] (read only): finished rows keep their logits and their counts.  Returns None."""
+    if bias is not None and not isinstance(bias, BiasTable):
+        raise TypeError(f"shape_logits: bias must be an ops.BiasTable (or None), got {type(bias).__name__}")
+    _need_cuda(logits, counts, last_token, finished, *((bias.off, bias.ids, bias.val) if bias is not None else ()))
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("shape_logits: logits must be fp32 [B, V] with unit column stride")
+    for name, t, dt in (("counts", counts, torch.int32), ("last_token", last_token, torch.int64), ("finished", finished, torch.uint8)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"shape_logits: {name} must be a contiguous {dt} tensor")
+    B, V = logits.shape
+    for name, t in (("last_token", last_token), ("finished", finished)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"shape_logits: {name} must have shape [{B}]")
+    if counts is not None and tuple(counts.shape) != (B, V):
+        raise ValueError(f"shape_logits: counts must have shape [{B}, {V}], got {tuple(counts.shape)}")
+    if bias is not None and bias.B != B:
+        raise ValueError(f"shape_logits: bias has {bias.B} rows, logits {B}")
+    a = H.ShapeArgs()
+    a.logits, a.ld, a.B, a.V = logits.data_ptr(), (logits.stride(0) if B > 1 else max(logits.stride(0), V)), B, V
+    if bias is not None:
+        a.bias_off, a.bias_ids, a.bias_val, a.n_bias = bias.off.data_ptr(), bias.ids.data_ptr(), bias.val.data_ptr(), bias.n
+    a.counts, a.frequency, a.presence = H.ptr(counts), float(frequency_penalty), float(presence_penalty)
+    a.last_token, a.finished = H.ptr(last_token), H.ptr(finished)
+    H.check(H.load().kx_shape_logits(C.byref(a), _stream()), "kx_shape_logits")
 
 
 def embed_step(tokens, embed, pos, pos_a, pos_b=-1):
