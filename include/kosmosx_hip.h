@@ -1309,6 +1309,56 @@ int kx_shape_logits(const kx_shape_args* args, void* stream);
 int kx_sample_logits_min_p(const kx_sample_args* args, int32_t* positions, int64_t advance, float min_p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Classifier-free guidance (added within ABI 7: one struct and one function are appended; no existing layout moves and the
+ * kx_struct_id list is unchanged — kx_guidance_args carries its own struct_bytes, which kx_guidance_logits checks, as
+ * kx_shape_args does — so kx_version() stays 7).
+ *
+ * generate(guidance_scale = s) runs every sequence as two rows of one ragged batch: row b reads the prompt (the conditional row),
+ * row B + b a negative prompt or a negative image (the unconditional row); both are fed the same sampled token.  Order per step:
+ * kx_guidance_logits, then kx_constrain_logits' bans, kx_automaton_step's bans, kx_shape_logits, then the sampler — bans and
+ * biases apply to the guided row, the `transformers` order.
+ *
+ * kx_guidance_logits: one launch on B pairs of raw fp32 rows.
+ *   cond, ld_cond      fp32 [B, V]   the conditional rows
+ *   uncond, ld_uncond  fp32 [B, V]   the unconditional rows
+ *   out, ld_out        fp32 [B, V]   the guided rows; out may be cond with ld_out == ld_cond (in place), and overlaps neither input
+ *                                    otherwise
+ *   Any ld >= V; no alignment is asked of a row.
+ *   scale s            a finite host float; 1 reproduces the conditional log-softmax, 0 the unconditional one
+ *   finished  uint8 [B] or NULL      read only
+ *   positions int32 [B] or NULL      in/out: the unconditional rows' device positions
+ *   advance   0 or 1
+ * Per pair b, in order:
+ *   1. log-probs: lc_i = (c_i - max c) - log(sum exp(c - max c)), likewise lu_i from the unconditional row — the arithmetic and
+ *      the summation order of kx_token_logprob, bit for bit what it returns for that row and id;
+ *   2. combine: out_i = lu_i + s * (lc_i - lu_i) — a subtract, a multiply and an add in IEEE fp32, never contracted into an FMA, so
+ *      a numpy float32 restatement over the device's own log-probs matches bit for bit;
+ *   3. a result that is not finite (either input -inf or NaN at i, a NaN anywhere in a row — its sum is NaN —, a row of -inf
+ *      alone, overflow) is written as -inf: such an id is never a candidate, and a row of nothing but -inf makes the sampler emit
+ *      a pad and finish the row (its rule 6);
+ *   4. finished[b] != 0: out row b is not written and neither input row is read;
+ *   5. positions != NULL and advance != 0: one lane stores positions[b] + advance, finished rows included — the rule
+ *      kx_sample_logits_ragged follows for the conditional rows, so an unconditional row moves exactly when its partner does.
+ * One 256-thread workgroup per pair with no hand-off between workgroups: results do not depend on B or on the pair's index, and
+ * two calls give identical bits.
+ * Limits (KX_ERR_UNSUPPORTED, before any launch): V <= 2^23 (kx_sample_logits' own limit).  Argument errors (KX_ERR_INVALID_ARG,
+ * nothing launched, the message names the argument): a null cond, uncond or out, B < 1, V < 1, an ld < V, a non-finite scale, an
+ * advance outside {0, 1}, out overlapping uncond, out overlapping cond without being cond.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_guidance_args) of the caller ("stale binding" otherwise) */
+  int32_t reserved;
+  const float* cond; int64_t ld_cond;
+  const float* uncond; int64_t ld_uncond;
+  float* out; int64_t ld_out;
+  int64_t B; int64_t V;
+  float scale; int32_t reserved2;
+  const uint8_t* finished;                    /* [B] or NULL, read only */
+  int32_t* positions;                         /* [B] or NULL, in/out */
+  int64_t advance;
+} kx_guidance_args;
+int kx_guidance_logits(const kx_guidance_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process kernel timing (bench.py's roofline leg; the reference's own ad-hoc equivalents are the
  * wall-clock fences of /root/reference/tests/test_benchmarking.py:68-95,192-196).
  * When enabled, every kernel launch made through this library is bracketed by hipEventRecord on

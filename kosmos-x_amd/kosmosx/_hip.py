@@ -208,6 +208,18 @@ class ShapeArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class GuidanceArgs(C.Structure):
+    """kx_guidance_args; struct_bytes is filled in at construction ("stale binding" check of kx_guidance_logits — like kx_shape_args
+    the struct has no kx_struct_id: the list of ids is pinned, so its size is checked by the call itself)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", i32), ("cond", vp), ("ld_cond", i64), ("uncond", vp), ("ld_uncond", i64),
+                ("out", vp), ("ld_out", i64), ("B", i64), ("V", i64), ("scale", f32), ("reserved2", i32), ("finished", vp),
+                ("positions", vp), ("advance", i64)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -257,6 +269,7 @@ SYMBOLS = {
     "kx_automaton_step": (C.c_int, [C.POINTER(AutomatonArgs), vp]),
     "kx_shape_logits": (C.c_int, [C.POINTER(ShapeArgs), vp]),
     "kx_sample_logits_min_p": (C.c_int, [C.POINTER(SampleArgs), vp, i64, f32, vp]),
+    "kx_guidance_logits": (C.c_int, [C.POINTER(GuidanceArgs), vp]),
     "kx_attention_decode_block": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp]),
     "kx_decoder_decode_step_block": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp,
                                                vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),

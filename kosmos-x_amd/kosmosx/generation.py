@@ -57,7 +57,17 @@ session), adds the per-id biases (-inf = a ban) and subtracts frequency * count 
 operations an outside reference can restate bit for bit.  ``min_p`` is one more threshold inside the sampler, after top-p
 (kx_sample_logits_min_p).  With the four at their defaults: no buffer, no launch, the sampler's old entry points.
 
-Not offered: the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
+Classifier-free guidance (``guidance_scale`` = s with ``negative_prompt_ids`` / ``negative_prompt_lengths`` / ``negative_images``;
+run_generate and generate_loop): every sequence runs as two rows of one 2B-row ragged batch — rows 0..B-1 read the prompt (the
+conditional rows), rows B..2B-1 a negative prompt or a negative image (the unconditional rows) — prefilled through _prefill unchanged
+and stepped by the ragged decode step at 2B rows.  One kx_guidance_logits launch per token, in front of the constraint, automaton and
+shaping launches, writes lu + s * (lc - lu) over the two raw rows' log-softmaxes onto the conditional row — kx_token_logprob's
+arithmetic, then three single fp32 operations an outside reference restates bit for bit — and moves the unconditional positions on;
+the sampler and every row editor see the first B rows; one device-to-device copy feeds the sampled token to both rows.  With the scale
+at 1.0: no buffer, no launch, no further host read, nothing doubled.
+
+Not offered: guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
+image, log-probs of the guided distribution; the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
 turn, typical-p / epsilon / eta sampling; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
 that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
 sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
@@ -79,7 +89,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
                   prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0, token_automaton=None,
-                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
+                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
+                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -120,9 +131,28 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     session's turn starts from zero.  ``min_p`` goes to the sampler launch (kx_sample_logits_min_p), after top-p.  The raw row
     ``output_logits`` and ``output_logprobs`` use is taken before the launch.  With the four at their defaults: no buffer, no
     launch, the sampler's old entry points.
-    Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits``; then with ``output_logprobs`` the fp32
+    ``guidance_scale`` = s other than 1.0 (check_guidance_args): ``logits``, ``prompt_tokens``, ``lengths`` and ``text_lengths`` are the
+    2B rows run_generate prefilled — rows 0..B-1 conditional, rows B..2B-1 unconditional, always a ragged batch; the negatives are
+    already those rows, so ``negative_prompt_ids`` / ``negative_prompt_lengths`` are only checked here.  The step runs at 2B rows
+    (``positions`` int32 [2B], ``nxt`` int64 [2B], _ragged_scratch at 2B); the sampler and every row editor see B rows — the first
+    B of ``positions`` / ``nxt`` and the conditional logits rows, with ``finished``, the histories (the conditional prompts' text ids,
+    then the output), the counts, the automaton states and ``out`` at B rows.  Per token one kx_guidance_logits launch comes first:
+    it reads the two raw rows, writes the guided row over the conditional one and advances the unconditional positions with the
+    sampler's own ``advance``; after the sampler one device-to-device copy nxt[B:] = nxt[:B] feeds the token to both rows.  Row b
+    draws at the conditional row's Philox position with ``sequence_ids[b]``: the stream of the unguided ragged call.  No host read is
+    added: the error word covers all 2B rows and is read where it already is.  ``output_logits`` keeps the conditional rows' raw
+    logits and, returned directly after them, the unconditional rows', both taken before the launch; ``output_logprobs`` reads the
+    conditional rows' raw logits.  ``pad_launches`` (sessions) is refused.  With the scale at 1.0 nothing of this happens.
+    Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits`` (under guidance followed by the fp32
+    [B, n, V] unconditional logits); then with ``output_logprobs`` the fp32
     [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
-    B, T, V = logits.shape
+    R, T, V = logits.shape                                                # R: the rows of the step; B: the rows of the sampler
+    guide = check_guidance_args(R // 2, guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids,
+                                negative_prompt_lengths=negative_prompt_lengths)
+    B = R if guide is None else R // 2
+    if guide is not None and (R % 2 or lengths is None or len(lengths) != R or pad_launches is not None):
+        raise ValueError(f"guidance_scale = {guidance_scale!r} takes the 2B-row ragged batch of run_generate: conditional rows, then "
+                         "unconditional rows, ``lengths`` for all of them, no ``pad_launches``")
     gathered = prompt_rows is not None
     if gathered:
         T = prompt_rows
@@ -136,16 +166,17 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     shaping = shape is not None and shape["launch"]
     min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
-    nxt = torch.empty(B, dtype=torch.int64, device=dev)
+    nxt = torch.empty(R, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
     history = None
+    prompt_tokens = prompt_tokens[:B]                                     # (guidance: the histories see the conditional prompts)
     Tt = prompt_tokens.shape[1]
     if float(repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"]):
         history = torch.empty((B, Tt + max_new_tokens), dtype=torch.int64, device=dev)           # (the sampler appends with r == 1 too)
         history[:, :Tt] = prompt_tokens
     if sequence_ids is not None:
         sequence_ids = sequence_ids.to(device=dev, dtype=torch.int64).contiguous()
-    kept = []
+    kept, kept_u = [], []
     k = int(top_logprobs)
     lp = top_lp = top_ids = snap = None
     if output_logprobs:                                                   # every buffer before the first step
@@ -163,10 +194,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         # history slots already hold the row's own first prompt token (mask_padding): the penalty is applied once per distinct
         # id, so the duplicates change nothing and every row keeps the common hist_len.
         last = torch.tensor([l - 1 for l in lengths], dtype=torch.int64, device=dev)
-        row = logits[:, 0] if gathered else logits[torch.arange(B, device=dev), last]   # [B, V]
+        row = logits[:, 0] if gathered else logits[torch.arange(R, device=dev), last]   # [R, V]
         positions = torch.tensor(lengths, dtype=torch.int32, device=dev)
         state.update(positions=positions, pos_max=max(lengths))
-        decoder._ragged_scratch(state, dev, rows=B)                       # (before the first sampler launch: no fill between steps)
+        decoder._ragged_scratch(state, dev, rows=R)                       # (before the first sampler launch: no fill between steps)
         err = state["error"]                                              # the step kernels' sticky error word
     else:
         row = logits[:, -1]                                               # [B, V] view, row stride T * V
@@ -174,7 +205,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         bad, stop = (ops.SequenceTable(cons[k], dev) if cons[k] else None for k in ("bad", "stop"))
         plens = None
         if lengths is not None:
-            plens = torch.tensor(lengths if text_lengths is None else text_lengths, dtype=torch.int32, device=dev)
+            plens = torch.tensor((lengths if text_lengths is None else text_lengths)[:B], dtype=torch.int32, device=dev)
     if auto is not None:                                                  # the one upload: the automaton's tables and the start states
         table = ops.AutomatonTable(*token_automaton.tables(), dev)
         states = (torch.tensor(auto, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
@@ -183,34 +214,45 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         bias = ops.BiasTable(shape["bias"], dev) if shape["bias"] is not None else None
         penalised = shape["frequency"] != 0.0 or shape["presence"] != 0.0
         counts = torch.zeros((B, V), dtype=torch.int32, device=dev) if penalised else None
+    # what the sampler and every row editor see: all R rows, or under guidance the first B of them (views, taken once)
+    spos, snxt = (positions, nxt) if guide is None else (positions[:B], nxt[:B])
     n = 0
     for g in range(max_new_tokens):
         constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
+        step_rows = row
+        if guide is not None:
+            row = step_rows[:B]                                           # the conditional rows; step_rows[B:] are the unconditional ones
         raw = row
         if output_logits:
             kept.append(row.clone())                                      # the model's own logits: before any ban (the sampler only reads the row)
             raw = kept[-1]
-        elif output_logprobs and (constrained or auto is not None or shaping):
-            raw = row.clone()                                             # (the constraint, automaton and shaping launches edit the row in place)
+            if guide is not None:
+                kept_u.append(step_rows[B:].clone())
+        elif output_logprobs and (constrained or auto is not None or shaping or guide is not None):
+            raw = row.clone()                                             # (the guidance, constraint, automaton and shaping launches edit the row in place)
+        if guide is not None:                                             # the guided row over the conditional one; the unconditional positions move on
+            ops.guidance_logits(row, step_rows[B:], scale=guide["scale"], finished=finished, positions=positions[B:], advance=int(g > 0))
         if constrained:
             ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
                                  no_repeat_ngram_size=cons["ngram"], bad_words=bad, stop_sequences=stop,
                                  min_new_tokens=cons["min_new"], eos_token_id=eos_token_id, finished=finished)
         if auto is not None:
-            ops.automaton_step(row, table, states[g & 1], states[1 - (g & 1)], last_token=nxt if g else None, finished=finished)
+            ops.automaton_step(row, table, states[g & 1], states[1 - (g & 1)], last_token=snxt if g else None, finished=finished)
         if shaping:
             ops.shape_logits(row, bias=bias, counts=counts, frequency_penalty=shape["frequency"], presence_penalty=shape["presence"],
-                             last_token=nxt if g else None, finished=finished)
+                             last_token=snxt if g else None, finished=finished)
         if pad_launches is not None:
             pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
         if snap is not None:
             snap.copy_(finished)
         if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                              do_sample=do_sample, seed=seed, positions=positions, advance=int(g > 0), sequence_ids=sequence_ids,
+                              do_sample=do_sample, seed=seed, positions=spos, advance=int(g > 0), sequence_ids=sequence_ids,
                               history=history, hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, out=nxt, out_tokens=out, out_col=g, **min_p)
+                              pad_token_id=pad_token_id, out=snxt, out_tokens=out, out_col=g, **min_p)
+            if guide is not None:
+                nxt[B:].copy_(snxt)                                       # both rows of a pair are fed the token just sampled
         else:
             ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                               do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
@@ -218,13 +260,13 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                               out=nxt, out_tokens=out, out_col=g, **min_p)
         if auto is not None and snap is not None:
             # a row this launch finished on a token other than the EOS had no candidate: what it emitted is a pad, no token of the row
-            dead = (finished - snap) * (nxt != not_eos)
+            dead = (finished - snap) * (snxt != not_eos)
             if pad_launches is not None:
                 pad_launches.add_(dead)
             if output_logprobs:
                 snap.add_(dead)                                           # (its log-prob slots stay 0.0 / -1)
         if output_logprobs:
-            ops.step_logprobs(raw, nxt, out=lp, col=g, skip=snap, top_n=k, top_out=top_lp, top_ids=top_ids)
+            ops.step_logprobs(raw, snxt, out=lp, col=g, skip=snap, top_n=k, top_out=top_lp, top_ids=top_ids)
         n = g + 1
         if n == max_new_tokens:
             break
@@ -252,6 +294,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     res = [out[:, :n]]
     if output_logits:
         res.append(torch.stack(kept, dim=1))
+        if guide is not None:
+            res.append(torch.stack(kept_u, dim=1))                        # the unconditional rows' raw logits, directly after
     if output_logprobs:
         res.append(lp[:, :n])
         if k > 0:
@@ -426,6 +470,93 @@ def check_shape_args(vocab: int, batch: int, *, logit_bias=None, presence_penalt
                          f"{prompt_lookup_num_tokens}): a verify step emits a varying number of tokens per row; see DESIGN.md §8")
     out["launch"] = names != ["min_p"]
     return out
+
+
+def check_guidance_args(batch: int, *, guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None,
+                        min_len: int = 1, multimodal: bool = False, num_beams=1, prompt_lookup_num_tokens=0, num_return_sequences=1,
+                        return_session=False):
+    """ValueError (naming ``guidance_scale``, ``negative_prompt_ids``, ``negative_prompt_lengths`` or ``negative_images``) for what
+    generate() refuses of the guidance arguments; host only, before the device check and any launch.  ``batch``: the sequences B
+    (the step then runs 2B rows); ``min_len``: the model's shortest prompt; ``multimodal``: Kosmos, which takes ``negative_images``
+    and needs at least one negative.  Returns None with the scale at 1.0 (no launch, no buffer, nothing doubled), else a dict:
+    ``scale`` (float) and ``lengths`` (the negative prompts' host lengths where they could be checked without a device read, else
+    None: an integer tensor is resolved after the device check, as ``prompt_lengths`` is)."""
+    s = guidance_scale
+    if isinstance(s, bool) or not isinstance(s, (int, float)) or not abs(s) <= 3.4028234663852886e38:
+        raise ValueError(f"guidance_scale must be a finite number (in fp32; 1.0 = off), got {s!r}")
+    given = [n for n, v in (("negative_prompt_ids", negative_prompt_ids), ("negative_prompt_lengths", negative_prompt_lengths),
+                            ("negative_images", negative_images)) if v is not None]
+    if float(s) == 1.0:
+        if given:
+            raise ValueError(f"{', '.join(given)}: given without a guidance_scale other than 1.0 (1.0 turns guidance off)")
+        return None
+    for name, on in ((f"num_beams = {num_beams}", num_beams not in (1, None)),
+                     (f"prompt-lookup speculation (prompt_lookup_num_tokens = {prompt_lookup_num_tokens})",
+                      prompt_lookup_num_tokens not in (0, None)),
+                     (f"num_return_sequences = {num_return_sequences}", num_return_sequences not in (1, None)),
+                     ("return_session", bool(return_session))):
+        if on:
+            raise ValueError(f"guidance_scale = {s!r}: guidance is not offered together with {name}: every sequence runs as a "
+                             "conditional and an unconditional row of one ragged batch; see DESIGN.md §8")
+    if negative_images is not None:
+        if not multimodal:
+            raise ValueError("negative_images: this model takes no images")
+        if not isinstance(negative_images, torch.Tensor) or not negative_images.is_floating_point() or negative_images.dim() != 4 \
+                or negative_images.shape[0] != batch:
+            raise ValueError(f"negative_images must be a floating-point [{batch}, 3, H, W] tensor like images, got "
+                             f"{tuple(negative_images.shape) if isinstance(negative_images, torch.Tensor) else type(negative_images).__name__}")
+    if negative_prompt_ids is None and negative_prompt_lengths is not None:
+        raise ValueError("negative_prompt_lengths: given without negative_prompt_ids")
+    if multimodal and negative_prompt_ids is None and negative_images is None:
+        raise ValueError(f"guidance_scale = {s!r} needs negative_prompt_ids or negative_images (or both): without either the "
+                         "unconditional rows would repeat the conditional ones")
+    lengths = None
+    if negative_prompt_ids is not None:
+        t = negative_prompt_ids
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("negative_prompt_ids must be an integer tensor [batch, seq], got "
+                             f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dim() != 2 or t.shape[0] != batch:
+            raise ValueError(f"negative_prompt_ids must be [batch, seq] with batch {batch} (one negative prompt per row), got {tuple(t.shape)}")
+        if t.shape[1] < min_len:
+            raise ValueError(f"negative_prompt_ids holds {t.shape[1]} token{'s' if t.shape[1] != 1 else ''} per row: a negative prompt "
+                             f"has at least {min_len}" + (" (the image is spliced after two text tokens)" if min_len == 2 else ""))
+        if isinstance(negative_prompt_lengths, torch.Tensor):
+            p = negative_prompt_lengths
+            if p.is_floating_point() or p.is_complex() or p.dtype == torch.bool:
+                raise ValueError(f"negative_prompt_lengths must hold integers, got a {p.dtype} tensor")
+            if tuple(p.shape) != (batch,):
+                raise ValueError(f"negative_prompt_lengths must have {batch} entries, got shape {tuple(p.shape)}")
+        elif negative_prompt_lengths is not None:
+            lengths = resolve_prompt_lengths(negative_prompt_lengths, batch, t.shape[1], min_len=min_len, name="negative_prompt_lengths")
+    return dict(scale=float(s), lengths=lengths)
+
+
+def _guided_prompt(prompt: dict, prompt_lengths, guide: dict, *, negative_prompt_ids=None, negative_prompt_lengths=None):
+    """The 2B-row prompt of a guided call: rows 0..B-1 are ``prompt``'s own (the conditional rows), rows B..2B-1 the unconditional
+    ones — ``negative_prompt_ids``, or by default what prompt["negative_default"] names: the row's last prompt token ("last_token",
+    the text model, as `transformers` does) or the row's own text ("own_text", the multimodal model under ``negative_images``) —
+    right-padded to the wider of the two.  Returns the prompt dict with these tokens and the 2B host lengths, which _prefill takes
+    as a ragged batch.  Runs after the device check; no host read unless a length was given as a device tensor."""
+    tokens = prompt["tokens"].long()
+    B, Tt = tokens.shape
+    lens = [Tt] * B if prompt_lengths is None else resolve_prompt_lengths(prompt_lengths, B, Tt, min_len=prompt["min_len"])
+    if negative_prompt_ids is not None:
+        neg = negative_prompt_ids.long()
+        nlens = guide["lengths"]
+        if nlens is None:
+            nlens = [neg.shape[1]] * B if negative_prompt_lengths is None else resolve_prompt_lengths(
+                negative_prompt_lengths, B, neg.shape[1], min_len=prompt["min_len"], name="negative_prompt_lengths")
+    elif prompt["negative_default"] == "last_token":
+        neg = tokens.gather(1, torch.tensor([[l - 1] for l in lens], dtype=torch.int64, device=tokens.device))
+        nlens = [1] * B
+    else:
+        neg, nlens = tokens, lens
+    W = max(max(lens), max(nlens))
+    both = torch.zeros((2 * B, W), dtype=torch.int64, device=tokens.device)     # (mask_padding replaces what lies behind a row's length)
+    both[:B, :min(Tt, W)] = tokens[:, :W]
+    both[B:, :min(neg.shape[1], W)] = neg[:, :W]
+    return dict(prompt, tokens=both), lens + nlens
 
 
 def check_beam_args(vocab: int, *, num_beams, length_penalty=1.0, num_return_sequences=1, do_sample=False, temperature=1.0,
@@ -923,6 +1054,10 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
     automaton = ("token_automaton", "automaton_start")
     shaping = ("logit_bias", "presence_penalty", "frequency_penalty", "min_p")
+    negatives = ("negative_prompt_ids", "negative_prompt_lengths")
+    guide = check_guidance_args(tokens.shape[0] if tokens.dim() else 0, min_len=prompt["min_len"], multimodal="negative_images" in kw,
+                                negative_images=kw.get("negative_images"), **pick(
+        "guidance_scale", *negatives, "num_beams", "prompt_lookup_num_tokens", "num_return_sequences", "return_session"))
     beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
         "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
         "output_scores", "output_trace"))
@@ -937,8 +1072,18 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
                                                                               "prompt_lookup_num_tokens"))
-    prompt["check"]()
+    prompt["check"](**({} if guide is None or kw["negative_prompt_ids"] is None else pick("negative_prompt_ids")))
     with torch.no_grad():
+        if guide is not None:
+            # every sequence as two rows of one ragged batch: the prompt (rows 0..B-1) and its negative (rows B..2B-1), prefilled
+            # through _prefill unchanged; generate_loop gives the sampler the first B rows and feeds both halves the same token
+            prompt, lengths2 = _guided_prompt(prompt, kw["prompt_lengths"], guide, **pick(*negatives))
+            tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, lengths2, max_new_tokens, chunk=chunk)
+            return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, pos_shift=prompt["pos_shift"],
+                                 prompt_rows=prompt_rows, lengths=[prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
+                                 guidance_scale=guide["scale"], **pick(
+                                     "eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits",
+                                     "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
         tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts,
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
@@ -999,28 +1144,28 @@ def _raise_position_error(word: int, state: dict):
                          f"{state.get('pos_max')}, cache of {state.get('max_len')} rows); that row's step wrote nothing")
 
 
-def resolve_prompt_lengths(prompt_lengths, B: int, width: int, min_len: int = 1) -> list:
+def resolve_prompt_lengths(prompt_lengths, B: int, width: int, min_len: int = 1, name: str = "prompt_lengths") -> list:
     """``prompt_lengths`` (a sequence of B ints or an integer tensor) -> a host list of B ints in [min_len, width], or
-    ValueError.  Host data is taken as it is; a device tensor is read back once."""
+    ValueError naming ``name``.  Host data is taken as it is; a device tensor is read back once."""
     if isinstance(prompt_lengths, torch.Tensor):
         if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
-            raise ValueError(f"prompt_lengths must hold integers, got a {prompt_lengths.dtype} tensor")
+            raise ValueError(f"{name} must hold integers, got a {prompt_lengths.dtype} tensor")
         if prompt_lengths.dim() != 1:
-            raise ValueError(f"prompt_lengths must have {B} entries, got shape {tuple(prompt_lengths.shape)}")
+            raise ValueError(f"{name} must have {B} entries, got shape {tuple(prompt_lengths.shape)}")
         lens = prompt_lengths.tolist()                     # (the one read of a device tensor)
     else:
         try:
             lens = [operator.index(l) for l in prompt_lengths]
         except TypeError:
-            raise ValueError(f"prompt_lengths must be a sequence of {B} integers or an integer tensor, got {prompt_lengths!r}") from None
+            raise ValueError(f"{name} must be a sequence of {B} integers or an integer tensor, got {prompt_lengths!r}") from None
     if len(lens) != B:
-        raise ValueError(f"prompt_lengths must have {B} entries (one per row), got {len(lens)}")
+        raise ValueError(f"{name} must have {B} entries (one per row), got {len(lens)}")
     for b, l in enumerate(lens):
         if l < min_len:
-            raise ValueError(f"prompt_lengths[{b}] = {l}: a prompt has at least {min_len} token" + ("s" if min_len > 1 else "")
+            raise ValueError(f"{name}[{b}] = {l}: a prompt has at least {min_len} token" + ("s" if min_len > 1 else "")
                              + (" (the image is spliced after two text tokens)" if min_len == 2 else ""))
         if l > width:
-            raise ValueError(f"prompt_lengths[{b}] = {l} exceeds the padded width {width}")
+            raise ValueError(f"{name}[{b}] = {l} exceeds the padded width {width}")
     return lens
 
 

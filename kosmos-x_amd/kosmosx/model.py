@@ -1334,7 +1334,8 @@ class Kosmos(nn.Module):
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
                  prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
-                 token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
+                 token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
+                 guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1424,11 +1425,30 @@ class Kosmos(nn.Module):
         ``output_logprobs`` keep returning the model's own distribution.  They compose with sampling, ``prompt_lengths``,
         ``num_return_sequences`` (prompt b's biases go to its n samples, each with its own counts), the constraints, automata,
         ``prefill_chunk``, log-probs and sessions; with ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0, or with a bad value:
-        ValueError naming the argument.  With the four at their defaults nothing is added."""
+        ValueError naming the argument.  With the four at their defaults nothing is added.
+        ``guidance_scale`` = s with ``negative_prompt_ids`` / ``negative_prompt_lengths`` / ``negative_images``: classifier-free
+        guidance against a second prompt, on the device (`transformers`' guidance_scale / negative_prompt_ids).  Every sequence
+        runs as two rows of one 2B-row ragged batch — row b the prompt, row B + b the negative text ([B, Tn] integer ids, at least
+        two per row, ragged through ``negative_prompt_lengths``; default: the row's own text) spliced with the negative images
+        (default: the row's own; the tower and resampler then run once) — and both are fed the token the pair sampled.  One
+        kx_guidance_logits launch per token writes lu + s * (lc - lu) over the two raw rows' log-softmaxes lc and lu onto the
+        conditional row (kx_token_logprob's arithmetic, then a subtract, a multiply and an add in fp32; a result that is not finite
+        becomes -inf), in front of the constraint, automaton and shaping launches and the sampler, which therefore see the guided
+        row.  s is any finite float; 1.0 (the default) turns guidance off: no launch, no buffer, nothing doubled.  At least one of
+        ``negative_prompt_ids`` / ``negative_images`` is needed, and a negative argument without a scale other than 1 is refused.
+        A seeded draw addresses the stream of the unguided ragged call: the conditional row's position and ``sequence_ids[b]``.  The
+        repetition penalty and the constraints read the conditional prompt's ids and the output.  ``output_logits`` returns the
+        conditional rows' raw logits where it always did and, directly after, the unconditional rows' raw logits fp32
+        [B, n_new, vocab]; ``output_logprobs`` / ``top_logprobs`` keep meaning the model's own distribution on the conditional row.
+        It composes with sampling and all filters, ``prompt_lengths``, ``eos_token_id``, the constraints, automata, the shaping
+        keywords, log-probs and ``prefill_chunk``; with ``num_beams`` > 1, ``prompt_lookup_num_tokens`` > 0,
+        ``num_return_sequences`` > 1 or ``return_session``: ValueError naming ``guidance_scale``."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
-        return generation.run_generate(self, self._prompt(text_tokens, images), max_new_tokens, dict(
+        return generation.run_generate(self, self._prompt(text_tokens, images, negative_images), max_new_tokens, dict(
+            guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids, negative_prompt_lengths=negative_prompt_lengths,
+            negative_images=negative_images,
             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
             eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
             output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
@@ -1463,24 +1483,34 @@ class Kosmos(nn.Module):
             continuation_lengths=continuation_lengths, prompt_index=prompt_index, prompt_lengths=prompt_lengths,
             output_logits=output_logits, prefill_chunk=prefill_chunk))
 
-    def _prompt(self, text_tokens, images) -> dict:
-        """The multimodal prompt as generation.run_generate / run_score take it: tower -> resampler -> splice, as in forward()."""
+    def _prompt(self, text_tokens, images, negative_images=None) -> dict:
+        """The multimodal prompt as generation.run_generate / run_score take it: tower -> resampler -> splice, as in forward().
+        Under guidance run_generate passes 2B rows of tokens: rows B.. are the unconditional ones and get ``negative_images``
+        (the tower and resampler then run at 2B rows) or, without them, the B rows' own resampled images again."""
         n_img = self.cfg.perceiver.latents
 
         def check(**more):
             _warn_train_mode(self)
+            if negative_images is not None:
+                more = dict(more, negative_images=negative_images)
             for name, t in dict(text_tokens=text_tokens, images=images, **more).items():
                 _require_cuda(t, name)
             if text_tokens.dim() != 2 or text_tokens.shape[0] != images.shape[0]:
                 raise ValueError(f"text_tokens must be [batch, seq] with batch {images.shape[0]}, got {tuple(text_tokens.shape)}")
+            if negative_images is not None and negative_images.shape != images.shape:
+                raise ValueError(f"negative_images must have the shape of images {tuple(images.shape)}, got {tuple(negative_images.shape)}")
 
         def passed_x(tokens):
-            img = self.clip_model.run(images, self.precision, self._ws)
+            guided = tokens.shape[0] == 2 * images.shape[0]
+            pix = torch.cat([images, negative_images.to(images.dtype)]) if guided and negative_images is not None else images
+            img = self.clip_model.run(pix, self.precision, self._ws)
             img, _ = self.perceive.run(img, self.precision, self._ws, self.image_proj.weight)
+            if guided and negative_images is None:
+                img = torch.cat([img, img])                                 # the unconditional rows splice the row's own image
             return self.decoder.embed(tokens, self.precision, img=img)      # the prompt's ids are range-checked here, once
 
         return dict(tokens=text_tokens, check=check, passed_x=passed_x, min_len=2, prefix_rows=n_img,   # (the image is spliced after two tokens)
-                    pos_shift=n_img if self.switches.u1_inplace_alias else 0)
+                    pos_shift=n_img if self.switches.u1_inplace_alias else 0, negative_default="own_text")
 
     def _forward_graphed(self, text_tokens, images):
         """Replay the ~420 kernel launches of one forward as a single hipGraph (the library never allocates or
@@ -1604,7 +1634,8 @@ class KosmosLanguage(nn.Module):
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, prompt_lookup_num_tokens=0,
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
                  session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
-                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
+                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, guidance_scale=1.0,
+                 negative_prompt_ids=None, negative_prompt_lengths=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1615,11 +1646,15 @@ class KosmosLanguage(nn.Module):
         further turns on the kept KV cache, as there; ``output_logprobs`` and ``top_logprobs``: every generated token's log-prob
         and the most likely alternatives, as there; ``token_automaton`` and ``automaton_start``: the output follows a token-level
         automaton whose state lives on the device, as there; ``logit_bias``, ``presence_penalty``, ``frequency_penalty`` and
-        ``min_p``: the completion-API request fields, applied on the device, as there)."""
+        ``min_p``: the completion-API request fields, applied on the device, as there; ``guidance_scale``,
+        ``negative_prompt_ids`` and ``negative_prompt_lengths``: classifier-free guidance against a negative prompt, as there —
+        a negative prompt has at least one token, and with ``negative_prompt_ids`` None row b's unconditional context is its last
+        prompt token, as in `transformers`)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
         return generation.run_generate(self, self._prompt(x), max_new_tokens, dict(
+            guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids, negative_prompt_lengths=negative_prompt_lengths,
             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
             eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
             output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
@@ -1663,7 +1698,8 @@ class KosmosLanguage(nn.Module):
             if x.dim() != 2:
                 raise ValueError(f"x must be [batch, seq], got {tuple(x.shape)}")
 
-        return dict(tokens=x, check=check, passed_x=lambda tokens: None, min_len=1, prefix_rows=0, pos_shift=0)
+        return dict(tokens=x, check=check, passed_x=lambda tokens: None, min_len=1, prefix_rows=0, pos_shift=0,
+                    negative_default="last_token")
 
 
 class KosmosTokenizer:

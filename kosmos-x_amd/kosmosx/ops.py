@@ -697,6 +697,40 @@ def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, prese
     H.check(H.load().kx_shape_logits(C.byref(a), _stream()), "kx_shape_logits")
 
 
+def guidance_logits(cond, uncond, *, scale, out=None, finished=None, positions=None, advance=0):
+    """Classifier-free guidance on B pairs of raw fp32 rows `cond` / `uncond` [B, V] (unit column stride, any row stride >= V) by one
+    launch, in front of ops.constrain_logits / ops.automaton_step / ops.shape_logits and ops.sample_logits (kx_guidance_logits in
+    include/kosmosx_hip.h): out = lu + scale * (lc - lu) over the rows' log-softmaxes lc and lu — kx_token_logprob's arithmetic,
+    then a subtract, a multiply and an add in fp32; a result that is not finite becomes -inf.
+
+    ``out`` fp32 [B, V]: None or ``cond`` itself writes the guided rows over the conditional ones (in place); it never overlaps
+    ``uncond``.  finished uint8 [B] (read only): finished pairs are neither read nor written.  positions int32 [B] (in/out) with
+    ``advance`` 0 or 1: the unconditional rows' device positions, moved on by ``advance`` for every pair, finished ones included —
+    what the ragged sampler launch does for the conditional rows.  Returns ``out``."""
+    if out is None:
+        out = cond
+    _need_cuda(cond, uncond, out, finished, positions)
+    for name, t in (("cond", cond), ("uncond", uncond), ("out", out)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+            raise TypeError(f"guidance_logits: {name} must be fp32 [B, V] with unit column stride")
+    B, V = cond.shape
+    for name, t in (("uncond", uncond), ("out", out)):
+        if tuple(t.shape) != (B, V):
+            raise ValueError(f"guidance_logits: {name} must have shape [{B}, {V}], got {tuple(t.shape)}")
+    for name, t, dt in (("finished", finished, torch.uint8), ("positions", positions, torch.int32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f"guidance_logits: {name} must be a contiguous {dt} tensor")
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"guidance_logits: {name} must have shape [{B}]")
+    a = H.GuidanceArgs()
+    ld = [t.stride(0) if B > 1 else max(t.stride(0), V) for t in (cond, uncond, out)]
+    a.cond, a.ld_cond, a.uncond, a.ld_uncond, a.out, a.ld_out = cond.data_ptr(), ld[0], uncond.data_ptr(), ld[1], out.data_ptr(), ld[2]
+    a.B, a.V, a.scale = B, V, float(scale)
+    a.finished, a.positions, a.advance = H.ptr(finished), H.ptr(positions), int(advance)
+    H.check(H.load().kx_guidance_logits(C.byref(a), _stream()), "kx_guidance_logits")
+    return out
+
+
 def embed_step(tokens, embed, pos, pos_a, pos_b=-1):
     """Kernel-level wrapper (the model calls the library directly; this is what the kernel tests and tools drive).
     kx_embed_step: [B, d] fp32 rows embed[tokens[b]] + pos[2 + pos_a] (+ pos[2 + pos_b]) for int64 ``tokens`` [B] on the device."""
