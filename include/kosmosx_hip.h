@@ -1309,6 +1309,58 @@ int kx_shape_logits(const kx_shape_args* args, void* stream);
 int kx_sample_logits_min_p(const kx_sample_args* args, int32_t* positions, int64_t advance, float min_p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Truncation sampling: typical-p, epsilon and eta (added within ABI 7: one struct and one function are appended; no existing
+ * layout moves and the kx_struct_id list is unchanged — kx_truncate_args carries its own struct_bytes, which
+ * kx_sample_logits_truncate checks, as kx_shape_args does; kx_sample_args is untouched — so kx_version() stays 7).
+ *
+ * kx_sample_logits_truncate: kx_sample_logits_min_p (positions == NULL: the uniform form, advance unused; positions != NULL: the
+ * ragged form) with up to three more filters behind min-p, the `transformers` warper order — temperature -> top-k -> top-p ->
+ * min-p -> typical-p -> epsilon -> eta.  Each stage takes its probabilities renormalised over what the stage before it kept.
+ * With typical_p == 1, epsilon_cutoff == 0 and eta_cutoff == 0 it IS kx_sample_logits_min_p(args, positions, advance, min_p):
+ * the same launches.  Otherwise one launch of one more instantiation of the sampler's kernel, min-p inside it.
+ *
+ * Notation: x_i = the sampler's penalised logit / T (its rules 1-2), m = the row maximum, w_i = exp(x_i - m) in 2^-40 fixed
+ * point, truncated (x_i == m gives exactly 2^40, also when both are +inf) — the mass top-p already sums; S0 = the set the
+ * sampler's rules 1-4 and min-p keep.  Three properties hold for everything below:
+ *   (a) every sum is a 64-bit INTEGER sum (V <= 2^23 elements of at most 2^40 keep it below 2^63);
+ *   (b) every per-element quantity is a stated sequence of single IEEE operations;
+ *   (c) no result depends on the order in which lanes, waves or LDS atomics run: a row's outputs do not depend on B or on its
+ *       row index, and two calls give identical bits.
+ * Over a set S: Z(S) = sum of w_i; E(S) = sum of e_i with e_i = (uint64)((double)w_i * (double)(m - x_i)), m - x_i one fp32
+ * subtraction, and e_i = 0 where x_i == m or w_i == 0 (the +inf ties; w (m - x) <= 2^40 / e per element);
+ * mu(S) = (float)((double)E / (double)Z): the expected surprise minus (lse - m).
+ *
+ * typical_p = t in (0, 1], 1 = off.  With mu = mu(S0): d_i = fabsf(s_i - mu), s_i = m - x_i (0 where x_i == m) — two fp32
+ * operations and an absolute value; the lse cancels out of |-log p_i - H|, no logarithm is taken.  i in S0 stays iff the mass of
+ * {j in S0 : d_j < d_i} (STRICTLY smaller) is < ceil((double)t * Z(S0)) — the integer form top-p uses, found by the same radix
+ * select over the order-preserving key of d, ascending.  Ties in d stay or go together.  This is TypicalLogitsWarper: it always
+ * keeps the tokens of least d — not necessarily the arg max.  S1 = what stays.
+ * epsilon_cutoff = e in [0, 1), 0 = off.  i in S1 stays iff w_i >= ceil((double)e * Z(S1)), or x_i is the maximum of S1
+ * (min_tokens_to_keep = 1; exact ties at that maximum all stay).  S2 = what stays.
+ * eta_cutoff = e in [0, 1), 0 = off.  With H2 = log(Z(S2) 2^-40) + mu(S2), the entropy of S2's distribution, the cut-off is
+ * min(e, sqrt(e) exp(-H2)); it is applied as the integer compare w_i >= ceil(c), c = min((double)e * Z(S2),
+ * sqrt((double)e) * exp(-(double)mu(S2)) * 2^40) computed once per row in double by one thread, or x_i is the maximum of S2
+ * (which is the maximum of S1).
+ * A stage whose Z is 0 keeps what it was given.  (S0 always holds the arg max, and a stage never drops all mass it was handed, so
+ * this is a guard and not a reachable state; the nearest reachable row — everything but the maximum underflows 2^-40 relative to
+ * m — is handled by the rules as written: e_i = 0 there, mu = 0, and the maximum alone has d = 0.)
+ * The Gumbel draw runs over the conjunction of all stage predicates; keep_mask / kept_count report that final set.  Under greedy
+ * all three are ignored, as top-k and min-p are.  Finished rows and rows without a candidate behave as in kx_sample_logits.
+ * Passes over the row (it stays in L2): typical-p 1 + 3, epsilon 1, eta 1; no LDS beyond the sampler's own.
+ * Argument errors (KX_ERR_INVALID_ARG, nothing launched, the message names the argument): a null trunc, a stale struct_bytes,
+ * min_p outside [0, 1], typical_p outside (0, 1], epsilon_cutoff or eta_cutoff outside [0, 1) (NaN included), a negative
+ * advance; then kx_sample_logits' own.  Never allocates, never synchronises. */
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_truncate_args) of the caller ("stale binding" otherwise) */
+  float min_p;                                /* [0, 1], 0 = off: kx_sample_logits_min_p's argument */
+  float typical_p;                            /* (0, 1], 1 = off */
+  float epsilon_cutoff;                       /* [0, 1), 0 = off */
+  float eta_cutoff;                           /* [0, 1), 0 = off */
+  int32_t reserved;
+} kx_truncate_args;
+int kx_sample_logits_truncate(const kx_sample_args* args, int32_t* positions, int64_t advance, const kx_truncate_args* trunc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Classifier-free guidance (added within ABI 7: one struct and one function are appended; no existing layout moves and the
  * kx_struct_id list is unchanged — kx_guidance_args carries its own struct_bytes, which kx_guidance_logits checks, as
  * kx_shape_args does — so kx_version() stays 7).

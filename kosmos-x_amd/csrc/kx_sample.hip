@@ -8,6 +8,9 @@
 //   * the k-th largest value and the top-p threshold are found by radix select on that key (11 + 11 + 10 bits) over a
 //     2048-bin LDS histogram of 64-bit INTEGER sums: element counts for top-k, exp(x_i - max) in 2^-40 fixed point for top-p
 //     (integer adds commute, so the LDS atomics may land in any order);
+//   * typical-p / epsilon / eta (kx_sample_logits_truncate) add 64-bit integer sums of the same masses and of
+//     (uint64)((double)w_i * (double)(m - x_i)), one mean per row taken from two such sums, and one more radix select, over the key
+//     of |(m - x_i) - mean| ascending;
 //   * the draw is a Gumbel arg max with Philox4x32-10 addressed by (seed, sequence id, position, element index).
 // Every loop has a trip count fixed by V, the histogram size or the wave width; there is no waiting on other threads
 // beyond __syncthreads().
@@ -42,16 +45,33 @@ __device__ __forceinline__ float load_x(const SampleParams& a, const float* __re
   return l;
 }
 
-// The largest key K (among candidates with key >= limit) whose weight at or above it reaches `target`:
-//   MASS = false: weight = element count  -> K = the target-th largest value;
-//   MASS = true : weight = mass_fix       -> K = the smallest value whose strictly-greater mass is still below target.
+// What radix_select orders the row by: KEY(x, key) says whether x takes part and gives its 32-bit key (larger = selected first).
+//   XKey: the value itself, among the candidates with key(x) >= limit (top-k, top-p);
+//   DistKey: typical-p — among the same candidates, the distance d = |(m - x) - mu| ASCENDING: the key is ~key(d), two fp32
+//            subtractions and an absolute value (x == m gives m - x = 0, also when both are +inf).
+struct XKey {
+  unsigned limit;
+  __device__ __forceinline__ bool operator()(float x, unsigned& key) const { key = f2key(x); return key >= limit; }
+};
+__device__ __forceinline__ unsigned dist_key(float x, float m, float mu) {
+  const float s = x == m ? 0.f : m - x;
+  return ~f2key(fabsf(s - mu));
+}
+struct DistKey {
+  unsigned limit; float m, mu;
+  __device__ __forceinline__ bool operator()(float x, unsigned& key) const { key = dist_key(x, m, mu); return f2key(x) >= limit; }
+};
+
+// The largest key K (among the elements KEY admits) whose weight at or above it reaches `target`:
+//   MASS = false: weight = element count  -> K = the target-th largest key;
+//   MASS = true : weight = mass_fix       -> K = the smallest key whose strictly-greater mass is still below target.
 // Three histogram passes fix the key's digits from the top; `carry` is the weight strictly above the chosen bin.
 // Returns false (key untouched) when the whole weight stays below target.
 // (OWNER: one instantiation per kernel that calls it, so that each stays a single-caller function the compiler folds into its
 // kernel exactly as it did when there was one kernel)
-template <bool MASS, bool OWNER, bool MINP = false>
+template <bool MASS, typename OWNER, typename KEY>
 __device__ bool radix_select(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, float m,
-                             unsigned limit, unsigned long long target, unsigned long long* hist,
+                             const KEY admit, unsigned long long target, unsigned long long* hist,
                              unsigned long long* gsum, unsigned long long* sel, unsigned& key_out) {
   const int tid = threadIdx.x;
   unsigned prefix = 0, pmask = 0;
@@ -65,8 +85,8 @@ __device__ bool radix_select(const SampleParams& a, const float* __restrict__ ro
 #pragma unroll 4
     for (int i = tid; i < a.V; i += SB) {            // consecutive lanes read consecutive logits
       const float x = load_x(a, row, bitmap, i);
-      const unsigned key = f2key(x);
-      if (key >= limit && (key & pmask) == prefix) {
+      unsigned key;
+      if (admit(x, key) && (key & pmask) == prefix) {
         const unsigned long long inc = MASS ? mass_fix(x, m) : 1ull;
         if (inc) atomicAdd(&hist[(key >> shift) & dmask], inc);
       }
@@ -128,8 +148,46 @@ __device__ bool radix_select(const SampleParams& a, const float* __restrict__ ro
 // kernel-argument layout it always had.
 // MINP (kx_sample_logits_min_p): one more kernel argument behind it (MinP: lm = log(min_p), taken on the host) and one more
 // threshold after top-p, x_i >= x_max + lm.  The empty and the RaggedPos-only pack stay the kernels they always were.
+// TRUNC (kx_sample_logits_truncate): one more kernel argument, last of the pack (Trunc: min-p's lm with its on/off flag, and the
+// three cut-offs as the ABI carries them) and up to three more stages after min-p — typical-p, epsilon, eta — each over what the
+// stage before it kept.  The kept set stays a conjunction of per-element predicates (Kept), so every pass recomputes membership
+// from x alone and nothing per element is stored.
 struct RaggedPos { int* positions; int advance; };
 struct MinP { float lm; };
+struct Trunc { float lm, typical, epsilon, eta; int minp; };
+struct Kept {
+  unsigned tau;                  // rules 1-4 and min-p: key(x) >= tau
+  int typ; float mu; unsigned dkey;        // typical-p (typ != 0): dist_key(x) >= dkey
+  unsigned long long wmin; unsigned ktop;  // epsilon / eta (wmin != 0): mass_fix(x) >= wmin, or key(x) == ktop (the stage's arg max)
+};
+__device__ __forceinline__ bool kept_in(const Kept& s, float x, float m) {
+  const unsigned k = f2key(x);
+  bool in = k >= s.tau;
+  if (s.typ) in = in && dist_key(x, m, s.mu) >= s.dkey;
+  if (s.wmin) in = in && (mass_fix(x, m) >= s.wmin || k == s.ktop);
+  return in;
+}
+// Over the kept set: Z = sum of w_i, E = sum of (uint64)((double)w_i * (double)(m - x_i)) (0 where x_i == m or w_i == 0), both
+// 64-bit integer sums, and the largest key(x).  One pass over the row, three block reductions.
+__device__ __forceinline__ void kept_stats(const SampleParams& a, const float* __restrict__ row, const unsigned* bitmap, float m,
+                                           const Kept& s, unsigned long long* red, unsigned long long& Z, unsigned long long& E,
+                                           unsigned& ktop) {
+  unsigned long long z = 0, e = 0, top = 0;
+#pragma unroll 2
+  for (int i = threadIdx.x; i < a.V; i += SB) {
+    const float x = load_x(a, row, bitmap, i);
+    if (kept_in(s, x, m)) {
+      const unsigned long long w = mass_fix(x, m);
+      z += w;
+      if (w != 0 && x != m) e += (unsigned long long)((double)w * (double)(m - x));
+      const unsigned long long k = f2key(x);
+      top = k > top ? k : top;
+    }
+  }
+  Z = block_sum_u64(z, red);
+  E = block_sum_u64(e, red);
+  ktop = (unsigned)block_max_u64(top, red);
+}
 template <typename A, typename... Rest> __device__ __forceinline__ const A& first_arg(const A& a, const Rest&...) { return a; }
 template <typename A, typename... Rest> __device__ __forceinline__ const auto& last_arg(const A& a, const Rest&... rest) {
   if constexpr (sizeof...(Rest) == 0) return a; else return last_arg(rest...);
@@ -140,6 +198,8 @@ template <typename... R>
 __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const R... r) {
   constexpr bool RAGGED = pack_has<RaggedPos, R...>;    // (first of the pack)
   constexpr bool MINP = pack_has<MinP, R...>;           // (last of the pack)
+  constexpr bool TRUNC = pack_has<Trunc, R...>;         // (last of the pack)
+  using Owner = void(R...);
   __shared__ unsigned long long hist[BINS];
   __shared__ unsigned long long red[SW];
   __shared__ unsigned long long gsum[BINS / 64];
@@ -193,7 +253,7 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
       unsigned tau = KEY_MIN_VALID;
       if (a.k > 0 && a.k < a.V) {
         unsigned kk;
-        if (radix_select<false, RAGGED, MINP>(a, row, bitmap, m, tau, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
+        if (radix_select<false, Owner>(a, row, bitmap, m, XKey{tau}, (unsigned long long)a.k, hist, gsum, sel, kk)) tau = kk;
       }
       if (a.p < 1.0f) {
         unsigned long long z = 0;                     // mass of what top-k kept
@@ -206,11 +266,51 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
         // keep iff (mass strictly above) < p Z; the masses are integers, so "< p Z" is "< ceil(p Z)"
         const unsigned long long target = (unsigned long long)ceil((double)a.p * (double)z);
         unsigned kp;
-        if (radix_select<true, RAGGED, MINP>(a, row, bitmap, m, tau, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
+        if (radix_select<true, Owner>(a, row, bitmap, m, XKey{tau}, target > 0 ? target : 1ull, hist, gsum, sel, kp)) tau = kp;
       }
       if constexpr (MINP) {                             // min-p, after top-p: x_i >= x_max + lm (keys order as the values do)
         const unsigned km = f2key(m + last_arg(r...).lm);
         tau = km > tau ? km : tau;
+      }
+      [[maybe_unused]] Kept s{tau, 0, 0.f, 0u, 0ull, kmax};
+      if constexpr (TRUNC) {
+        const Trunc& t = last_arg(r...);
+        if (t.minp) {                                   // min-p, as above
+          const unsigned km = f2key(m + t.lm);
+          s.tau = km > tau ? km : tau;
+        }
+        unsigned long long Z, E;
+        unsigned top;
+        if (t.typical < 1.0f) {                         // typical-p: the band of least |(m - x) - mu| whose mass reaches typical * Z
+          kept_stats(a, row, bitmap, m, s, red, Z, E, top);
+          if (Z) {                                      // (a stage without mass keeps what it was given)
+            const float mu = (float)((double)E / (double)Z);
+            const unsigned long long target = (unsigned long long)ceil((double)t.typical * (double)Z);
+            unsigned dk;
+            if (radix_select<true, Owner>(a, row, bitmap, m, DistKey{s.tau, m, mu}, target > 0 ? target : 1ull, hist, gsum, sel, dk)) {
+              s.typ = 1; s.mu = mu; s.dkey = dk;
+            }
+          }
+        }
+        if (t.epsilon > 0.f || t.eta > 0.f) {
+          kept_stats(a, row, bitmap, m, s, red, Z, E, top);
+          s.ktop = top;                                 // the arg max of what typical-p left; epsilon keeps it, so it is eta's too
+          if (t.epsilon > 0.f) {                        // epsilon: w_i >= epsilon * Z
+            s.wmin = (unsigned long long)ceil((double)t.epsilon * (double)Z);
+            if (t.eta > 0.f) kept_stats(a, row, bitmap, m, s, red, Z, E, top);
+          }
+          if (t.eta > 0.f && Z) {                       // eta: w_i >= min(eta, sqrt(eta) exp(-H)) * Z, H = log(Z 2^-40) + mu2
+            if (tid == 0) {
+              const float mu2 = (float)((double)E / (double)Z);
+              const double cut = fmin((double)t.eta * (double)Z, sqrt((double)t.eta) * exp(-(double)mu2) * 1099511627776.0);
+              sel[0] = (unsigned long long)ceil(cut);
+            }
+            __syncthreads();
+            const unsigned long long w2 = sel[0];
+            __syncthreads();
+            s.wmin = w2 > s.wmin ? w2 : s.wmin;
+          }
+        }
       }
       // Gumbel arg max over the kept set {key >= tau}; Philox block `base / 4` serves elements base .. base + 3, so here
       // (and only here) a thread owns four consecutive elements
@@ -229,7 +329,8 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
           xs[e] = 0.f;
           if (i < a.V) {
             xs[e] = load_x(a, row, bitmap, i);
-            kp[e] = f2key(xs[e]) >= tau;
+            if constexpr (TRUNC) kp[e] = kept_in(s, xs[e], m);
+            else kp[e] = f2key(xs[e]) >= tau;
             if (mask) mask[i] = kp[e];
           }
           any |= kp[e];
@@ -334,7 +435,8 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const long long* __rest
 
 }  // namespace
 
-static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream, const float* log_min_p = nullptr) {
+static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream, const float* log_min_p = nullptr,
+                       const Trunc* trunc = nullptr) {
   KX_REQUIRE(args != nullptr, "kx_sample_logits: null args");
   KX_REQUIRE(args->struct_bytes == sizeof(kx_sample_args),
              "kx_sample_logits: stale binding — caller declares kx_sample_args as %u bytes, this library (ABI %d) as %zu",
@@ -380,7 +482,11 @@ static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t a
   p.kept_count = args->kept_count; p.keep_mask = args->keep_mask;
   const size_t lds = p.pen ? (size_t)((args->V + 31) / 32) * 4 : 0;
   KxProfScope prof(KX_K_MISC, args->B, args->V, 0, (hipStream_t)stream);
-  if (log_min_p && positions)
+  if (trunc && positions)
+    hipLaunchKernelGGL((sample_kernel<RaggedPos, Trunc>), dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+                       RaggedPos{(int*)positions, (int)advance}, *trunc);
+  else if (trunc) hipLaunchKernelGGL(sample_kernel<Trunc>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p, *trunc);
+  else if (log_min_p && positions)
     hipLaunchKernelGGL((sample_kernel<RaggedPos, MinP>), dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
                        RaggedPos{(int*)positions, (int)advance}, MinP{*log_min_p});
   else if (log_min_p) hipLaunchKernelGGL(sample_kernel<MinP>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p, MinP{*log_min_p});
@@ -407,6 +513,31 @@ extern "C" int kx_sample_logits_min_p(const kx_sample_args* args, int32_t* posit
   if (min_p == 0.0f) return sample_impl(args, positions, positions ? advance : 0, stream);
   const float lm = (float)log((double)min_p);
   return sample_impl(args, positions, positions ? advance : 0, stream, &lm);
+}
+
+// The three cut-offs at their defaults: kx_sample_logits_min_p's launches.  Otherwise one launch of the Trunc instantiation, min-p inside it.
+extern "C" int kx_sample_logits_truncate(const kx_sample_args* args, int32_t* positions, int64_t advance, const kx_truncate_args* trunc,
+                                         void* stream) {
+  KX_REQUIRE(trunc != nullptr, "kx_sample_logits_truncate: null trunc");
+  KX_REQUIRE(trunc->struct_bytes == sizeof(kx_truncate_args),
+             "kx_sample_logits_truncate: stale binding — caller declares kx_truncate_args as %u bytes, this library (ABI %d) as %zu",
+             (unsigned)trunc->struct_bytes, KX_ABI_VERSION, sizeof(kx_truncate_args));
+  KX_REQUIRE(trunc->min_p >= 0.0f && trunc->min_p <= 1.0f, "kx_sample_logits_truncate: min_p=%g must be in [0, 1]", (double)trunc->min_p);
+  KX_REQUIRE(trunc->typical_p > 0.0f && trunc->typical_p <= 1.0f, "kx_sample_logits_truncate: typical_p=%g must be in (0, 1]",
+             (double)trunc->typical_p);
+  KX_REQUIRE(trunc->epsilon_cutoff >= 0.0f && trunc->epsilon_cutoff < 1.0f, "kx_sample_logits_truncate: epsilon_cutoff=%g must be in [0, 1)",
+             (double)trunc->epsilon_cutoff);
+  KX_REQUIRE(trunc->eta_cutoff >= 0.0f && trunc->eta_cutoff < 1.0f, "kx_sample_logits_truncate: eta_cutoff=%g must be in [0, 1)",
+             (double)trunc->eta_cutoff);
+  KX_REQUIRE(positions == nullptr || (advance >= 0 && advance <= 0x7fffffffll), "kx_sample_logits_truncate: advance=%lld must be >= 0",
+             (long long)advance);
+  if (trunc->typical_p == 1.0f && trunc->epsilon_cutoff == 0.0f && trunc->eta_cutoff == 0.0f)
+    return kx_sample_logits_min_p(args, positions, advance, trunc->min_p, stream);
+  Trunc t;
+  t.minp = trunc->min_p != 0.0f;
+  t.lm = t.minp ? (float)log((double)trunc->min_p) : 0.0f;
+  t.typical = trunc->typical_p; t.epsilon = trunc->epsilon_cutoff; t.eta = trunc->eta_cutoff;
+  return sample_impl(args, positions, positions ? advance : 0, stream, nullptr, &t);
 }
 
 // span == 1: kx_step_prepare's launch.  span > 1: B counts the rows, `span` consecutive ones per entry of positions (see the kernel).

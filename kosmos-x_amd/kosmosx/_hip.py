@@ -208,6 +208,17 @@ class ShapeArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class TruncateArgs(C.Structure):
+    """kx_truncate_args; struct_bytes is filled in at construction ("stale binding" check of kx_sample_logits_truncate — like
+    kx_shape_args the struct has no kx_struct_id).  The defaults are the filters switched off."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("min_p", f32), ("typical_p", f32), ("epsilon_cutoff", f32), ("eta_cutoff", f32),
+                ("reserved", i32)]
+
+    def __init__(self, **k):
+        super().__init__(**dict(dict(typical_p=1.0), **k))
+        self.struct_bytes = C.sizeof(type(self))
+
+
 class GuidanceArgs(C.Structure):
     """kx_guidance_args; struct_bytes is filled in at construction ("stale binding" check of kx_guidance_logits — like kx_shape_args
     the struct has no kx_struct_id: the list of ids is pinned, so its size is checked by the call itself)."""
@@ -269,6 +280,7 @@ SYMBOLS = {
     "kx_automaton_step": (C.c_int, [C.POINTER(AutomatonArgs), vp]),
     "kx_shape_logits": (C.c_int, [C.POINTER(ShapeArgs), vp]),
     "kx_sample_logits_min_p": (C.c_int, [C.POINTER(SampleArgs), vp, i64, f32, vp]),
+    "kx_sample_logits_truncate": (C.c_int, [C.POINTER(SampleArgs), vp, i64, C.POINTER(TruncateArgs), vp]),
     "kx_guidance_logits": (C.c_int, [C.POINTER(GuidanceArgs), vp]),
     "kx_attention_decode_block": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp]),
     "kx_decoder_decode_step_block": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp,

@@ -57,6 +57,11 @@ session), adds the per-id biases (-inf = a ban) and subtracts frequency * count 
 operations an outside reference can restate bit for bit.  ``min_p`` is one more threshold inside the sampler, after top-p
 (kx_sample_logits_min_p).  With the four at their defaults: no buffer, no launch, the sampler's old entry points.
 
+Truncation sampling (``typical_p``, ``epsilon_cutoff``, ``eta_cutoff``; generate_loop and everything that runs it): the three
+`transformers` truncation samplers as further stages inside the sampler launch, behind min-p and in that order, each over what the
+stage before it kept (kx_sample_logits_truncate).  Only when sampling; no buffer, no further launch, and with the three at their
+defaults the entry points above.
+
 Classifier-free guidance (``guidance_scale`` = s with ``negative_prompt_ids`` / ``negative_prompt_lengths`` / ``negative_images``;
 run_generate and generate_loop): every sequence runs as two rows of one 2B-row ragged batch — rows 0..B-1 read the prompt (the
 conditional rows), rows B..2B-1 a negative prompt or a negative image (the unconditional rows) — prefilled through _prefill unchanged
@@ -68,7 +73,7 @@ at 1.0: no buffer, no launch, no further host read, nothing doubled.
 
 Not offered: guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
 image, log-probs of the guided distribution; the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
-turn, typical-p / epsilon / eta sampling; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
+turn; the truncation samplers with beams or prompt lookup, ``min_tokens_to_keep`` above 1, log-probs of the truncated distribution; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
 that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
 sessions, sessions under beams or prompt lookup, compaction of finished rows, replaying the step as a captured graph, padding masks in
 ``Decoder.forward`` (``self_attn_padding_mask``); speculation with sampling, beams, constraints or ragged prompts, a draft model; with beams: ragged prompts, penalties, sampling and the constraints that read a per-beam history
@@ -90,7 +95,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                   no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
                   prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0, token_automaton=None,
                   automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None):
+                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
     ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
     reads — the last position, or lengths[b] - 1 of a ragged row.
@@ -131,6 +136,9 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     session's turn starts from zero.  ``min_p`` goes to the sampler launch (kx_sample_logits_min_p), after top-p.  The raw row
     ``output_logits`` and ``output_logprobs`` use is taken before the launch.  With the four at their defaults: no buffer, no
     launch, the sampler's old entry points.
+    ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` (check_truncation_args): the ones switched on go to the sampler launch
+    (kx_sample_logits_truncate, ``min_p`` with them), behind min-p in that order.  No buffer and no further launch; with the three at
+    their defaults the entry points are the ones named above.
     ``guidance_scale`` = s other than 1.0 (check_guidance_args): ``logits``, ``prompt_tokens``, ``lengths`` and ``text_lengths`` are the
     2B rows run_generate prefilled — rows 0..B-1 conditional, rows B..2B-1 unconditional, always a ragged batch; the negatives are
     already those rows, so ``negative_prompt_ids`` / ``negative_prompt_lengths`` are only checked here.  The step runs at 2B rows
@@ -165,6 +173,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                              min_p=min_p)
     shaping = shape is not None and shape["launch"]
     min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
+    min_p.update(check_truncation_args(typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))          # (everything the sampler launch takes beyond its old arguments)
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(R, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -469,6 +478,34 @@ def check_shape_args(vocab: int, batch: int, *, logit_bias=None, presence_penalt
         raise ValueError(f"{', '.join(names)}: not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
                          f"{prompt_lookup_num_tokens}): a verify step emits a varying number of tokens per row; see DESIGN.md §8")
     out["launch"] = names != ["min_p"]
+    return out
+
+
+def check_truncation_args(*, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, num_beams=1, prompt_lookup_num_tokens=0):
+    """ValueError (naming ``typical_p``, ``epsilon_cutoff`` or ``eta_cutoff``) for what generate() refuses of the truncation
+    samplers, before the device check and any launch: ``typical_p`` outside (0, 1] (1 = off), a cut-off outside [0, 1) (0 = off), a
+    bool or a non-number, and any of them together with beams or prompt lookup.  Returns the keywords ops.sample_logits takes for
+    the ones that are switched on — an empty dict at the defaults: the sampler's old entry points."""
+    out = {}
+    for name, v, off, low_open in (("typical_p", typical_p, 1.0, True), ("epsilon_cutoff", epsilon_cutoff, 0.0, False),
+                                   ("eta_cutoff", eta_cutoff, 0.0, False)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+        v = float(v)
+        if low_open and not 0.0 < v <= 1.0:
+            raise ValueError(f"typical_p = {v!r} must be in (0, 1] (1 = off)")
+        if not low_open and not 0.0 <= v < 1.0:
+            raise ValueError(f"{name} = {v!r} must be in [0, 1) (0 = off)")
+        if v != off:
+            out[name] = v
+    if not out:
+        return out
+    if num_beams not in (1, None):
+        raise ValueError(f"{', '.join(out)}: not offered together with num_beams = {num_beams}: beams rank log-probs and do not "
+                         "sample; see DESIGN.md §8")
+    if prompt_lookup_num_tokens not in (0, None):
+        raise ValueError(f"{', '.join(out)}: not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
+                         f"{prompt_lookup_num_tokens}): its verify step is greedy; see DESIGN.md §8")
     return out
 
 
@@ -1054,6 +1091,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
     automaton = ("token_automaton", "automaton_start")
     shaping = ("logit_bias", "presence_penalty", "frequency_penalty", "min_p")
+    truncation = ("typical_p", "epsilon_cutoff", "eta_cutoff")
     negatives = ("negative_prompt_ids", "negative_prompt_lengths")
     guide = check_guidance_args(tokens.shape[0] if tokens.dim() else 0, min_len=prompt["min_len"], multimodal="negative_images" in kw,
                                 negative_images=kw.get("negative_images"), **pick(
@@ -1069,6 +1107,7 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     check_logprob_args(vocab, beams=beams, drafts=drafts, **pick("output_logprobs", "top_logprobs"))
     check_automaton_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*automaton, "prompt_lookup_num_tokens"))
     check_shape_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*shaping, "num_beams", "prompt_lookup_num_tokens"))
+    check_truncation_args(**pick(*truncation, "num_beams", "prompt_lookup_num_tokens"))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
                                                                               "prompt_lookup_num_tokens"))
@@ -1083,12 +1122,12 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
                                  prompt_rows=prompt_rows, lengths=[prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
                                  guidance_scale=guide["scale"], **pick(
                                      "eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits",
-                                     "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
+                                     "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
         tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts,
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
             return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
-                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping)))
+                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation)))
         common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
@@ -1101,10 +1140,10 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
         if samples > 1:
             return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
                                  lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
+                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
         return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
                              lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping))
+                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
 
 
 def run_score(model, prompt: dict, continuations, kw: dict):
@@ -1334,7 +1373,7 @@ class Session:
                  top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prefill_chunk=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
-                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0):
+                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
         at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
         session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
@@ -1345,7 +1384,8 @@ class Session:
         ``token_automaton`` / ``automaton_start``: this turn's own automaton, every row beginning in its start state — the states of
         an earlier turn are not kept, and the automaton reads the turn's output only.
         ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p``: as in generate(); the penalties count what THIS turn
-        emitted — every turn starts from zero counts, and neither the prompt nor an earlier turn's output counts."""
+        emitted — every turn starts from zero counts, and neither the prompt nor an earlier turn's output counts.
+        ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: as in generate()."""
         lens = self._check_turn(x, prompt_lengths)
         vocab = self._model.embed.weight.shape[0]
         check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
@@ -1354,6 +1394,7 @@ class Session:
         check_automaton_args(vocab, self.batch, token_automaton=token_automaton, automaton_start=automaton_start)
         check_shape_args(vocab, self.batch, logit_bias=logit_bias, presence_penalty=presence_penalty,
                          frequency_penalty=frequency_penalty, min_p=min_p)
+        check_truncation_args(typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         chunk = check_prefill_chunk(prefill_chunk)
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
@@ -1373,7 +1414,8 @@ class Session:
                     output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                     min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, output_logprobs=output_logprobs,
                     top_logprobs=top_logprobs, token_automaton=token_automaton, automaton_start=automaton_start,
-                    logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p))
+                    logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p,
+                    typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
             finally:
                 self._state["pos_max"] = max(self._cached)
             out = res[0] if isinstance(res, tuple) else res

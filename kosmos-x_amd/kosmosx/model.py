@@ -1335,7 +1335,8 @@ class Kosmos(nn.Module):
                  prompt_lookup_num_tokens=0, max_matching_ngram_size=2, output_acceptance=False, _draft_from=None,
                  prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
                  token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                 guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None):
+                 guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None,
+                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1442,7 +1443,16 @@ class Kosmos(nn.Module):
         [B, n_new, vocab]; ``output_logprobs`` / ``top_logprobs`` keep meaning the model's own distribution on the conditional row.
         It composes with sampling and all filters, ``prompt_lengths``, ``eos_token_id``, the constraints, automata, the shaping
         keywords, log-probs and ``prefill_chunk``; with ``num_beams`` > 1, ``prompt_lookup_num_tokens`` > 0,
-        ``num_return_sequences`` > 1 or ``return_session``: ValueError naming ``guidance_scale``."""
+        ``num_return_sequences`` > 1 or ``return_session``: ValueError naming ``guidance_scale``.
+        ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: the `transformers` truncation samplers, inside the sampler launch
+        (kx_sample_logits_truncate) behind ``min_p`` and in that order, each over the distribution renormalised on what the stage
+        before it kept; only when sampling, ignored under greedy as ``top_k`` is.  ``typical_p`` = t in (0, 1] (1 = off): the tokens
+        whose surprise -log p lies closest to the entropy, as many as it takes to reach mass t — ties included, and not necessarily
+        the most likely token.  ``epsilon_cutoff`` = e in [0, 1) (0 = off): the tokens with p >= e.  ``eta_cutoff`` = e in [0, 1)
+        (0 = off): the tokens with p >= min(e, sqrt(e) exp(-entropy)).  Epsilon and eta always keep the most likely token of what
+        they were handed.  They compose with everything sampling composes with; with ``num_beams`` > 1 or
+        ``prompt_lookup_num_tokens`` > 0, or with a value out of range: ValueError naming the argument.  With the three at their
+        defaults nothing changes: the same launches."""
         from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1459,7 +1469,7 @@ class Kosmos(nn.Module):
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
             output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
             automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, min_p=min_p))
+            frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1635,7 +1645,7 @@ class KosmosLanguage(nn.Module):
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
                  session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
                  logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, guidance_scale=1.0,
-                 negative_prompt_ids=None, negative_prompt_lengths=None):
+                 negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1649,7 +1659,8 @@ class KosmosLanguage(nn.Module):
         ``min_p``: the completion-API request fields, applied on the device, as there; ``guidance_scale``,
         ``negative_prompt_ids`` and ``negative_prompt_lengths``: classifier-free guidance against a negative prompt, as there —
         a negative prompt has at least one token, and with ``negative_prompt_ids`` None row b's unconditional context is its last
-        prompt token, as in `transformers`)."""
+        prompt token, as in `transformers`; ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff``: the truncation samplers inside the
+        sampler launch, as there)."""
         from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
@@ -1665,7 +1676,7 @@ class KosmosLanguage(nn.Module):
             prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
             output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
             automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, min_p=min_p))
+            frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):

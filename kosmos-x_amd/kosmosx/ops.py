@@ -440,7 +440,8 @@ def token_range(tokens, out=None):
 
 def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
                   position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
-                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0, min_p=0.0):
+                  pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0, min_p=0.0,
+                  typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """Next token of every row of fp32 `logits` [B, V] (row stride >= V), drawn on the device by one launch
     (kx_sample_logits in include/kosmosx_hip.h: repetition penalty -> temperature -> top-k -> top-p -> Gumbel-max draw
     addressed by (seed, sequence id, position); greedy when ``do_sample`` is false or ``temperature`` is 0).
@@ -452,6 +453,9 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     ``positions[b] + advance`` and, when ``advance`` is not 0, leaves that value in ``positions[b]``; ``position`` is unused.
     min_p in [0, 1] (0 = off: the two entry points above are called as before): after top-p, keep only x_i >= x_max + log(min_p)
     (kx_sample_logits_min_p, either form); ignored under greedy.
+    typical_p in (0, 1] (1 = off), epsilon_cutoff and eta_cutoff in [0, 1) (0 = off; with all three off the entry points above are
+    called as before): the `transformers` truncation samplers, behind min-p in that order, each over what the one before it kept
+    (kx_sample_logits_truncate, either form); ignored under greedy.
     Returns next_token [B] int64 (and kept_count [B] int32, keep_mask [B, V] uint8 with ``return_debug``)."""
     _need_cuda(logits, sequence_ids, history, finished, out, out_tokens, positions)
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
@@ -489,7 +493,19 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     min_p = float(min_p)
     if not 0.0 <= min_p <= 1.0:
         raise ValueError(f"sample_logits: min_p = {min_p} must be in [0, 1]")
-    if min_p != 0.0:
+    typical_p, epsilon_cutoff, eta_cutoff = float(typical_p), float(epsilon_cutoff), float(eta_cutoff)
+    if not 0.0 < typical_p <= 1.0:
+        raise ValueError(f"sample_logits: typical_p = {typical_p} must be in (0, 1]")
+    for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        if not 0.0 <= v < 1.0:
+            raise ValueError(f"sample_logits: {name} = {v} must be in [0, 1)")
+    if typical_p != 1.0 or epsilon_cutoff != 0.0 or eta_cutoff != 0.0:
+        if positions is not None:
+            a.position = 0
+        t = H.TruncateArgs(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        H.check(H.load().kx_sample_logits_truncate(C.byref(a), H.ptr(positions), int(advance) if positions is not None else 0,
+                                                   C.byref(t), _stream()), "kx_sample_logits_truncate")
+    elif min_p != 0.0:
         if positions is not None:
             a.position = 0
         H.check(H.load().kx_sample_logits_min_p(C.byref(a), H.ptr(positions), int(advance) if positions is not None else 0, min_p,
