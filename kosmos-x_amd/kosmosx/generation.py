@@ -4,6 +4,12 @@ The loop stays on the device: kx_sample_logits reads the logits row a step has j
 device memory, kx_embed_step gathers its embedding for the next step.  The host only enqueues; its one read is the stop
 poll, every ``eos_poll`` steps and only when an ``eos_token_id`` is given.
 
+Options: a public generate() takes its keyword arguments by name (_keywords) and run_generate validates every one of them once, in
+one fixed order, each check_* function being handed the keywords its own signature names (_own).  What the plain loop was asked for
+then travels as one LoopOptions — validated, resolved, frozen — to generate_loop and to everything that runs it: parallel_loop, the
+guided call, a session's turns.  loop_options is the one internal place that names the plain loop's keywords and their defaults, and
+where each of them is described; Session.generate and the tests that drive the loops directly call it.  The loops check nothing again.
+
 Ragged batches (``prompt_lengths``): every row has its own position, an int32 word in device memory that the sampler
 advances (kx_sample_logits_ragged) and the decode step reads (kx_decoder_decode_step_ragged) — a step's launch arguments are
 then the same for every token.  Each row generates what it would generate alone.
@@ -81,6 +87,9 @@ sessions, sessions under beams or prompt lookup, compaction of finished rows, re
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
+import inspect
 import operator
 
 import torch
@@ -89,30 +98,67 @@ from . import _hip as H
 from . import ops
 
 
-def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
-                  *, pos_shift: int = 0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
-                  seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, lengths=None,
-                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None, text_lengths=None,
-                  prompt_rows=None, pad_launches=None, output_logprobs=False, top_logprobs=0, token_automaton=None,
-                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
-    """``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
-    ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
-    reads — the last position, or lengths[b] - 1 of a ragged row.
-    ``prompt_tokens`` [B, Tt] int64: what the repetition penalty sees before the first new token.  ``pos_shift`` > 0: the
-    prompt holds that many spliced rows that are not tokens and text rows carry two position rows (the multimodal prompt
-    under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t].
-    ``lengths`` (host ints, validated by resolve_prompt_lengths): the ragged batch — row b's sequence has lengths[b] <= T
-    positions (spliced rows included), the rest of its prompt is right padding whose ids mask_padding replaced.
+def _keywords(scope: dict, *positional) -> dict:
+    """A function's keyword arguments by name: ``scope`` is its locals(), taken as the first statement of its body, ``positional``
+    the parameters that are not among them.  The signature stays the one place that spells them."""
+    return {k: v for k, v in scope.items() if k not in positional}
+
+
+@functools.lru_cache(maxsize=None)
+def _keyword_names(fn) -> tuple:
+    return tuple(n for n, p in inspect.signature(fn).parameters.items() if p.kind is p.KEYWORD_ONLY)
+
+
+def _own(fn, kw: dict) -> dict:
+    """The entries of ``kw`` that ``fn`` declares as keyword-only arguments: a check or a loop is handed what its signature names."""
+    return {n: kw[n] for n in _keyword_names(fn) if n in kw}
+
+
+@dataclasses.dataclass(frozen=True)
+class LoopOptions:
+    """What generate_loop was asked for, validated and resolved: loop_options builds it, or run_generate from its own checks."""
+    do_sample: bool
+    temperature: float
+    top_k: int
+    top_p: float
+    repetition_penalty: float
+    seed: int
+    sequence_ids: object
+    eos_token_id: object
+    pad_token_id: int
+    eos_poll: int
+    output_logits: bool
+    output_logprobs: bool
+    top_logprobs: int
+    constraints: object                 # check_constraint_args' dict, or None: no kx_constrain_logits launch
+    automaton: object                   # (the TokenAutomaton, check_automaton_args' host list of start states), or None
+    shape: object                       # check_shape_args' dict, or None
+    sampler: dict                       # what the sampler launch takes beyond its old arguments: min_p, check_truncation_args' keywords
+    guidance: object                    # check_guidance_args' scale, or None
+
+    @classmethod
+    def resolved(cls, kw: dict, cons, starts, shape, truncation: dict, guide):
+        """From the keyword arguments by name and what the checks returned for them."""
+        min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
+        return cls(**{f.name: kw[f.name] for f in dataclasses.fields(cls) if f.name in kw}, constraints=cons, shape=shape,
+                   automaton=None if starts is None else (kw["token_automaton"], starts), sampler={**min_p, **truncation},
+                   guidance=None if guide is None else guide["scale"])
+
+
+def loop_options(vocab: int, batch: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
+                 eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, no_repeat_ngram_size=0,
+                 bad_words_ids=None, min_new_tokens=0, stop_sequences=None, output_logprobs=False, top_logprobs=0,
+                 token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
+                 guidance_scale=1.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0) -> LoopOptions:
+    """The plain loop's keyword arguments -> the LoopOptions generate_loop takes, or the ValueError of the first check that refuses
+    one: check_constraint_args, check_logprob_args, check_automaton_args, check_shape_args, check_truncation_args, in this order
+    (then the scale through check_guidance_args); host only.  ``vocab``: the model's; ``batch``: the rows B the per-row values are
+    given for.  What generate_loop does with each of them:
     Constraints (check_constraint_args): kx_constrain_logits runs on the row immediately before each sampler launch.  Its
     history is ``prompt_tokens`` followed by the generated tokens — the TEXT ids only: spliced image rows contribute no ids, so
     an n-gram, a bad word or a stop sequence may span the splice point.  ``text_lengths`` (ragged batches; default ``lengths``):
     row b's number of prompt TOKENS, where ``lengths`` counts the spliced rows too.  ``output_logits`` keeps returning the
     model's own logits, taken before the bans.
-    ``pad_launches`` (sessions; ragged batches only): an int32 [B] device tensor, zero on entry.  Before every sampler launch — after
-    the step's constraint launch — the ``finished`` bytes are added to it, so that row b entered n - pad_launches[b] of the n
-    sampler launches unfinished: its valid tokens, an EOS or the last token of a stop sequence included.  It is read back once,
-    after the loop, in the same copy as the step kernels' error word, and left in state["turn"] = (n, [pad launches per row]).
     ``output_logprobs`` / ``top_logprobs`` = k (check_logprob_args): one kx_step_logprobs launch after each sampler launch writes
     column g of token_logprobs [B, max_new_tokens] — the log-prob of the token just drawn under the model's own logits, the rows
     ``output_logits`` returns — and with k > 0 of top_logprobs / top_ids [B, max_new_tokens, k].  On a step with a constraint launch
@@ -141,7 +187,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     their defaults the entry points are the ones named above.
     ``guidance_scale`` = s other than 1.0 (check_guidance_args): ``logits``, ``prompt_tokens``, ``lengths`` and ``text_lengths`` are the
     2B rows run_generate prefilled — rows 0..B-1 conditional, rows B..2B-1 unconditional, always a ragged batch; the negatives are
-    already those rows, so ``negative_prompt_ids`` / ``negative_prompt_lengths`` are only checked here.  The step runs at 2B rows
+    already those rows, so the loop takes the scale alone.  The step runs at 2B rows
     (``positions`` int32 [2B], ``nxt`` int64 [2B], _ragged_scratch at 2B); the sampler and every row editor see B rows — the first
     B of ``positions`` / ``nxt`` and the conditional logits rows, with ``finished``, the histories (the conditional prompts' text ids,
     then the output), the counts, the automaton states and ``out`` at B rows.  Per token one kx_guidance_logits launch comes first:
@@ -150,43 +196,64 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     draws at the conditional row's Philox position with ``sequence_ids[b]``: the stream of the unguided ragged call.  No host read is
     added: the error word covers all 2B rows and is read where it already is.  ``output_logits`` keeps the conditional rows' raw
     logits and, returned directly after them, the unconditional rows', both taken before the launch; ``output_logprobs`` reads the
-    conditional rows' raw logits.  ``pad_launches`` (sessions) is refused.  With the scale at 1.0 nothing of this happens.
+    conditional rows' raw logits.  ``pad_launches`` (sessions) is refused.  With the scale at 1.0 nothing of this happens."""
+    kw = _keywords(locals(), "vocab", "batch")
+    cons = check_constraint_args(vocab, **_own(check_constraint_args, kw))
+    check_logprob_args(vocab, **_own(check_logprob_args, kw))
+    starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
+    shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
+    truncation = check_truncation_args(**_own(check_truncation_args, kw))
+    return LoopOptions.resolved(kw, cons, starts, shape, truncation, check_guidance_args(batch, **_own(check_guidance_args, kw)))
+
+
+def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
+                  opts: LoopOptions, *, pos_shift: int = 0, lengths=None, text_lengths=None, prompt_rows=None, pad_launches=None):
+    """The plain loop on a prefilled state; ``opts``: what the caller asked for, resolved (LoopOptions; loop_options says what the
+    loop does with each option).  Nothing is validated here but the shape of a guided batch.
+    ``logits`` [B, T, V]: the prefill's output, ``state`` the incremental state it filled (state["len"] == T).
+    ``prompt_rows`` = T (a chunked prefill, _prefill): ``logits`` is [B, 1, V] instead and holds only the row each sequence
+    reads — the last position, or lengths[b] - 1 of a ragged row.
+    ``prompt_tokens`` [B, Tt] int64: what the repetition penalty sees before the first new token.  ``pos_shift`` > 0: the
+    prompt holds that many spliced rows that are not tokens and text rows carry two position rows (the multimodal prompt
+    under u1_inplace_alias): a token at sequence position t is embedded with pos[2 + t - pos_shift] + pos[2 + t].
+    ``lengths`` (host ints, validated by resolve_prompt_lengths): the ragged batch — row b's sequence has lengths[b] <= T
+    positions (spliced rows included), the rest of its prompt is right padding whose ids mask_padding replaced.
+    ``text_lengths`` (ragged batches; default ``lengths``): row b's number of prompt TOKENS, what the constraints' history holds.
+    ``pad_launches`` (sessions; ragged batches only): an int32 [B] device tensor, zero on entry.  Before every sampler launch — after
+    the step's constraint launch — the ``finished`` bytes are added to it, so that row b entered n - pad_launches[b] of the n
+    sampler launches unfinished: its valid tokens, an EOS or the last token of a stop sequence included.  It is read back once,
+    after the loop, in the same copy as the step kernels' error word, and left in state["turn"] = (n, [pad launches per row]).
+    Under guidance (``opts.guidance``) ``logits``, ``prompt_tokens``, ``lengths`` and ``text_lengths`` hold 2B rows.
     Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits`` (under guidance followed by the fp32
     [B, n, V] unconditional logits); then with ``output_logprobs`` the fp32
     [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
+    eos_token_id, pad_token_id, eos_poll, sequence_ids = opts.eos_token_id, opts.pad_token_id, opts.eos_poll, opts.sequence_ids
+    output_logits, output_logprobs, k = opts.output_logits, opts.output_logprobs, int(opts.top_logprobs)
+    cons, shape, guide = opts.constraints, opts.shape, opts.guidance
+    token_automaton, auto = opts.automaton or (None, None)
     R, T, V = logits.shape                                                # R: the rows of the step; B: the rows of the sampler
-    guide = check_guidance_args(R // 2, guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids,
-                                negative_prompt_lengths=negative_prompt_lengths)
     B = R if guide is None else R // 2
     if guide is not None and (R % 2 or lengths is None or len(lengths) != R or pad_launches is not None):
-        raise ValueError(f"guidance_scale = {guidance_scale!r} takes the 2B-row ragged batch of run_generate: conditional rows, then "
+        raise ValueError(f"guidance_scale = {guide!r} takes the 2B-row ragged batch of run_generate: conditional rows, then "
                          "unconditional rows, ``lengths`` for all of them, no ``pad_launches``")
     gathered = prompt_rows is not None
     if gathered:
         T = prompt_rows
     dev = logits.device
-    cons = check_constraint_args(V, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                                 min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
-    auto = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
     can_finish = eos_token_id is not None or (cons is not None and cons["stop"]) or auto is not None
-    shape = check_shape_args(V, B, logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                             min_p=min_p)
     shaping = shape is not None and shape["launch"]
-    min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
-    min_p.update(check_truncation_args(typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))          # (everything the sampler launch takes beyond its old arguments)
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(R, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
     history = None
     prompt_tokens = prompt_tokens[:B]                                     # (guidance: the histories see the conditional prompts)
     Tt = prompt_tokens.shape[1]
-    if float(repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"]):
+    if float(opts.repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"]):
         history = torch.empty((B, Tt + max_new_tokens), dtype=torch.int64, device=dev)           # (the sampler appends with r == 1 too)
         history[:, :Tt] = prompt_tokens
     if sequence_ids is not None:
         sequence_ids = sequence_ids.to(device=dev, dtype=torch.int64).contiguous()
     kept, kept_u = [], []
-    k = int(top_logprobs)
     lp = top_lp = top_ids = snap = None
     if output_logprobs:                                                   # every buffer before the first step
         lp = torch.zeros((B, max_new_tokens), dtype=torch.float32, device=dev)
@@ -225,6 +292,10 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         counts = torch.zeros((B, V), dtype=torch.int32, device=dev) if penalised else None
     # what the sampler and every row editor see: all R rows, or under guidance the first B of them (views, taken once)
     spos, snxt = (positions, nxt) if guide is None else (positions[:B], nxt[:B])
+    # the sampler launch's arguments that every token shares (opts.sampler: what it takes beyond its old arguments)
+    sampler = dict(temperature=opts.temperature, top_k=opts.top_k, top_p=opts.top_p, repetition_penalty=opts.repetition_penalty,
+                   do_sample=opts.do_sample, seed=opts.seed, sequence_ids=sequence_ids, history=history, finished=finished,
+                   eos_token_id=eos_token_id, pad_token_id=pad_token_id, out_tokens=out, **opts.sampler)
     n = 0
     for g in range(max_new_tokens):
         constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
@@ -240,7 +311,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         elif output_logprobs and (constrained or auto is not None or shaping or guide is not None):
             raw = row.clone()                                             # (the guidance, constraint, automaton and shaping launches edit the row in place)
         if guide is not None:                                             # the guided row over the conditional one; the unconditional positions move on
-            ops.guidance_logits(row, step_rows[B:], scale=guide["scale"], finished=finished, positions=positions[B:], advance=int(g > 0))
+            ops.guidance_logits(row, step_rows[B:], scale=guide, finished=finished, positions=positions[B:], advance=int(g > 0))
         if constrained:
             ops.constrain_logits(row, history=history, hist_len=Tt + g if history is not None else 0, prompt_width=Tt,
                                  prompt_lens=plens if history is not None else None, new_tokens=g,
@@ -256,17 +327,11 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if snap is not None:
             snap.copy_(finished)
         if positions is not None:                                         # Philox position lengths[b] + g, kept in positions[b]
-            ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                              do_sample=do_sample, seed=seed, positions=spos, advance=int(g > 0), sequence_ids=sequence_ids,
-                              history=history, hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, out=snxt, out_tokens=out, out_col=g, **min_p)
+            ops.sample_logits(row, positions=spos, advance=int(g > 0), hist_len=Tt + g, out=snxt, out_col=g, **sampler)
             if guide is not None:
                 nxt[B:].copy_(snxt)                                       # both rows of a pair are fed the token just sampled
         else:
-            ops.sample_logits(row, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                              do_sample=do_sample, seed=seed, position=T + g, sequence_ids=sequence_ids, history=history,
-                              hist_len=Tt + g, finished=finished, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                              out=nxt, out_tokens=out, out_col=g, **min_p)
+            ops.sample_logits(row, position=T + g, hist_len=Tt + g, out=nxt, out_col=g, **sampler)
         if auto is not None and snap is not None:
             # a row this launch finished on a token other than the EOS had no candidate: what it emitted is a pad, no token of the row
             dead = (finished - snap) * (snxt != not_eos)
@@ -314,6 +379,35 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
 
 MAX_BEAMS = 16
 MAX_NGRAM = MAX_SEQUENCE = 64           # kx_constrain_logits' limits
+FP32_MAX = 3.4028234663852886e38
+
+
+def _finite_fp32(v) -> bool:
+    """Whether ``v`` is a number (a bool is none) that is finite in fp32."""
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and abs(v) <= FP32_MAX
+
+
+def _host_ints(v, count: int, name: str, per: str, joint: bool = False) -> list:
+    """``v``, a sequence of ``count`` integers or an integer tensor -> the host list, or ValueError naming ``name``.  ``per``: what
+    an entry stands for; ``joint``: a tensor's dtype and shape are refused in one message.  Host data is taken as it is; a device
+    tensor is read back once."""
+    if isinstance(v, torch.Tensor):
+        integers = not (v.is_floating_point() or v.is_complex() or v.dtype == torch.bool)
+        if joint and not (integers and v.dim() == 1):
+            raise ValueError(f"{name} must be {count} integers, got a {v.dtype} tensor of shape {tuple(v.shape)}")
+        if not integers:
+            raise ValueError(f"{name} must hold integers, got a {v.dtype} tensor")
+        if v.dim() != 1:
+            raise ValueError(f"{name} must have {count} entries, got shape {tuple(v.shape)}")
+        out = v.tolist()                                   # (the one read of a device tensor)
+    else:
+        try:
+            out = [operator.index(i) for i in v]
+        except TypeError:
+            raise ValueError(f"{name} must be a sequence of {count} integers or an integer tensor, got {v!r}") from None
+    if len(out) != count:
+        raise ValueError(f"{name} must have {count} entries (one per {per}), got {len(out)}")
+    return out
 
 
 def _check_sequences(name: str, seqs, vocab: int) -> list:
@@ -410,18 +504,7 @@ def check_automaton_args(vocab: int, batch: int, *, token_automaton=None, automa
     S = token_automaton.num_states
     if automaton_start is None:
         return [token_automaton.start] * batch
-    if isinstance(automaton_start, torch.Tensor):
-        t = automaton_start
-        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
-            raise ValueError(f"automaton_start must be {batch} integers, got a {t.dtype} tensor of shape {tuple(t.shape)}")
-        starts = t.tolist()                                # (the one read of a device tensor)
-    else:
-        try:
-            starts = [operator.index(s) for s in automaton_start]
-        except TypeError:
-            raise ValueError(f"automaton_start must be a sequence of {batch} integers or an integer tensor, got {automaton_start!r}") from None
-    if len(starts) != batch:
-        raise ValueError(f"automaton_start must have {batch} entries (one per row), got {len(starts)}")
+    starts = _host_ints(automaton_start, batch, "automaton_start", "row", joint=True)
     for b, s in enumerate(starts):
         if not 0 <= s < S:
             raise ValueError(f"automaton_start[{b}] = {s} is outside the automaton's {S} states")
@@ -438,7 +521,7 @@ def check_shape_args(vocab: int, batch: int, *, logit_bias=None, presence_penalt
     import math
     out = dict(bias=None)
     for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty), ("min_p", min_p)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(v) <= 3.4028234663852886e38:
+        if not _finite_fp32(v):
             raise ValueError(f"{name} must be a finite number (in fp32), got {v!r}")
         out[name.split("_")[0] if name != "min_p" else name] = float(v)
     if not 0.0 <= out["min_p"] <= 1.0:
@@ -461,7 +544,7 @@ def check_shape_args(vocab: int, batch: int, *, logit_bias=None, presence_penalt
                     raise ValueError(f"logit_bias[{b}]: id {i} is outside the vocabulary of {vocab}")
                 if i in ent:
                     raise ValueError(f"logit_bias[{b}]: id {i} is listed twice")
-                if not (v == -math.inf or abs(v) <= 3.4028234663852886e38):
+                if not (v == -math.inf or _finite_fp32(v)):
                     raise ValueError(f"logit_bias[{b}][{i}] = {v} must be finite (in fp32) or -inf (a ban)")
                 ent[i] = v
             bias.append(sorted(ent.items()))
@@ -486,9 +569,9 @@ def check_truncation_args(*, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, 
     samplers, before the device check and any launch: ``typical_p`` outside (0, 1] (1 = off), a cut-off outside [0, 1) (0 = off), a
     bool or a non-number, and any of them together with beams or prompt lookup.  Returns the keywords ops.sample_logits takes for
     the ones that are switched on — an empty dict at the defaults: the sampler's old entry points."""
-    out = {}
-    for name, v, off, low_open in (("typical_p", typical_p, 1.0, True), ("epsilon_cutoff", epsilon_cutoff, 0.0, False),
-                                   ("eta_cutoff", eta_cutoff, 0.0, False)):
+    given, out = locals(), {}
+    for name, off, low_open in (("typical_p", 1.0, True), ("epsilon_cutoff", 0.0, False), ("eta_cutoff", 0.0, False)):
+        v = given[name]
         if isinstance(v, bool) or not isinstance(v, (int, float)):
             raise ValueError(f"{name} must be a number, got {v!r}")
         v = float(v)
@@ -519,7 +602,7 @@ def check_guidance_args(batch: int, *, guidance_scale=1.0, negative_prompt_ids=N
     ``scale`` (float) and ``lengths`` (the negative prompts' host lengths where they could be checked without a device read, else
     None: an integer tensor is resolved after the device check, as ``prompt_lengths`` is)."""
     s = guidance_scale
-    if isinstance(s, bool) or not isinstance(s, (int, float)) or not abs(s) <= 3.4028234663852886e38:
+    if not _finite_fp32(s):
         raise ValueError(f"guidance_scale must be a finite number (in fp32; 1.0 = off), got {s!r}")
     given = [n for n, v in (("negative_prompt_ids", negative_prompt_ids), ("negative_prompt_lengths", negative_prompt_lengths),
                             ("negative_images", negative_images)) if v is not None]
@@ -738,20 +821,20 @@ def check_parallel_args(*, num_return_sequences=1, beams=False, prompt_lookup_nu
     return n
 
 
-def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int, *,
-                  num_return_sequences: int, lengths=None, text_lengths=None, prompt_rows=None, token_automaton=None,
-                  automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, **loop):
+def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
+                  opts: LoopOptions, *, num_return_sequences: int, pos_shift: int = 0, lengths=None, text_lengths=None, prompt_rows=None):
     """n = ``num_return_sequences`` sampled continuations of each of the B prefilled prompts: ``state``, ``logits``, ``prompt_tokens``,
-    ``lengths``, ``text_lengths`` and ``prompt_rows`` as generate_loop takes them after a prefill at B rows, ``loop`` its further
-    keyword arguments.  The state's caches become the read-only prefix caches of B * n rows (state["prefix"]): row b * n + i reads the
-    len_b cache rows of sequence b and appends to its own sequence of the [L, B * n, heads, max_new_tokens, 64] tail caches.  The rows
-    then run generate_loop's ragged branch — the first logits row, the prompt tokens, the lengths and the start states of
-    ``token_automaton`` / ``automaton_start`` ([B]: prompt b's start goes to its n samples) and the per-prompt dicts of
-    ``logit_bias`` (prompt b's go to its n samples; every sample has its own counts) repeated n times, the positions
-    on the device — so row b * n + i gets what row b * n + i of generate_loop on the caches repeated per sample gets, bit for bit.
+    ``pos_shift``, ``lengths``, ``text_lengths`` and ``prompt_rows`` as generate_loop takes them after a prefill at B rows, ``opts``
+    the options resolved for those B rows.  The state's caches become the read-only prefix caches of B * n rows (state["prefix"]):
+    row b * n + i reads the len_b cache rows of sequence b and appends to its own sequence of the
+    [L, B * n, heads, max_new_tokens, 64] tail caches.  The rows then run generate_loop's ragged branch — the first logits row, the prompt tokens, the lengths, the automaton's start states
+    ([B]: prompt b's start goes to its n samples) and the per-prompt bias rows (prompt b's go to its n samples; every sample has
+    its own counts; one dict given for every row is already one list repeated) repeated n times on the resolved lists, nothing
+    parsed again, the positions on the device — so row b * n + i gets what row b * n + i of generate_loop on the caches repeated
+    per sample gets, bit for bit.
     Returns what generate_loop returns, at B * n rows."""
     n, N = int(num_return_sequences), int(max_new_tokens)
-    B, T, V = logits.shape
+    B, T, _ = logits.shape
     if prompt_rows is not None:
         T = prompt_rows
     dev = logits.device
@@ -764,18 +847,16 @@ def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     kc = state["kcache"]
     L, _, nh, _, hd = kc.shape
     seq = [b for b in range(B) for _ in range(n)]
-    starts = check_automaton_args(V, B, token_automaton=token_automaton, automaton_start=automaton_start)
-    check_shape_args(V, B, logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p)
-    if logit_bias is not None and not hasattr(logit_bias, "items"):
-        logit_bias = [list(logit_bias)[b] for b in seq]
+    if opts.automaton is not None:
+        opts = dataclasses.replace(opts, automaton=(opts.automaton[0], [opts.automaton[1][b] for b in seq]))
+    if opts.shape is not None and opts.shape["bias"] is not None:
+        opts = dataclasses.replace(opts, shape=dict(opts.shape, bias=[opts.shape["bias"][b] for b in seq]))
     state["prefix"] = dict(ktail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            vtail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            prefix_seq=torch.tensor(seq, dtype=torch.int32, device=dev),
                            prefix_len=torch.tensor([plens[b] for b in seq], dtype=torch.int32, device=dev))
     return generate_loop(decoder, prec, state, first.repeat_interleave(n, dim=0).unsqueeze(1), prompt_tokens.repeat_interleave(n, dim=0),
-                         N, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T,
-                         token_automaton=token_automaton, automaton_start=None if starts is None else [starts[b] for b in seq],
-                         logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, **loop)
+                         N, opts, pos_shift=pos_shift, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T)
 
 
 MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
@@ -925,19 +1006,7 @@ def check_score_args(batch: int, continuations, continuation_lengths=None, promp
     if continuation_lengths is None:
         lens = [L] * C
     else:
-        if isinstance(continuation_lengths, torch.Tensor):
-            cl = continuation_lengths
-            if cl.is_floating_point() or cl.is_complex() or cl.dtype == torch.bool or cl.dim() != 1:
-                raise ValueError(f"continuation_lengths must be {C} integers, got a {cl.dtype} tensor of shape {tuple(cl.shape)}")
-            lens = cl.tolist()                             # (the one read of a device tensor)
-        else:
-            try:
-                lens = [operator.index(l) for l in continuation_lengths]
-            except TypeError:
-                raise ValueError(f"continuation_lengths must be a sequence of {C} integers or an integer tensor, got "
-                                 f"{continuation_lengths!r}") from None
-        if len(lens) != C:
-            raise ValueError(f"continuation_lengths must have {C} entries (one per candidate), got {len(lens)}")
+        lens = _host_ints(continuation_lengths, C, "continuation_lengths", "candidate", joint=True)
         for c, l in enumerate(lens):
             if not 1 <= l <= L:
                 raise ValueError(f"continuation_lengths[{c}] = {l} is outside 1..{L}")
@@ -1084,66 +1153,44 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     argument checks), ``passed_x`` (a callable: the tokens as prefilled -> the [B, T, D] rows the prefill takes, or None for the
     tokens alone), ``min_len`` (the shortest ragged prompt), ``prefix_rows`` (the rows passed_x adds to the tokens') and
     ``pos_shift`` (as in generate_loop)."""
-    def pick(*names):
-        return {n: kw[n] for n in names}
     decoder, prec, vocab, tokens = model.decoder, model.precision, model.embed.weight.shape[0], prompt["tokens"]
-    sampling = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
-    constraints = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
-    automaton = ("token_automaton", "automaton_start")
-    shaping = ("logit_bias", "presence_penalty", "frequency_penalty", "min_p")
-    truncation = ("typical_p", "epsilon_cutoff", "eta_cutoff")
-    negatives = ("negative_prompt_ids", "negative_prompt_lengths")
-    guide = check_guidance_args(tokens.shape[0] if tokens.dim() else 0, min_len=prompt["min_len"], multimodal="negative_images" in kw,
-                                negative_images=kw.get("negative_images"), **pick(
-        "guidance_scale", *negatives, "num_beams", "prompt_lookup_num_tokens", "num_return_sequences", "return_session"))
-    beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **pick(
-        "num_beams", "length_penalty", "num_return_sequences", *sampling, "prompt_lengths", "sequence_ids", "output_logits",
-        "output_scores", "output_trace"))
-    samples = check_parallel_args(beams=beams, **pick("num_return_sequences", "prompt_lookup_num_tokens", "return_session"))
-    check_constraint_args(vocab, num_beams=kw["num_beams"] if beams else None, **pick(*constraints, "eos_token_id"))
-    drafts = check_lookup_args(tokens.shape[0] if tokens.dim() else 0, draft_from=kw["_draft_from"], **pick(
-        "prompt_lookup_num_tokens", "max_matching_ngram_size", "output_acceptance", *sampling, "num_beams", "prompt_lengths",
-        "sequence_ids", *constraints, "eos_poll"))
-    check_logprob_args(vocab, beams=beams, drafts=drafts, **pick("output_logprobs", "top_logprobs"))
-    check_automaton_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*automaton, "prompt_lookup_num_tokens"))
-    check_shape_args(vocab, tokens.shape[0] if tokens.dim() else 0, **pick(*shaping, "num_beams", "prompt_lookup_num_tokens"))
-    check_truncation_args(**pick(*truncation, "num_beams", "prompt_lookup_num_tokens"))
+    batch = tokens.shape[0] if tokens.dim() else 0
+    # every check once, in this order (the first refusal is the one a caller sees), each with the keywords its signature names
+    guide = check_guidance_args(batch, min_len=prompt["min_len"], multimodal="negative_images" in kw, **_own(check_guidance_args, kw))
+    beams = check_beam_args(vocab, beam_path=kw["_beam_path"], **_own(check_beam_args, kw))
+    samples = check_parallel_args(beams=beams, **_own(check_parallel_args, kw))
+    cons = check_constraint_args(vocab, **dict(_own(check_constraint_args, kw), num_beams=kw["num_beams"] if beams else None))
+    drafts = check_lookup_args(batch, draft_from=kw["_draft_from"], **_own(check_lookup_args, kw))
+    check_logprob_args(vocab, beams=beams, drafts=drafts, **_own(check_logprob_args, kw))
+    starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
+    shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
+    truncation = check_truncation_args(**_own(check_truncation_args, kw))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
-    capacity = check_session_args(decoder, beams=beams, drafts=drafts, **pick("return_session", "session_capacity", "num_beams",
-                                                                              "prompt_lookup_num_tokens"))
-    prompt["check"](**({} if guide is None or kw["negative_prompt_ids"] is None else pick("negative_prompt_ids")))
+    capacity = check_session_args(decoder, beams=beams, drafts=drafts, **_own(check_session_args, kw))
+    prompt["check"](**({} if guide is None or kw["negative_prompt_ids"] is None else dict(negative_prompt_ids=kw["negative_prompt_ids"])))
+    opts = LoopOptions.resolved(kw, cons, starts, shape, truncation, guide)      # what the four plain-loop paths below take
     with torch.no_grad():
         if guide is not None:
             # every sequence as two rows of one ragged batch: the prompt (rows 0..B-1) and its negative (rows B..2B-1), prefilled
             # through _prefill unchanged; generate_loop gives the sampler the first B rows and feeds both halves the same token
-            prompt, lengths2 = _guided_prompt(prompt, kw["prompt_lengths"], guide, **pick(*negatives))
+            prompt, lengths2 = _guided_prompt(prompt, kw["prompt_lengths"], guide, **_own(_guided_prompt, kw))
             tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, lengths2, max_new_tokens, chunk=chunk)
-            return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, pos_shift=prompt["pos_shift"],
-                                 prompt_rows=prompt_rows, lengths=[prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 guidance_scale=guide["scale"], **pick(
-                                     "eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits",
-                                     "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
+            return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, opts, pos_shift=prompt["pos_shift"],
+                                 prompt_rows=prompt_rows, lengths=[prompt["prefix_rows"] + l for l in lens], text_lengths=lens)
         tokens, lens, _, state, logits, prompt_rows = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, spare=drafts,
                                                                chunk=chunk, capacity=capacity)
         if capacity is not None:
-            return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, dict(
-                **pick("eos_token_id", "pad_token_id", "eos_poll", *sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation)))
-        common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows, **pick("eos_token_id", "pad_token_id", "eos_poll"))
+            return _first_turn(model, prompt, state, logits, tokens.long(), lens, prompt_rows, max_new_tokens, capacity, opts)
+        common = dict(pos_shift=prompt["pos_shift"], prompt_rows=prompt_rows)
         if drafts:
             return lookup_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_drafts=drafts,
-                               ngram_max=kw["max_matching_ngram_size"], draft_from=kw["_draft_from"], **common,
-                               **pick("output_logits", "output_acceptance"))
+                               ngram_max=kw["max_matching_ngram_size"], draft_from=kw["_draft_from"], **common, **_own(lookup_loop, kw))
         if beams:
-            return beam_loop(decoder, prec, state, logits, max_new_tokens, **common, **pick(
-                "num_beams", "length_penalty", "early_stopping", "num_return_sequences", "output_scores", "output_trace",
-                "bad_words_ids", "min_new_tokens", *automaton))
+            return beam_loop(decoder, prec, state, logits, max_new_tokens, **common, **_own(beam_loop, kw))
+        common.update(lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens)
         if samples > 1:
-            return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, num_return_sequences=samples, **common,
-                                 lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                                 **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
-        return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, **common,
-                             lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens], text_lengths=lens,
-                             **pick(*sampling, "seed", "sequence_ids", "output_logits", "output_logprobs", "top_logprobs", *constraints, *automaton, *shaping, *truncation))
+            return parallel_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, opts, num_return_sequences=samples, **common)
+        return generate_loop(decoder, prec, state, logits, tokens.long(), max_new_tokens, opts, **common)
 
 
 def run_score(model, prompt: dict, continuations, kw: dict):
@@ -1186,19 +1233,7 @@ def _raise_position_error(word: int, state: dict):
 def resolve_prompt_lengths(prompt_lengths, B: int, width: int, min_len: int = 1, name: str = "prompt_lengths") -> list:
     """``prompt_lengths`` (a sequence of B ints or an integer tensor) -> a host list of B ints in [min_len, width], or
     ValueError naming ``name``.  Host data is taken as it is; a device tensor is read back once."""
-    if isinstance(prompt_lengths, torch.Tensor):
-        if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
-            raise ValueError(f"{name} must hold integers, got a {prompt_lengths.dtype} tensor")
-        if prompt_lengths.dim() != 1:
-            raise ValueError(f"{name} must have {B} entries, got shape {tuple(prompt_lengths.shape)}")
-        lens = prompt_lengths.tolist()                     # (the one read of a device tensor)
-    else:
-        try:
-            lens = [operator.index(l) for l in prompt_lengths]
-        except TypeError:
-            raise ValueError(f"{name} must be a sequence of {B} integers or an integer tensor, got {prompt_lengths!r}") from None
-    if len(lens) != B:
-        raise ValueError(f"{name} must have {B} entries (one per row), got {len(lens)}")
+    lens = _host_ints(prompt_lengths, B, name, "row")
     for b, l in enumerate(lens):
         if l < min_len:
             raise ValueError(f"{name}[{b}] = {l}: a prompt has at least {min_len} token" + ("s" if min_len > 1 else "")
@@ -1253,20 +1288,20 @@ def session_after_turn(cached: list, block_lens: list, n_valid: list):
     return lengths, rows, [nv - 1 for nv in n_valid]
 
 
-def _loop_turn(session, rows, history, hist_lens, starts, max_new_tokens, kw):
+def _loop_turn(session, rows, history, hist_lens, starts, max_new_tokens, opts):
     """generate_loop on a session's state: ``rows`` [B, 1, V] the logits every sequence draws its first token from, ``history``
     [B, W] the conversation's text ids (mask_padding-ed), ``hist_lens`` their lengths, ``starts`` the positions the first new
     tokens take = the valid cache rows.  Returns (what generate_loop returns, n_valid per row)."""
     dev = rows.device
     pads = torch.zeros(len(starts), dtype=torch.int32, device=dev)
-    res = generate_loop(session._decoder, session._model.precision, session._state, rows, history, max_new_tokens,
+    res = generate_loop(session._decoder, session._model.precision, session._state, rows, history, max_new_tokens, opts,
                         pos_shift=session._pos_shift, lengths=list(starts), text_lengths=list(hist_lens), prompt_rows=max(starts),
-                        pad_launches=pads, **kw)
+                        pad_launches=pads)
     n, padded = session._state.pop("turn")
     return res, [n - p for p in padded]
 
 
-def _first_turn(model, prompt, state, logits, tokens, lens, prompt_rows, max_new_tokens, capacity, kw):
+def _first_turn(model, prompt, state, logits, tokens, lens, prompt_rows, max_new_tokens, capacity, opts):
     """The generate() call that opens a session: the plain ragged loop on the prefilled state (a uniform batch as a ragged one of
     equal lengths: the same Philox positions, the same bits), then the Session around what it left."""
     B, Tt = tokens.shape
@@ -1276,7 +1311,7 @@ def _first_turn(model, prompt, state, logits, tokens, lens, prompt_rows, max_new
         idx = torch.tensor([s - 1 for s in starts], dtype=torch.int64, device=logits.device)
         logits = logits[torch.arange(B, device=logits.device), idx][:, None]
     session = Session(model, state, capacity, prompt["pos_shift"], prompt["prefix_rows"])
-    res, n_valid = _loop_turn(session, logits, tokens, text_lens, starts, max_new_tokens, kw)
+    res, n_valid = _loop_turn(session, logits, tokens, text_lens, starts, max_new_tokens, opts)
     out = res[0] if isinstance(res, tuple) else res
     session._advance([tokens[b, :l] for b, l in enumerate(text_lens)], starts, [0] * B, out, n_valid)
     return (*res, session) if isinstance(res, tuple) else (res, session)
@@ -1386,15 +1421,9 @@ class Session:
         ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p``: as in generate(); the penalties count what THIS turn
         emitted — every turn starts from zero counts, and neither the prompt nor an earlier turn's output counts.
         ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: as in generate()."""
+        kw = _keywords(locals(), "self", "x", "max_new_tokens", "prompt_lengths", "prefill_chunk")
         lens = self._check_turn(x, prompt_lengths)
-        vocab = self._model.embed.weight.shape[0]
-        check_constraint_args(vocab, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                              min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, eos_token_id=eos_token_id)
-        check_logprob_args(vocab, output_logprobs=output_logprobs, top_logprobs=top_logprobs)
-        check_automaton_args(vocab, self.batch, token_automaton=token_automaton, automaton_start=automaton_start)
-        check_shape_args(vocab, self.batch, logit_bias=logit_bias, presence_penalty=presence_penalty,
-                         frequency_penalty=frequency_penalty, min_p=min_p)
-        check_truncation_args(typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        opts = loop_options(self._model.embed.weight.shape[0], self.batch, **kw)
         chunk = check_prefill_chunk(prefill_chunk)
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be a positive integer, got {max_new_tokens!r}")
@@ -1408,14 +1437,7 @@ class Session:
             try:
                 rows = self._extend(block, block_lens, chunk, True)
                 starts = [c + bl for c, bl in zip(cached, block_lens)]
-                res, n_valid = _loop_turn(self, rows, history, hist_lens, starts, max_new_tokens, dict(
-                    do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                    seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-                    output_logits=output_logits, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-                    min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, output_logprobs=output_logprobs,
-                    top_logprobs=top_logprobs, token_automaton=token_automaton, automaton_start=automaton_start,
-                    logit_bias=logit_bias, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p,
-                    typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+                res, n_valid = _loop_turn(self, rows, history, hist_lens, starts, max_new_tokens, opts)
             finally:
                 self._state["pos_max"] = max(self._cached)
             out = res[0] if isinstance(res, tuple) else res

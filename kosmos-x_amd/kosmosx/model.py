@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip as H
+from . import generation
 from .config import DecoderConfig, KosmosConfig, PerceiverConfig, Switches, VitConfig
 
 # the reference configures the root logger at import (/root/reference/kosmosx/model.py:8-10)
@@ -1453,23 +1454,10 @@ class Kosmos(nn.Module):
         they were handed.  They compose with everything sampling composes with; with ``num_beams`` > 1 or
         ``prompt_lookup_num_tokens`` > 0, or with a value out of range: ValueError naming the argument.  With the three at their
         defaults nothing changes: the same launches."""
-        from . import generation
+        kw = generation._keywords(locals(), "self", "text_tokens", "images", "max_new_tokens")
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
-        return generation.run_generate(self, self._prompt(text_tokens, images, negative_images), max_new_tokens, dict(
-            guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids, negative_prompt_lengths=negative_prompt_lengths,
-            negative_images=negative_images,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
-            eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-            output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
-            early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
-            output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
-            output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
-            automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+        return generation.run_generate(self, self._prompt(text_tokens, images, negative_images), max_new_tokens, kw)
 
     def score(self, text_tokens: torch.Tensor, images: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None,
               prompt_index=None, prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1486,7 +1474,6 @@ class Kosmos(nn.Module):
         end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
         prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
         is T + L - 1 positions.  Ids outside the vocabulary raise IndexError, as in forward()."""
-        from . import generation
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
         return generation.run_score(self, self._prompt(text_tokens, images), continuations, dict(
@@ -1661,22 +1648,10 @@ class KosmosLanguage(nn.Module):
         a negative prompt has at least one token, and with ``negative_prompt_ids`` None row b's unconditional context is its last
         prompt token, as in `transformers`; ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff``: the truncation samplers inside the
         sampler launch, as there)."""
-        from . import generation
+        kw = generation._keywords(locals(), "self", "x", "max_new_tokens")
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
-        return generation.run_generate(self, self._prompt(x), max_new_tokens, dict(
-            guidance_scale=guidance_scale, negative_prompt_ids=negative_prompt_ids, negative_prompt_lengths=negative_prompt_lengths,
-            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
-            eos_token_id=eos_token_id, pad_token_id=pad_token_id, sequence_ids=sequence_ids, eos_poll=eos_poll,
-            output_logits=output_logits, prompt_lengths=prompt_lengths, num_beams=num_beams, length_penalty=length_penalty,
-            early_stopping=early_stopping, num_return_sequences=num_return_sequences, output_scores=output_scores,
-            output_trace=output_trace, _beam_path=_beam_path, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
-            min_new_tokens=min_new_tokens, stop_sequences=stop_sequences, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, output_acceptance=output_acceptance, _draft_from=_draft_from,
-            prefill_chunk=prefill_chunk, return_session=return_session, session_capacity=session_capacity,
-            output_logprobs=output_logprobs, top_logprobs=top_logprobs, token_automaton=token_automaton,
-            automaton_start=automaton_start, logit_bias=logit_bias, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+        return generation.run_generate(self, self._prompt(x), max_new_tokens, kw)
 
     def score(self, x: torch.Tensor, continuations: torch.Tensor, *, continuation_lengths=None, prompt_index=None,
               prompt_lengths=None, output_logits=False, prefill_chunk=None):
@@ -1693,7 +1668,6 @@ class KosmosLanguage(nn.Module):
         end and columns 1..L-1 come from ONE pass over the weights with C * (L - 1) rows in which every candidate attends over its
         prompt's cache rows — shared, never appended to — and its own earlier tokens (kosmosx.generation.score_loop).  The budget
         is T + L - 1 positions.  Ids outside the vocabulary raise IndexError, as in forward()."""
-        from . import generation
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")
         return generation.run_score(self, self._prompt(x), continuations, dict(

@@ -212,7 +212,7 @@ def test_check_automaton_args_returns_the_start_states():
 
 def test_the_signatures_carry_the_keyword_only_arguments():
     from kosmosx.model import Kosmos, KosmosLanguage
-    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.generate_loop, G.parallel_loop, G.beam_loop):
+    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.loop_options, G.beam_loop):
         p = inspect.signature(fn).parameters
         for name in ("token_automaton", "automaton_start"):
             assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default is None, (fn.__qualname__, name)

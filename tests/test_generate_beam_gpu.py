@@ -212,7 +212,8 @@ def test_repeatable_and_the_default_path_is_untouched():
         state = {"max_len": 9 + 12}
         with torch.no_grad():
             logits = lm.decoder._forward_incremental(tok, state, None, lm.precision)
-            want = generation.generate_loop(lm.decoder, lm.precision, state, logits, tok.long(), 12, **extra)
+            want = generation.generate_loop(lm.decoder, lm.precision, state, logits, tok.long(), 12,
+                                            generation.loop_options(502, 2, **extra))
         assert torch.equal(got, want) and torch.equal(got, lm.generate(tok, 12, **extra))
 
 

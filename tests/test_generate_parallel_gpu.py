@@ -43,11 +43,12 @@ def _loop_pair(model, prompt, prompt_lengths, n, N, kw, chunk=None):
         else:
             first = logits[:, 0]
         first = first.repeat_interleave(n, dim=0).unsqueeze(1).clone()
-        common = dict(pos_shift=prompt["pos_shift"], output_logits=True, **kw)
-        a = G.parallel_loop(model.decoder, model.precision, state, logits, tokens.long(), N, num_return_sequences=n,
-                            lengths=None if lens is None else plens, text_lengths=lens, prompt_rows=prows, **common)
-        b = G.generate_loop(model.decoder, model.precision, rep, first, tokens.long().repeat_interleave(n, dim=0), N,
-                            lengths=[plens[i] for i in seq], text_lengths=[tlens[i] for i in seq], prompt_rows=T, **common)
+        opts = G.loop_options(logits.shape[2], B, output_logits=True, **kw)   # (nothing per row among them: the same for both)
+        a = G.parallel_loop(model.decoder, model.precision, state, logits, tokens.long(), N, opts, num_return_sequences=n,
+                            pos_shift=prompt["pos_shift"], lengths=None if lens is None else plens, text_lengths=lens, prompt_rows=prows)
+        b = G.generate_loop(model.decoder, model.precision, rep, first, tokens.long().repeat_interleave(n, dim=0), N, opts,
+                            pos_shift=prompt["pos_shift"], lengths=[plens[i] for i in seq], text_lengths=[tlens[i] for i in seq],
+                            prompt_rows=T)
         assert "prefix" in state and "prefix" not in rep
         assert tuple(state["prefix"]["ktail"].shape) == (state["kcache"].shape[0], B * n, state["kcache"].shape[2], N, 64)
         assert state["kcache"].shape[1] == B and rep["kcache"].shape[1] == B * n

@@ -145,9 +145,10 @@ def test_the_signatures_carry_the_keyword_only_arguments():
     from kosmosx import ops
     from kosmosx.model import Kosmos, KosmosLanguage
     names = dict(guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None)
-    for fn in (Kosmos.generate, KosmosLanguage.generate, G.generate_loop):
+    # (the loop takes the scale alone: run_generate turns the negatives into rows)
+    for fn, pinned in ((Kosmos.generate, names), (KosmosLanguage.generate, names), (G.loop_options, dict(guidance_scale=1.0))):
         p = inspect.signature(fn).parameters
-        for name, default in names.items():
+        for name, default in pinned.items():
             assert p[name].kind is inspect.Parameter.KEYWORD_ONLY, (fn.__qualname__, name)
             assert p[name].default is None if default is None else p[name].default == 1.0, (fn.__qualname__, name)
     p = inspect.signature(Kosmos.generate).parameters["negative_images"]

@@ -75,7 +75,7 @@ def test_the_three_generate_signatures_carry_the_keyword_only_arguments():
         p = inspect.signature(fn).parameters
         for name, default in (("output_logprobs", False), ("top_logprobs", 0)):
             assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default is default, (fn.__qualname__, name)
-    p = inspect.signature(G.generate_loop).parameters
+    p = inspect.signature(G.loop_options).parameters
     assert p["output_logprobs"].default is False and p["top_logprobs"].default == 0
 
 

@@ -116,7 +116,7 @@ def test_generate_with_the_keywords_reaches_the_device_check():
 
 def test_the_signatures_carry_the_keyword_only_arguments():
     from kosmosx.model import Kosmos, KosmosLanguage
-    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.generate_loop, G.parallel_loop):
+    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.loop_options):
         p = inspect.signature(fn).parameters
         for name, default in zip(NAMES, (None, 0.0, 0.0, 0.0)):
             assert p[name].kind is inspect.Parameter.KEYWORD_ONLY, (fn.__qualname__, name)

@@ -245,7 +245,7 @@ def test_generate_with_the_keywords_reaches_the_device_check():
 def test_the_signatures_carry_the_keyword_only_arguments():
     from kosmosx import ops
     from kosmosx.model import Kosmos, KosmosLanguage
-    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.generate_loop, G.check_truncation_args, ops.sample_logits):
+    for fn in (Kosmos.generate, KosmosLanguage.generate, G.Session.generate, G.loop_options, G.check_truncation_args, ops.sample_logits):
         p = inspect.signature(fn).parameters
         for name, default in zip(NAMES, (1.0, 0.0, 0.0)):
             assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, (fn.__qualname__, name)
