@@ -1411,6 +1411,81 @@ typedef struct {
 int kx_guidance_logits(const kx_guidance_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-row sampling options: a batch of unlike requests in one launch (added within ABI 7: two structs and three functions are
+ * appended; no existing layout moves and the kx_struct_id list is unchanged — kx_sample_rows_args carries its own struct_bytes,
+ * which kx_sample_logits_rows checks, as kx_truncate_args does; kx_sample_args and kx_shape_args are untouched — so kx_version()
+ * stays 7).
+ *
+ * kx_sample_row: what one row of the batch asked of the sampler — everything kx_sample_args and kx_truncate_args carry once per
+ * launch.  56 bytes, 8-byte aligned; the table of a launch is B of them, consecutive.
+ *
+ * kx_sample_rows_pack: `in` [B] host records -> `out` [B] host records ready for upload, and the launch summary in *flags_out.
+ * Host only and pure: it touches no device and makes no runtime call.  Every record is validated with the rules of
+ * kx_sample_logits, kx_sample_logits_min_p and kx_sample_logits_truncate — temperature >= 0, top_p > 0, repetition_penalty > 0,
+ * min_p in [0, 1], typical_p in (0, 1], epsilon_cutoff and eta_cutoff in [0, 1) (NaN refused everywhere), max_new >= 0 — else
+ * KX_ERR_INVALID_ARG with a message that names the row and the field, and *flags_out is not written.  out[b] is in[b] with
+ * log_min_p = (float)log((double)min_p), the expression kx_sample_logits_min_p evaluates (0 where min_p == 0: off), and the
+ * reserved word 0.  Flags: KX_SAMPLE_ROWS_PENALTY (bit 0) some row has repetition_penalty != 1; KX_SAMPLE_ROWS_BUDGET (bit 1)
+ * some row has max_new > 0.  in == out is allowed; B >= 1, V >= 1 (the vocabulary the table is meant for).
+ *
+ * kx_sample_logits_rows: kx_sample_logits_truncate (positions == NULL: the uniform form, advance unused; positions != NULL: the
+ * ragged form) with row b sampled under rows->table[b] instead of the launch's scalars: greedy or not (do_sample == 0 or
+ * temperature == 0: greedy, every filter ignored), repetition penalty, temperature, top-k, top-p, min-p through log_min_p,
+ * typical-p, epsilon, eta — the same stages in the same order over the same passes, LDS and 1024-thread workgroup — and seed as
+ * the row's Philox key; the counter stays (position, sequence id, i >> 2, 0).  Row b's outputs are bit for bit those of a one-row
+ * launch of the scalar entry points with the record's values.  One more instantiation of the sampler's kernel per form; its
+ * workgroup reads its record through a workgroup-uniform address, so every branch on a record value is uniform.
+ *   rows->table   DEVICE memory, B records as kx_sample_rows_pack wrote them; rows->flags: the pack's.
+ *   The scalar sampling fields of args (do_sample, temperature, top_k, top_p, repetition_penalty, seed) are ignored — not read,
+ *   not validated.  Everything else in args means what it means in kx_sample_logits.
+ * Rules:
+ *   1. the launch carries the history bitmap in LDS iff flag bit 0 is set, history != NULL and hist_len > 0; then V <= 327680
+ *      (KX_ERR_UNSUPPORTED), as for kx_sample_logits with a penalty;
+ *   2. a record with repetition_penalty != 1 in a launch without the bitmap is read as 1; in a launch with it a record of exactly 1
+ *      divides and multiplies by 1 (exact).  No record value ever decides whether LDS is addressed;
+ *   3. flag bit 1 with finished == NULL is KX_ERR_INVALID_ARG; with flag bit 1 clear every max_new is read as 0;
+ *   4. a row with max_new > 0 becomes finished by the launch in which out_col + 1 >= max_new (out_col counts the launches of the
+ *      call whether or not out_tokens is given).  The token of that launch is emitted normally; from the next launch on the row
+ *      emits pad_id, as a row that drew the EOS does;
+ *   5. record values are compared and used in arithmetic only, never as an index; top_k outside (0, V) is off.  A malformed table
+ *      changes what is sampled, never what is addressed;
+ *   6. all of kx_sample_logits' guarantees carry over: a row's outputs do not depend on B, on its row index or on execution
+ *      order, and two calls give identical bits.  Finished rows and rows without a candidate behave as in kx_sample_logits.
+ * Argument errors (KX_ERR_INVALID_ARG, nothing launched): a null rows, a stale struct_bytes, a null table, flags beyond the two
+ * bits, a negative advance; then kx_sample_logits' own.  Never allocates, never synchronises. */
+typedef struct {
+  int32_t do_sample;                          /* 0: greedy */
+  float temperature;                          /* >= 0; 0: greedy */
+  int32_t top_k;                              /* outside (0, V): off */
+  float top_p;                                /* > 0; >= 1: off */
+  float repetition_penalty;                   /* > 0; 1: off */
+  float min_p;                                /* [0, 1], 0 = off */
+  float log_min_p;                            /* filled by kx_sample_rows_pack */
+  float typical_p;                            /* (0, 1], 1 = off */
+  float epsilon_cutoff;                       /* [0, 1), 0 = off */
+  float eta_cutoff;                           /* [0, 1), 0 = off */
+  int32_t max_new;                            /* the row's token budget, 0 = none */
+  int32_t reserved;
+  uint64_t seed;                              /* the row's Philox key */
+} kx_sample_row;
+#define KX_SAMPLE_ROWS_PENALTY 1u
+#define KX_SAMPLE_ROWS_BUDGET 2u
+typedef struct {
+  uint32_t struct_bytes;                      /* = sizeof(kx_sample_rows_args) of the caller ("stale binding" otherwise) */
+  uint32_t flags;                             /* kx_sample_rows_pack's flags_out */
+  const kx_sample_row* table;                 /* [B], device memory */
+} kx_sample_rows_args;
+int kx_sample_rows_pack(const kx_sample_row* in, int64_t B, int64_t V, kx_sample_row* out, uint32_t* flags_out);
+int kx_sample_logits_rows(const kx_sample_args* args, int32_t* positions, int64_t advance, const kx_sample_rows_args* rows, void* stream);
+
+/* kx_shape_logits_rows: kx_shape_logits with row b's penalties read from two device fp32 [B] arrays: f = frequency_rows[b] and
+ * p = presence_rows[b] in the same three single fp32 operations (its rule 4), never contracted.  Either array may be NULL: the
+ * scalar of args for every row; with both NULL it IS kx_shape_logits(args, stream).  counts is required when an array is given
+ * (KX_ERR_INVALID_ARG naming counts); the values of an array are used in arithmetic only — the caller passes finite ones, as it
+ * passes finite scalars.  Nothing else about the launch, its ownership rules or its limits changes. */
+int kx_shape_logits_rows(const kx_shape_args* args, const float* frequency_rows, const float* presence_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process kernel timing (bench.py's roofline leg; the reference's own ad-hoc equivalents are the
  * wall-clock fences of /root/reference/tests/test_benchmarking.py:68-95,192-196).
  * When enabled, every kernel launch made through this library is bracketed by hipEventRecord on

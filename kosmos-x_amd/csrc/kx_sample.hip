@@ -152,9 +152,18 @@ __device__ bool radix_select(const SampleParams& a, const float* __restrict__ ro
 // three cut-offs as the ABI carries them) and up to three more stages after min-p — typical-p, epsilon, eta — each over what the
 // stage before it kept.  The kept set stays a conjunction of per-element predicates (Kept), so every pass recomputes membership
 // from x alone and nothing per element is stored.
+// ROWS (kx_sample_logits_rows): one more kernel argument, last of the pack (Rows: the device table of one kx_sample_row per row and
+// whether the launch honours the budgets).  The workgroup reads its row's record through a workgroup-uniform address and runs the
+// stages of the Trunc instantiation with the record's values in place of the launch's scalars — greedy or not, r, T, k, p, min-p's
+// lm, the three cut-offs, the seed — so every branch on a record value is uniform across the workgroup and no barrier sits in
+// divergent code.  Whether the bitmap is built and read stays the launch's own a.pen: a record only supplies the r it is used with.
 struct RaggedPos { int* positions; int advance; };
 struct MinP { float lm; };
 struct Trunc { float lm, typical, epsilon, eta; int minp; };
+struct Rows { const kx_sample_row* table; int budget; };
+template <bool SECOND, typename T> __device__ __forceinline__ const T& pick(const T& a, const T& b) {
+  if constexpr (SECOND) return b; else return a;
+}
 struct Kept {
   unsigned tau;                  // rules 1-4 and min-p: key(x) >= tau
   int typ; float mu; unsigned dkey;        // typical-p (typ != 0): dist_key(x) >= dkey
@@ -195,11 +204,28 @@ template <typename A, typename... Rest> __device__ __forceinline__ const auto& l
 template <typename T, typename... R> constexpr bool pack_has = (std::is_same_v<T, R> || ...);
 
 template <typename... R>
-__global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const R... r) {
+__global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a0, const R... r) {
   constexpr bool RAGGED = pack_has<RaggedPos, R...>;    // (first of the pack)
   constexpr bool MINP = pack_has<MinP, R...>;           // (last of the pack)
-  constexpr bool TRUNC = pack_has<Trunc, R...>;         // (last of the pack)
+  constexpr bool ROWS = pack_has<Rows, R...>;           // (last of the pack)
+  constexpr bool TRUNC = pack_has<Trunc, R...> || ROWS; // (last of the pack; ROWS: the record's cut-offs)
   using Owner = void(R...);
+  // ROWS: the launch's parameters with the row's record over the scalar sampling fields; otherwise `a` IS the kernel argument
+  [[maybe_unused]] SampleParams ar;
+  [[maybe_unused]] Trunc tr;
+  [[maybe_unused]] int budget = 0;
+  if constexpr (ROWS) {
+    const Rows& rw = last_arg(r...);
+    const kx_sample_row rec = rw.table[blockIdx.x];     // (uniform: one record, read by every thread)
+    ar = a0;
+    ar.greedy = (!rec.do_sample || rec.temperature == 0.0f) ? 1 : 0;
+    ar.T = rec.temperature; ar.k = rec.top_k; ar.p = rec.top_p; ar.seed = rec.seed;
+    ar.r = a0.pen ? rec.repetition_penalty : 1.0f;      // (a launch without the bitmap reads every r as 1)
+    tr.minp = rec.min_p != 0.0f;
+    tr.lm = rec.log_min_p; tr.typical = rec.typical_p; tr.epsilon = rec.epsilon_cutoff; tr.eta = rec.eta_cutoff;
+    budget = rw.budget ? rec.max_new : 0;
+  }
+  const SampleParams& a = pick<ROWS>(a0, ar);
   __shared__ unsigned long long hist[BINS];
   __shared__ unsigned long long red[SW];
   __shared__ unsigned long long gsum[BINS / 64];
@@ -274,7 +300,7 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
       }
       [[maybe_unused]] Kept s{tau, 0, 0.f, 0u, 0ull, kmax};
       if constexpr (TRUNC) {
-        const Trunc& t = last_arg(r...);
+        const Trunc& t = [&]() -> const Trunc& { if constexpr (ROWS) return tr; else return last_arg(r...); }();
         if (t.minp) {                                   // min-p, as above
           const unsigned km = f2key(m + t.lm);
           s.tau = km > tau ? km : tau;
@@ -355,6 +381,9 @@ __global__ __launch_bounds__(SB) void sample_kernel(const SampleParams a, const 
       tok = 0xffffffffu - (unsigned)gbest;
     }
     if (!fin && a.eos >= 0 && tok == a.eos) fin = 1;
+    if constexpr (ROWS) {                               // the row's budget: this launch wrote its max_new-th token
+      if (budget > 0 && a.out_col + 1 >= (long long)budget) fin = 1;
+    }
   }
   if (tid == 0) {
     a.next[b] = tok;
@@ -436,7 +465,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const long long* __rest
 }  // namespace
 
 static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t advance, void* stream, const float* log_min_p = nullptr,
-                       const Trunc* trunc = nullptr) {
+                       const Trunc* trunc = nullptr, const kx_sample_rows_args* rows = nullptr) {
   KX_REQUIRE(args != nullptr, "kx_sample_logits: null args");
   KX_REQUIRE(args->struct_bytes == sizeof(kx_sample_args),
              "kx_sample_logits: stale binding — caller declares kx_sample_args as %u bytes, this library (ABI %d) as %zu",
@@ -446,10 +475,13 @@ static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t a
   KX_REQUIRE(args->B >= 1 && args->B <= 0x7fffffffll, "kx_sample_logits: B=%lld must be >= 1", (long long)args->B);
   KX_REQUIRE(args->V >= 1, "kx_sample_logits: V=%lld must be >= 1", (long long)args->V);
   KX_REQUIRE(args->ld >= args->V, "kx_sample_logits: ld=%lld is smaller than V=%lld", (long long)args->ld, (long long)args->V);
-  KX_REQUIRE(args->temperature >= 0.0f, "kx_sample_logits: temperature=%g must be >= 0", (double)args->temperature);
-  KX_REQUIRE(args->top_p > 0.0f, "kx_sample_logits: top_p=%g must be > 0", (double)args->top_p);
-  KX_REQUIRE(args->repetition_penalty > 0.0f, "kx_sample_logits: repetition_penalty=%g must be > 0",
+  // (rows: the scalar sampling fields are ignored — the table's records were validated by kx_sample_rows_pack)
+  KX_REQUIRE(rows || args->temperature >= 0.0f, "kx_sample_logits: temperature=%g must be >= 0", (double)args->temperature);
+  KX_REQUIRE(rows || args->top_p > 0.0f, "kx_sample_logits: top_p=%g must be > 0", (double)args->top_p);
+  KX_REQUIRE(rows || args->repetition_penalty > 0.0f, "kx_sample_logits: repetition_penalty=%g must be > 0",
              (double)args->repetition_penalty);
+  KX_REQUIRE(!rows || !(rows->flags & KX_SAMPLE_ROWS_BUDGET) || args->finished != nullptr,
+             "kx_sample_logits_rows: null finished with a row budget in the table (flags bit 1)");
   KX_REQUIRE(args->hist_len >= 0 && args->hist_len <= 0x7fffffffll, "kx_sample_logits: hist_len=%lld must be >= 0",
              (long long)args->hist_len);
   KX_REQUIRE(args->history == nullptr || args->hist_ld > args->hist_len,
@@ -467,7 +499,8 @@ static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t a
   p.logits = args->logits; p.ld = args->ld; p.V = (int)args->V;
   p.greedy = (!args->do_sample || args->temperature == 0.0f) ? 1 : 0;
   p.T = args->temperature; p.p = args->top_p; p.r = args->repetition_penalty; p.k = args->top_k;
-  p.pen = (args->repetition_penalty != 1.0f && args->history != nullptr && args->hist_len > 0) ? 1 : 0;
+  const bool penalty = rows ? (rows->flags & KX_SAMPLE_ROWS_PENALTY) != 0 : args->repetition_penalty != 1.0f;
+  p.pen = (penalty && args->history != nullptr && args->hist_len > 0) ? 1 : 0;
   if (p.pen && args->V > KX_SAMPLE_MAX_V_PENALTY) {
     kx_set_error("kx_sample_logits: repetition_penalty with V=%lld exceeds %lld (the history bitmap is kept in LDS)",
                  (long long)args->V, KX_SAMPLE_MAX_V_PENALTY);
@@ -482,7 +515,13 @@ static int sample_impl(const kx_sample_args* args, int32_t* positions, int64_t a
   p.kept_count = args->kept_count; p.keep_mask = args->keep_mask;
   const size_t lds = p.pen ? (size_t)((args->V + 31) / 32) * 4 : 0;
   KxProfScope prof(KX_K_MISC, args->B, args->V, 0, (hipStream_t)stream);
-  if (trunc && positions)
+  if (rows && positions)
+    hipLaunchKernelGGL((sample_kernel<RaggedPos, Rows>), dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+                       RaggedPos{(int*)positions, (int)advance}, Rows{rows->table, (rows->flags & KX_SAMPLE_ROWS_BUDGET) ? 1 : 0});
+  else if (rows)
+    hipLaunchKernelGGL(sample_kernel<Rows>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
+                       Rows{rows->table, (rows->flags & KX_SAMPLE_ROWS_BUDGET) ? 1 : 0});
+  else if (trunc && positions)
     hipLaunchKernelGGL((sample_kernel<RaggedPos, Trunc>), dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p,
                        RaggedPos{(int*)positions, (int)advance}, *trunc);
   else if (trunc) hipLaunchKernelGGL(sample_kernel<Trunc>, dim3((unsigned)args->B), dim3(SB), lds, (hipStream_t)stream, p, *trunc);
@@ -538,6 +577,21 @@ extern "C" int kx_sample_logits_truncate(const kx_sample_args* args, int32_t* po
   t.lm = t.minp ? (float)log((double)trunc->min_p) : 0.0f;
   t.typical = trunc->typical_p; t.epsilon = trunc->epsilon_cutoff; t.eta = trunc->eta_cutoff;
   return sample_impl(args, positions, positions ? advance : 0, stream, nullptr, &t);
+}
+
+// One launch of the Rows instantiation (either form), whatever the records hold; the pack function lives in kx_sample_rows.hip.
+extern "C" int kx_sample_logits_rows(const kx_sample_args* args, int32_t* positions, int64_t advance, const kx_sample_rows_args* rows,
+                                     void* stream) {
+  KX_REQUIRE(rows != nullptr, "kx_sample_logits_rows: null rows");
+  KX_REQUIRE(rows->struct_bytes == sizeof(kx_sample_rows_args),
+             "kx_sample_logits_rows: stale binding — caller declares kx_sample_rows_args as %u bytes, this library (ABI %d) as %zu",
+             (unsigned)rows->struct_bytes, KX_ABI_VERSION, sizeof(kx_sample_rows_args));
+  KX_REQUIRE(rows->table != nullptr, "kx_sample_logits_rows: null table");
+  KX_REQUIRE((rows->flags & ~(KX_SAMPLE_ROWS_PENALTY | KX_SAMPLE_ROWS_BUDGET)) == 0, "kx_sample_logits_rows: flags=%#x beyond bits 0 and 1",
+             (unsigned)rows->flags);
+  KX_REQUIRE(positions == nullptr || (advance >= 0 && advance <= 0x7fffffffll), "kx_sample_logits_rows: advance=%lld must be >= 0",
+             (long long)advance);
+  return sample_impl(args, positions, positions ? advance : 0, stream, nullptr, nullptr, rows);
 }
 
 // span == 1: kx_step_prepare's launch.  span > 1: B counts the rows, `span` consecutive ones per entry of positions (see the kernel).

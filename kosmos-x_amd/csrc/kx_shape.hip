@@ -22,6 +22,7 @@ struct ShapeParams {
   float* logits; long long ld; int V;
   const int* bias_off; const int* bias_ids; const float* bias_val; int E;
   int* counts; float f, p;
+  const float* f_rows; const float* p_rows;             // kx_shape_logits_rows: row b's own f / p (NULL: the scalar)
   const long long* last_token; const unsigned char* finished;
   int slices;
 };
@@ -70,15 +71,17 @@ __global__ __launch_bounds__(HB) void shape_kernel(const ShapeParams a) {
     if (t >= v0 && t < v0 + n) last = (int)(t - v0);
   }
   int* __restrict__ cnt = a.counts + (long long)b * a.V + v0;
+  const float f = a.f_rows ? a.f_rows[b] : a.f;         // (uniform: one word per array, read by every thread)
+  const float p = a.p_rows ? a.p_rows[b] : a.p;
   for (int i = tid; i < n; i += HB) {
     int c = cnt[i];
     if (i == last) { c += 1; cnt[i] = c; }
     if (c > 0) {
       const float l = row[i];
       if (l > ninf) {
-        const float t = a.f * (float)c;
+        const float t = f * (float)c;
         const float u = l - t;
-        row[i] = u - a.p;
+        row[i] = u - p;
       }
     }
   }
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(HB) void shape_kernel(const ShapeParams a) {
 
 }  // namespace
 
-extern "C" int kx_shape_logits(const kx_shape_args* args, void* stream) {
+static int shape_impl(const kx_shape_args* args, const float* frequency_rows, const float* presence_rows, void* stream) {
   KX_REQUIRE(args != nullptr, "kx_shape_logits: null args");
   KX_REQUIRE(args->struct_bytes == sizeof(kx_shape_args),
              "kx_shape_logits: stale binding — caller declares kx_shape_args as %u bytes, this library (ABI %d) as %zu",
@@ -119,15 +122,25 @@ extern "C" int kx_shape_logits(const kx_shape_args* args, void* stream) {
   KX_REQUIRE(args->presence - args->presence == 0.0f, "kx_shape_logits: presence=%g must be finite", (double)args->presence);
   KX_REQUIRE(args->counts != nullptr || (args->frequency == 0.0f && args->presence == 0.0f),
              "kx_shape_logits: null counts with frequency=%g, presence=%g", (double)args->frequency, (double)args->presence);
+  KX_REQUIRE(args->counts != nullptr || (frequency_rows == nullptr && presence_rows == nullptr),
+             "kx_shape_logits_rows: null counts with per-row penalties");
   KX_REQUIRE(args->counts != nullptr || args->bias_off != nullptr, "kx_shape_logits: neither bias_off nor counts: nothing to shape");
   ShapeParams p;
   p.logits = args->logits; p.ld = args->ld; p.V = (int)args->V;
   p.bias_off = args->bias_off; p.bias_ids = args->bias_ids; p.bias_val = args->bias_val; p.E = (int)args->n_bias;
   p.counts = args->counts; p.f = args->frequency; p.p = args->presence;
+  p.f_rows = frequency_rows; p.p_rows = presence_rows;
   p.last_token = (const long long*)args->last_token; p.finished = args->finished;
   p.slices = (int)slices;
   KxProfScope prof(KX_K_MISC, args->B, args->V, 4, (hipStream_t)stream);
   hipLaunchKernelGGL(shape_kernel, dim3((unsigned)(args->B * slices)), dim3(HB), 0, (hipStream_t)stream, p);
   KX_CHECK_LAUNCH("kx_shape_logits");
   return KX_OK;
+}
+
+extern "C" int kx_shape_logits(const kx_shape_args* args, void* stream) { return shape_impl(args, nullptr, nullptr, stream); }
+
+// Row b's f / p from the arrays (either may be NULL: the scalar); both NULL: kx_shape_logits' launch.
+extern "C" int kx_shape_logits_rows(const kx_shape_args* args, const float* frequency_rows, const float* presence_rows, void* stream) {
+  return shape_impl(args, frequency_rows, presence_rows, stream);
 }

@@ -231,6 +231,30 @@ class GuidanceArgs(C.Structure):
         self.struct_bytes = C.sizeof(type(self))
 
 
+class SampleRow(C.Structure):
+    """kx_sample_row: one row's sampling options, 56 bytes; an array of B of them is the table kx_sample_rows_pack fills and
+    kx_sample_logits_rows reads from device memory.  The defaults are the filters switched off (greedy, no budget)."""
+    _fields_ = [("do_sample", i32), ("temperature", f32), ("top_k", i32), ("top_p", f32), ("repetition_penalty", f32), ("min_p", f32),
+                ("log_min_p", f32), ("typical_p", f32), ("epsilon_cutoff", f32), ("eta_cutoff", f32), ("max_new", i32),
+                ("reserved", i32), ("seed", C.c_uint64)]
+
+    def __init__(self, **k):
+        super().__init__(**dict(dict(temperature=1.0, top_p=1.0, repetition_penalty=1.0, typical_p=1.0), **k))
+
+
+SAMPLE_ROWS_PENALTY, SAMPLE_ROWS_BUDGET = 1, 2          # kx_sample_rows_pack's flags
+
+
+class SampleRowsArgs(C.Structure):
+    """kx_sample_rows_args; struct_bytes is filled in at construction ("stale binding" check of kx_sample_logits_rows — like
+    kx_truncate_args the struct has no kx_struct_id)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("table", vp)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_bytes = C.sizeof(type(self))
+
+
 KERNEL_KINDS = ["gemm_bf16_128x128", "gemm_bf16_64x64", "gemm_f32_128x128", "gemm_f32_64x64", "layernorm",
                 "attn_bf16", "attn_f32", "embed", "misc", "gemm_bf16_160x128", "gemm_bf16_256x128_phased",
                 "gemm_bf16_256x256_phased",
@@ -282,6 +306,9 @@ SYMBOLS = {
     "kx_sample_logits_min_p": (C.c_int, [C.POINTER(SampleArgs), vp, i64, f32, vp]),
     "kx_sample_logits_truncate": (C.c_int, [C.POINTER(SampleArgs), vp, i64, C.POINTER(TruncateArgs), vp]),
     "kx_guidance_logits": (C.c_int, [C.POINTER(GuidanceArgs), vp]),
+    "kx_sample_rows_pack": (C.c_int, [C.POINTER(SampleRow), i64, i64, C.POINTER(SampleRow), C.POINTER(C.c_uint32)]),
+    "kx_sample_logits_rows": (C.c_int, [C.POINTER(SampleArgs), vp, i64, C.POINTER(SampleRowsArgs), vp]),
+    "kx_shape_logits_rows": (C.c_int, [C.POINTER(ShapeArgs), vp, vp, vp]),
     "kx_attention_decode_block": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp]),
     "kx_decoder_decode_step_block": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp,
                                                vp, vp, vp, vp, i64, vp, i32, vp, C.c_size_t, i32, vp, vp]),

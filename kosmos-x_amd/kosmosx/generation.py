@@ -77,7 +77,15 @@ arithmetic, then three single fp32 operations an outside reference restates bit 
 the sampler and every row editor see the first B rows; one device-to-device copy feeds the sampled token to both rows.  With the scale
 at 1.0: no buffer, no launch, no further host read, nothing doubled.
 
-Not offered: guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
+Per-row options (``row_options``; generate_loop and everything that runs it): B dicts of overrides, resolved against the call's own
+keywords by check_row_options into one table (LoopOptions.rows).  The table is packed by the library (kx_sample_rows_pack), uploaded
+once, and read by one more instantiation of the sampler's kernel (kx_sample_logits_rows): its workgroup takes greedy-or-not, the
+repetition penalty, temperature, top-k, top-p, min-p, the three cut-offs and the Philox seed from its row's record, so row b of a
+mixed batch gets the bits of a call of its own.  Presence and frequency penalties travel as two fp32 [B] arrays
+(kx_shape_logits_rows); a row's ``max_new_tokens`` is a budget the sampler launch itself enforces through ``finished``.  Without the
+keyword, or with B empty dicts: no buffer, no upload, the entry points above.
+
+Not offered: per-row ``eos_token_id``, constraints and stop sequences, row options with beams or prompt lookup; guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
 image, log-probs of the guided distribution; the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
 turn; the truncation samplers with beams or prompt lookup, ``min_tokens_to_keep`` above 1, log-probs of the truncated distribution; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
 that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
@@ -135,24 +143,25 @@ class LoopOptions:
     shape: object                       # check_shape_args' dict, or None
     sampler: dict                       # what the sampler launch takes beyond its old arguments: min_p, check_truncation_args' keywords
     guidance: object                    # check_guidance_args' scale, or None
+    rows: object = None                 # check_row_options' table: B dicts holding every ROW_KEYS entry resolved, or None
 
     @classmethod
-    def resolved(cls, kw: dict, cons, starts, shape, truncation: dict, guide):
+    def resolved(cls, kw: dict, cons, starts, shape, truncation: dict, guide, rows=None):
         """From the keyword arguments by name and what the checks returned for them."""
         min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
         return cls(**{f.name: kw[f.name] for f in dataclasses.fields(cls) if f.name in kw}, constraints=cons, shape=shape,
                    automaton=None if starts is None else (kw["token_automaton"], starts), sampler={**min_p, **truncation},
-                   guidance=None if guide is None else guide["scale"])
+                   guidance=None if guide is None else guide["scale"], rows=rows)
 
 
 def loop_options(vocab: int, batch: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
                  eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, output_logprobs=False, top_logprobs=0,
                  token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                 guidance_scale=1.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0) -> LoopOptions:
+                 guidance_scale=1.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None, max_new_tokens=None) -> LoopOptions:
     """The plain loop's keyword arguments -> the LoopOptions generate_loop takes, or the ValueError of the first check that refuses
-    one: check_constraint_args, check_logprob_args, check_automaton_args, check_shape_args, check_truncation_args, in this order
-    (then the scale through check_guidance_args); host only.  ``vocab``: the model's; ``batch``: the rows B the per-row values are
+    one: check_constraint_args, check_logprob_args, check_automaton_args, check_shape_args, check_truncation_args,
+    check_row_options, in this order (then the scale through check_guidance_args); host only.  ``vocab``: the model's; ``batch``: the rows B the per-row values are
     given for.  What generate_loop does with each of them:
     Constraints (check_constraint_args): kx_constrain_logits runs on the row immediately before each sampler launch.  Its
     history is ``prompt_tokens`` followed by the generated tokens — the TEXT ids only: spliced image rows contribute no ids, so
@@ -196,14 +205,28 @@ def loop_options(vocab: int, batch: int, *, do_sample=False, temperature=1.0, to
     draws at the conditional row's Philox position with ``sequence_ids[b]``: the stream of the unguided ragged call.  No host read is
     added: the error word covers all 2B rows and is read where it already is.  ``output_logits`` keeps the conditional rows' raw
     logits and, returned directly after them, the unconditional rows', both taken before the launch; ``output_logprobs`` reads the
-    conditional rows' raw logits.  ``pad_launches`` (sessions) is refused.  With the scale at 1.0 nothing of this happens."""
+    conditional rows' raw logits.  ``pad_launches`` (sessions) is refused.  With the scale at 1.0 nothing of this happens.
+    ``row_options`` (check_row_options; B dicts, one per row of this call, each naming any of ROW_KEYS; ``max_new_tokens``: the call's
+    own, the budgets' upper bound — None: not checked here): the resolved table travels as ``LoopOptions.rows``.  Before the first
+    step the loop packs and uploads it once (ops.SampleRowTable), allocates ``history`` when any row has a repetition penalty and
+    the counts when any row has a presence or frequency penalty, and uploads those two penalties as fp32 [B] arrays.  Per token the
+    launch list is the one above, the sampler entry point being kx_sample_logits_rows and — only when the shaping launch runs and a
+    row has a penalty — the shaping one kx_shape_logits_rows: row b gets what a call of its own with its resolved scalars gets, bit
+    for bit, at the Philox address (row b's seed; position, ``sequence_ids[b]``).  A row with a budget m_b is finished by the sampler
+    launch that writes its m_b-th token and emits ``pad_token_id`` from then on, exactly like a row that drew an EOS: budgets make
+    the loop able to finish, so the stop poll runs; ``pad_launches`` then counts m_b valid tokens with no further bookkeeping, and
+    the ``skip`` snapshot keeps the log-prob slots behind the budget at 0.0 / -1.  With an automaton a spent budget is told from
+    a dead end by the launch's kept count (0: no candidate), also when both fall into one launch.  With ``row_options`` the presence
+    and frequency penalties are the rows' resolved ones alone: the shaping launch runs for a bias or a row's penalty, never for the
+    call's scalar that every row overrode.  None, or B empty dicts: no buffer, no upload, the entry points above."""
     kw = _keywords(locals(), "vocab", "batch")
     cons = check_constraint_args(vocab, **_own(check_constraint_args, kw))
     check_logprob_args(vocab, **_own(check_logprob_args, kw))
     starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
     shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
     truncation = check_truncation_args(**_own(check_truncation_args, kw))
-    return LoopOptions.resolved(kw, cons, starts, shape, truncation, check_guidance_args(batch, **_own(check_guidance_args, kw)))
+    rows = check_row_options(vocab, batch, **_own(check_row_options, kw))
+    return LoopOptions.resolved(kw, cons, starts, shape, truncation, check_guidance_args(batch, **_own(check_guidance_args, kw)), rows)
 
 
 def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
@@ -229,7 +252,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     [B, n] token_logprobs and, k > 0, the fp32 [B, n, k] top_logprobs and int64 [B, n, k] top_ids."""
     eos_token_id, pad_token_id, eos_poll, sequence_ids = opts.eos_token_id, opts.pad_token_id, opts.eos_poll, opts.sequence_ids
     output_logits, output_logprobs, k = opts.output_logits, opts.output_logprobs, int(opts.top_logprobs)
-    cons, shape, guide = opts.constraints, opts.shape, opts.guidance
+    cons, shape, guide, rows = opts.constraints, opts.shape, opts.guidance, opts.rows
     token_automaton, auto = opts.automaton or (None, None)
     R, T, V = logits.shape                                                # R: the rows of the step; B: the rows of the sampler
     B = R if guide is None else R // 2
@@ -240,15 +263,21 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
     if gathered:
         T = prompt_rows
     dev = logits.device
-    can_finish = eos_token_id is not None or (cons is not None and cons["stop"]) or auto is not None
-    shaping = shape is not None and shape["launch"]
+    budgets = rows is not None and any(r["max_new_tokens"] for r in rows)
+    row_penalties = rows is not None and any(r["presence_penalty"] != 0.0 or r["frequency_penalty"] != 0.0 for r in rows)
+    can_finish = eos_token_id is not None or (cons is not None and cons["stop"]) or auto is not None or budgets
+    if rows is None:
+        shaping = shape is not None and shape["launch"]
+    else:                                                                 # the penalties are the rows' own: the call's scalars are resolved into them
+        shaping = row_penalties or (shape is not None and shape["bias"] is not None)
     out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
     nxt = torch.empty(R, dtype=torch.int64, device=dev)
     finished = torch.zeros(B, dtype=torch.uint8, device=dev)
     history = None
     prompt_tokens = prompt_tokens[:B]                                     # (guidance: the histories see the conditional prompts)
     Tt = prompt_tokens.shape[1]
-    if float(opts.repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"]):
+    if (float(opts.repetition_penalty) != 1.0 or (cons is not None and cons["reads_history"])
+            or (rows is not None and any(r["repetition_penalty"] != 1.0 for r in rows))):
         history = torch.empty((B, Tt + max_new_tokens), dtype=torch.int64, device=dev)           # (the sampler appends with r == 1 too)
         history[:, :Tt] = prompt_tokens
     if sequence_ids is not None:
@@ -287,15 +316,26 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         states = (torch.tensor(auto, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
         not_eos = -1 if eos_token_id is None else int(eos_token_id)
     if shaping:                                                           # the one upload: the bias table; the counts start at zero
-        bias = ops.BiasTable(shape["bias"], dev) if shape["bias"] is not None else None
-        penalised = shape["frequency"] != 0.0 or shape["presence"] != 0.0
+        bias = ops.BiasTable(shape["bias"], dev) if shape is not None and shape["bias"] is not None else None
+        if rows is None:
+            shaper = dict(frequency_penalty=shape["frequency"], presence_penalty=shape["presence"])
+            penalised = shape["frequency"] != 0.0 or shape["presence"] != 0.0
+        else:
+            shaper, penalised = {}, row_penalties                         # (every row resolved to 0: a bias alone, zero scalars)
         counts = torch.zeros((B, V), dtype=torch.int32, device=dev) if penalised else None
+        if row_penalties:                                                 # the rows' own penalties, uploaded once
+            shaper = dict(frequency_rows=torch.tensor([r["frequency_penalty"] for r in rows], dtype=torch.float32, device=dev),
+                          presence_rows=torch.tensor([r["presence_penalty"] for r in rows], dtype=torch.float32, device=dev))
     # what the sampler and every row editor see: all R rows, or under guidance the first B of them (views, taken once)
     spos, snxt = (positions, nxt) if guide is None else (positions[:B], nxt[:B])
     # the sampler launch's arguments that every token shares (opts.sampler: what it takes beyond its old arguments)
     sampler = dict(temperature=opts.temperature, top_k=opts.top_k, top_p=opts.top_p, repetition_penalty=opts.repetition_penalty,
                    do_sample=opts.do_sample, seed=opts.seed, sequence_ids=sequence_ids, history=history, finished=finished,
                    eos_token_id=eos_token_id, pad_token_id=pad_token_id, out_tokens=out, **opts.sampler)
+    if rows is not None:                                                  # the one upload: the rows' records, packed by the library
+        sampler["rows"] = ops.SampleRowTable([{k: r[k] for k in ops.SampleRowTable.FIELDS} for r in rows], V, dev)
+        if budgets and auto is not None and snap is not None:             # a dead end and a spent budget both finish a row on a non-EOS token:
+            sampler["kept_count"] = live = torch.empty(B, dtype=torch.int32, device=dev)   # the launch's kept count tells them apart
     n = 0
     for g in range(max_new_tokens):
         constrained = cons is not None and (cons["every_step"] or g < cons["min_new"])
@@ -320,8 +360,7 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if auto is not None:
             ops.automaton_step(row, table, states[g & 1], states[1 - (g & 1)], last_token=snxt if g else None, finished=finished)
         if shaping:
-            ops.shape_logits(row, bias=bias, counts=counts, frequency_penalty=shape["frequency"], presence_penalty=shape["presence"],
-                             last_token=snxt if g else None, finished=finished)
+            ops.shape_logits(row, bias=bias, counts=counts, last_token=snxt if g else None, finished=finished, **shaper)
         if pad_launches is not None:
             pad_launches.add_(finished)                                   # (rows that enter this launch finished: it writes their pad)
         if snap is not None:
@@ -335,6 +374,8 @@ def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         if auto is not None and snap is not None:
             # a row this launch finished on a token other than the EOS had no candidate: what it emitted is a pad, no token of the row
             dead = (finished - snap) * (snxt != not_eos)
+            if budgets:
+                dead = dead * (live == 0)                                 # (a row its budget finished drew from at least one candidate)
             if pad_launches is not None:
                 pad_launches.add_(dead)
             if output_logprobs:
@@ -590,6 +631,99 @@ def check_truncation_args(*, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, 
         raise ValueError(f"{', '.join(out)}: not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
                          f"{prompt_lookup_num_tokens}): its verify step is greedy; see DESIGN.md §8")
     return out
+
+
+ROW_KEYS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "min_p", "typical_p", "epsilon_cutoff", "eta_cutoff",
+            "seed", "presence_penalty", "frequency_penalty", "max_new_tokens")
+
+
+def _row_value(key: str, v, vocab: int, limit):
+    """One value of a row's dict under the rules of the scalar keyword ``key`` -> the value as the table holds it, or ValueError.
+    ``limit``: the call's ``max_new_tokens`` (None: no upper bound is checked)."""
+    import ctypes
+    if key == "do_sample":
+        if not isinstance(v, bool):
+            raise ValueError(f"must be True or False, got {v!r}")
+        return v
+    if key in ("top_k", "seed", "max_new_tokens"):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"must be an integer, got {v!r}")
+        if key == "top_k" and not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError(f"{v} does not fit 32 bits")
+        if key == "max_new_tokens" and (v < 1 or (limit is not None and v > limit)):
+            raise ValueError(f"{v} must be in 1..{limit if limit is not None else 'max_new_tokens'}, the call's max_new_tokens: a row "
+                             "may end early, not run longer")
+        return v
+    if key in ("presence_penalty", "frequency_penalty", "min_p"):        # check_shape_args' own rules, on a batch of one
+        out = check_shape_args(vocab, 1, **{key: v}, num_beams=None, prompt_lookup_num_tokens=None)
+        return 0.0 if out is None else out[key.split("_")[0] if key != "min_p" else key]
+    if key in ("typical_p", "epsilon_cutoff", "eta_cutoff"):             # check_truncation_args' own rules
+        check_truncation_args(**{key: v}, num_beams=None, prompt_lookup_num_tokens=None)
+        return float(v)
+    # temperature, top_p, repetition_penalty: what kx_sample_logits asks of them, on the value the fp32 field will hold
+    if not _finite_fp32(v):
+        raise ValueError(f"must be a finite number (in fp32), got {v!r}")
+    f = ctypes.c_float(v).value
+    if key == "temperature" and not f >= 0.0:
+        raise ValueError(f"{v!r} must be >= 0 (0 = greedy)")
+    if key != "temperature" and not f > 0.0:
+        raise ValueError(f"{v!r} must be > 0 (in fp32)")
+    return float(v)
+
+
+def check_row_options(vocab: int, batch: int, *, row_options=None, max_new_tokens=None, num_beams=1, prompt_lookup_num_tokens=0,
+                      num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
+                      min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """ValueError (naming ``row_options``, and ``row_options[b]['key']`` for a value) for what generate() refuses of the per-row
+    options, before the device check and any launch; after check_truncation_args, so the call's own scalars are already known to be
+    good.  ``row_options``: None, or ``batch`` dicts — row b's overrides of any of ROW_KEYS; a key a row does not name takes the
+    call's own keyword (``max_new_tokens``: the call's positional value, i.e. no budget).  A value is refused exactly where the
+    scalar keyword refuses it — the same ranges, the same bool / non-number / non-finite rules — and for temperature, top_p and
+    repetition_penalty, which the scalar path hands to the library unchecked, where kx_sample_logits refuses the fp32 value.
+    ``max_new_tokens`` = m_b needs 1 <= m_b <= the call's (``max_new_tokens``, when an integer is given).  Not offered with
+    ``num_beams`` > 1 or ``prompt_lookup_num_tokens`` > 0, and a row resolved to greedy is refused under ``num_return_sequences`` > 1
+    as scalar greedy is.
+    Returns None when there is nothing to do (None, or every dict empty: no buffer, no upload, the old entry points), else the
+    resolved table: ``batch`` dicts holding every ROW_KEYS entry, ``max_new_tokens`` 0 where the row has no budget."""
+    if row_options is None:
+        return None
+    if isinstance(row_options, (str, bytes)) or hasattr(row_options, "items") or not hasattr(row_options, "__iter__"):
+        raise ValueError(f"row_options must be a sequence of {batch} dicts (one per row) or None, got {type(row_options).__name__}")
+    given = list(row_options)
+    if len(given) != batch:
+        raise ValueError(f"row_options must have {batch} entries (one dict per row), got {len(given)}")
+    for b, r in enumerate(given):
+        if not hasattr(r, "items"):
+            raise ValueError(f"row_options[{b}] must be a dict of overrides, got {type(r).__name__}")
+        for key in r:
+            if key not in ROW_KEYS:
+                raise ValueError(f"row_options[{b}][{key!r}]: unknown key; a row may name {', '.join(ROW_KEYS)}")
+    if num_beams not in (1, None):
+        raise ValueError(f"row_options is not offered together with num_beams = {num_beams}: beams rank log-probs and do not sample; see "
+                         "DESIGN.md §8")
+    if prompt_lookup_num_tokens not in (0, None):
+        raise ValueError(f"row_options is not offered together with prompt-lookup speculation (prompt_lookup_num_tokens = "
+                         f"{prompt_lookup_num_tokens}): its verify step is greedy and emits a varying number of tokens per row; see "
+                         "DESIGN.md §8")
+    # (a call's max_new_tokens that is no positive integer is refused by its own check, in its own words: no bound is taken from it)
+    limit = max_new_tokens if isinstance(max_new_tokens, int) and not isinstance(max_new_tokens, bool) and max_new_tokens >= 1 else None
+    call = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                repetition_penalty=float(repetition_penalty), min_p=float(min_p), typical_p=float(typical_p),
+                epsilon_cutoff=float(epsilon_cutoff), eta_cutoff=float(eta_cutoff), seed=int(seed),
+                presence_penalty=float(presence_penalty), frequency_penalty=float(frequency_penalty), max_new_tokens=0)
+    rows = []
+    for b, r in enumerate(given):
+        row = dict(call)
+        for key, v in r.items():
+            try:
+                row[key] = _row_value(key, v, vocab, limit)
+            except ValueError as e:
+                raise ValueError(f"row_options[{b}][{key!r}]: {e}") from None
+        if num_return_sequences not in (1, None) and (not row["do_sample"] or row["temperature"] == 0.0):
+            raise ValueError(f"row_options[{b}] resolves to greedy (do_sample = {row['do_sample']}, temperature = {row['temperature']}) "
+                             f"under num_return_sequences = {num_return_sequences}: greedy copies of one prompt would all be equal")
+        rows.append(row)
+    return rows if any(given) else None
 
 
 def check_guidance_args(batch: int, *, guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None,
@@ -851,6 +985,8 @@ def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
         opts = dataclasses.replace(opts, automaton=(opts.automaton[0], [opts.automaton[1][b] for b in seq]))
     if opts.shape is not None and opts.shape["bias"] is not None:
         opts = dataclasses.replace(opts, shape=dict(opts.shape, bias=[opts.shape["bias"][b] for b in seq]))
+    if opts.rows is not None:                                             # prompt b's options go to its n samples
+        opts = dataclasses.replace(opts, rows=[opts.rows[b] for b in seq])
     state["prefix"] = dict(ktail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            vtail=torch.empty((L, B * n, nh, N, hd), dtype=kc.dtype, device=dev),
                            prefix_seq=torch.tensor(seq, dtype=torch.int32, device=dev),
@@ -1165,10 +1301,11 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
     shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
     truncation = check_truncation_args(**_own(check_truncation_args, kw))
+    rows = check_row_options(vocab, batch, max_new_tokens=max_new_tokens, **_own(check_row_options, kw))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **_own(check_session_args, kw))
     prompt["check"](**({} if guide is None or kw["negative_prompt_ids"] is None else dict(negative_prompt_ids=kw["negative_prompt_ids"])))
-    opts = LoopOptions.resolved(kw, cons, starts, shape, truncation, guide)      # what the four plain-loop paths below take
+    opts = LoopOptions.resolved(kw, cons, starts, shape, truncation, guide, rows)   # what the four plain-loop paths below take
     with torch.no_grad():
         if guide is not None:
             # every sequence as two rows of one ragged batch: the prompt (rows 0..B-1) and its negative (rows B..2B-1), prefilled
@@ -1408,7 +1545,8 @@ class Session:
                  top_p=1.0, repetition_penalty=1.0, seed=0, eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8,
                  output_logits=False, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
                  prefill_chunk=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
-                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                 logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
+                 row_options=None):
         """One more turn: ``x`` [B, Tn] int64 holds the new turn's ids only (``prompt_lengths``: row b's are x[b, :prompt_lengths[b]],
         at least one), the other arguments are the plain loop's, as in generate().  Returns what generate() returns and advances the
         session in place.  The Philox position of a token is the absolute position it will occupy; the repetition penalty and the
@@ -1420,8 +1558,9 @@ class Session:
         an earlier turn are not kept, and the automaton reads the turn's output only.
         ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_p``: as in generate(); the penalties count what THIS turn
         emitted — every turn starts from zero counts, and neither the prompt nor an earlier turn's output counts.
-        ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: as in generate()."""
-        kw = _keywords(locals(), "self", "x", "max_new_tokens", "prompt_lengths", "prefill_chunk")
+        ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: as in generate().
+        ``row_options``: this turn's own per-row options, as in generate(); a row's budget ends its turn after that many tokens."""
+        kw = _keywords(locals(), "self", "x", "prompt_lengths", "prefill_chunk")
         lens = self._check_turn(x, prompt_lengths)
         opts = loop_options(self._model.embed.weight.shape[0], self.batch, **kw)
         chunk = check_prefill_chunk(prefill_chunk)

@@ -1337,7 +1337,7 @@ class Kosmos(nn.Module):
                  prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
                  token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None,
-                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1453,7 +1453,19 @@ class Kosmos(nn.Module):
         (0 = off): the tokens with p >= min(e, sqrt(e) exp(-entropy)).  Epsilon and eta always keep the most likely token of what
         they were handed.  They compose with everything sampling composes with; with ``num_beams`` > 1 or
         ``prompt_lookup_num_tokens`` > 0, or with a value out of range: ValueError naming the argument.  With the three at their
-        defaults nothing changes: the same launches."""
+        defaults nothing changes: the same launches.
+        ``row_options``: a batch of unlike requests in one call — a sequence of B dicts, one per row (per prompt under
+        ``num_return_sequences`` > 1: prompt b's dict goes to its n samples), each naming any of ``do_sample``, ``temperature``,
+        ``top_k``, ``top_p``, ``repetition_penalty``, ``min_p``, ``typical_p``, ``epsilon_cutoff``, ``eta_cutoff``, ``seed``,
+        ``presence_penalty``, ``frequency_penalty`` and ``max_new_tokens``; what a row does not name is the call's own keyword.  Row
+        b is sampled exactly as a call of its own with its resolved values would sample it — the same stages, bits and Philox address
+        (row b's seed; position, ``sequence_ids[b]``) — inside the same launches (kx_sample_logits_rows, kx_shape_logits_rows: one
+        uploaded table, no further launch).  A row with ``temperature`` 0 or ``do_sample`` False is greedy and ignores its filters.
+        ``max_new_tokens`` = m_b in 1..``max_new_tokens``: row b emits m_b tokens, is then finished and padded with
+        ``pad_token_id`` like a row that drew an EOS.  It composes with ``prompt_lengths``, parallel sampling, guidance, sessions
+        (every turn takes its own) and everything the plain loop composes with; with ``num_beams`` > 1 or
+        ``prompt_lookup_num_tokens`` > 0, a wrong length, an unknown key or a value the scalar keyword would refuse: ValueError naming
+        ``row_options[b]['key']``.  None or B empty dicts change nothing: the same launches."""
         kw = generation._keywords(locals(), "self", "text_tokens", "images", "max_new_tokens")
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1632,7 +1644,8 @@ class KosmosLanguage(nn.Module):
                  max_matching_ngram_size=2, output_acceptance=False, _draft_from=None, prefill_chunk=None, return_session=False,
                  session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
                  logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, guidance_scale=1.0,
-                 negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                 negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
+                 row_options=None):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1647,7 +1660,7 @@ class KosmosLanguage(nn.Module):
         ``negative_prompt_ids`` and ``negative_prompt_lengths``: classifier-free guidance against a negative prompt, as there —
         a negative prompt has at least one token, and with ``negative_prompt_ids`` None row b's unconditional context is its last
         prompt token, as in `transformers`; ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff``: the truncation samplers inside the
-        sampler launch, as there)."""
+        sampler launch, as there; ``row_options``: B dicts of per-row sampling options and budgets, as there)."""
         kw = generation._keywords(locals(), "self", "x", "max_new_tokens")
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")

@@ -438,10 +438,41 @@ def token_range(tokens, out=None):
     return out
 
 
+class SampleRowTable:
+    """Per-row sampling options in the form kx_sample_logits_rows reads, the counterpart of BiasTable: B kx_sample_row records in
+    device memory (``table``, uint8 [B * 56]) and the launch summary ``flags`` kx_sample_rows_pack returned for them
+    (H.SAMPLE_ROWS_PENALTY: some row has a repetition penalty; H.SAMPLE_ROWS_BUDGET: some row has a budget).
+    ``rows``: B dicts naming any of do_sample, temperature, top_k, top_p, repetition_penalty, min_p, typical_p, epsilon_cutoff,
+    eta_cutoff, seed and max_new_tokens (0 = no budget); what a dict leaves out is switched off (a row without ``do_sample`` is
+    greedy).  ``V``: the vocabulary the table is for.  Packed on the host by the library (ValueError naming the row and the field for
+    what it refuses), uploaded once; built once per generate() call and passed to every ops.sample_logits of the loop."""
+    FIELDS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "min_p", "typical_p", "epsilon_cutoff", "eta_cutoff",
+              "seed", "max_new_tokens")
+
+    def __init__(self, rows, V, device):
+        rows = list(rows)
+        if not rows:
+            raise ValueError("SampleRowTable: rows must hold at least one record")
+        rec = (H.SampleRow * len(rows))()
+        for b, r in enumerate(rows):
+            unknown = set(r) - set(self.FIELDS)
+            if unknown:
+                raise ValueError(f"SampleRowTable: rows[{b}] names {sorted(unknown)}, not among {self.FIELDS}")
+            kw = {k: (float(v) if isinstance(getattr(rec[b], k), float) else int(v)) for k, v in r.items() if k not in ("seed", "max_new_tokens")}
+            rec[b] = H.SampleRow(seed=int(r.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, max_new=int(r.get("max_new_tokens", 0)), **kw)
+        got = C.c_uint32(0)
+        rc = H.load().kx_sample_rows_pack(rec, len(rows), int(V), rec, C.byref(got))
+        if rc != 0:
+            raise ValueError(f"SampleRowTable: {H.last_error()}")
+        self.B, self.V, self.flags = len(rows), int(V), int(got.value)
+        self.host = rec                                                   # the packed records (log_min_p filled in)
+        self.table = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8).to(device)
+
+
 def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, do_sample=True, seed=0,
                   position=0, sequence_ids=None, history=None, hist_len=0, finished=None, eos_token_id=None,
                   pad_token_id=1, return_debug=False, out=None, out_tokens=None, out_col=0, positions=None, advance=0, min_p=0.0,
-                  typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                  typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, rows=None, kept_count=None):
     """Next token of every row of fp32 `logits` [B, V] (row stride >= V), drawn on the device by one launch
     (kx_sample_logits in include/kosmosx_hip.h: repetition penalty -> temperature -> top-k -> top-p -> Gumbel-max draw
     addressed by (seed, sequence id, position); greedy when ``do_sample`` is false or ``temperature`` is 0).
@@ -456,17 +487,24 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     typical_p in (0, 1] (1 = off), epsilon_cutoff and eta_cutoff in [0, 1) (0 = off; with all three off the entry points above are
     called as before): the `transformers` truncation samplers, behind min-p in that order, each over what the one before it kept
     (kx_sample_logits_truncate, either form); ignored under greedy.
+    rows (a SampleRowTable of B records, or None): row b is sampled under its own record — do_sample, temperature, top_k, top_p,
+    repetition_penalty, min_p, the three cut-offs and the seed of this call are then ignored — and a row whose record has a budget
+    max_new becomes finished by the launch with ``out_col`` + 1 >= max_new (kx_sample_logits_rows, either form; ``finished`` is then
+    required).  Row b gets the bits of a one-row call with its record's values.
+    kept_count [B] int32 (device, out): a caller-owned place for the size of the set every row drew from — ``return_debug``'s count
+    without its mask; 0 for a row that entered the launch finished or had no candidate.
     Returns next_token [B] int64 (and kept_count [B] int32, keep_mask [B, V] uint8 with ``return_debug``)."""
-    _need_cuda(logits, sequence_ids, history, finished, out, out_tokens, positions)
+    _need_cuda(logits, sequence_ids, history, finished, out, out_tokens, positions, kept_count)
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise TypeError("sample_logits: logits must be fp32 [B, V] with unit column stride")
     for name, t, dt in (("sequence_ids", sequence_ids, torch.int64), ("history", history, torch.int64),
                         ("finished", finished, torch.uint8), ("out", out, torch.int64), ("out_tokens", out_tokens, torch.int64),
-                        ("positions", positions, torch.int32)):
+                        ("positions", positions, torch.int32), ("kept_count", kept_count, torch.int32)):
         if t is not None and (t.dtype != dt or not t.is_contiguous()):
             raise TypeError(f"sample_logits: {name} must be a contiguous {dt} tensor")
     B, V = logits.shape
-    for name, t in (("sequence_ids", sequence_ids), ("finished", finished), ("out", out), ("positions", positions)):
+    for name, t in (("sequence_ids", sequence_ids), ("finished", finished), ("out", out), ("positions", positions),
+                    ("kept_count", kept_count)):
         if t is not None and tuple(t.shape) != (B,):
             raise ValueError(f"sample_logits: {name} must have shape [{B}]")
     for name, t in (("history", history), ("out_tokens", out_tokens)):
@@ -486,10 +524,24 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=1.0, repetition_pen
     a.next_token = out.data_ptr()
     a.out_tokens, a.out_ld, a.out_col = H.ptr(out_tokens), (0 if out_tokens is None else out_tokens.shape[1]), int(out_col)
     kept = mask = None
+    if kept_count is not None:
+        a.kept_count = kept_count.data_ptr()
     if return_debug:
-        kept = torch.empty(B, dtype=torch.int32, device=logits.device)
+        kept = kept_count if kept_count is not None else torch.empty(B, dtype=torch.int32, device=logits.device)
         mask = torch.empty((B, V), dtype=torch.uint8, device=logits.device)
         a.kept_count, a.keep_mask = kept.data_ptr(), mask.data_ptr()
+    if rows is not None:
+        if not isinstance(rows, SampleRowTable):
+            raise TypeError(f"sample_logits: rows must be an ops.SampleRowTable (or None), got {type(rows).__name__}")
+        _need_cuda(rows.table)
+        if rows.B != B or rows.V != V:
+            raise ValueError(f"sample_logits: rows holds {rows.B} records for a vocabulary of {rows.V}, logits are [{B}, {V}]")
+        if positions is not None:
+            a.position = 0
+        r = H.SampleRowsArgs(flags=rows.flags, table=rows.table.data_ptr())
+        H.check(H.load().kx_sample_logits_rows(C.byref(a), H.ptr(positions), int(advance) if positions is not None else 0, C.byref(r),
+                                               _stream()), "kx_sample_logits_rows")
+        return (out, kept, mask) if return_debug else out
     min_p = float(min_p)
     if not 0.0 <= min_p <= 1.0:
         raise ValueError(f"sample_logits: min_p = {min_p} must be in [0, 1]")
@@ -679,7 +731,8 @@ class BiasTable:
         return t
 
 
-def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, presence_penalty=0.0, last_token=None, finished=None):
+def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, presence_penalty=0.0, last_token=None, finished=None,
+                 frequency_rows=None, presence_rows=None):
     """Logit bias and presence / frequency penalties on every row of fp32 `logits` [B, V] (row stride >= V) IN PLACE, by one launch,
     after ops.constrain_logits / ops.automaton_step and before ops.sample_logits reads them (kx_shape_logits in
     include/kosmosx_hip.h): counts[b, last_token[b]] += 1, then l = l + bias for the listed ids, then where the count c is
@@ -687,17 +740,22 @@ def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, prese
 
     ``bias``: BiasTable of B rows (or None).  counts int32 [B, V] (in/out; None when both penalties are 0): how often this call
     emitted each id, zeroed by the caller before the first step.  last_token int64 [B]: the sampler's token of the previous step
-    (None at step 0).  finished uint8 [B] (read only): finished rows keep their logits and their counts.  Returns None."""
+    (None at step 0).  finished uint8 [B] (read only): finished rows keep their logits and their counts.
+    frequency_rows / presence_rows fp32 [B] (device; either may be None: the scalar for every row): row b's own penalties in the
+    same three operations (kx_shape_logits_rows; ``counts`` is then required).  With both None the call is kx_shape_logits.
+    Returns None."""
     if bias is not None and not isinstance(bias, BiasTable):
         raise TypeError(f"shape_logits: bias must be an ops.BiasTable (or None), got {type(bias).__name__}")
     _need_cuda(logits, counts, last_token, finished, *((bias.off, bias.ids, bias.val) if bias is not None else ()))
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise TypeError("shape_logits: logits must be fp32 [B, V] with unit column stride")
-    for name, t, dt in (("counts", counts, torch.int32), ("last_token", last_token, torch.int64), ("finished", finished, torch.uint8)):
+    _need_cuda(frequency_rows, presence_rows)
+    for name, t, dt in (("counts", counts, torch.int32), ("last_token", last_token, torch.int64), ("finished", finished, torch.uint8),
+                        ("frequency_rows", frequency_rows, torch.float32), ("presence_rows", presence_rows, torch.float32)):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous()):
             raise TypeError(f"shape_logits: {name} must be a contiguous {dt} tensor")
     B, V = logits.shape
-    for name, t in (("last_token", last_token), ("finished", finished)):
+    for name, t in (("last_token", last_token), ("finished", finished), ("frequency_rows", frequency_rows), ("presence_rows", presence_rows)):
         if t is not None and tuple(t.shape) != (B,):
             raise ValueError(f"shape_logits: {name} must have shape [{B}]")
     if counts is not None and tuple(counts.shape) != (B, V):
@@ -710,7 +768,10 @@ def shape_logits(logits, *, bias=None, counts=None, frequency_penalty=0.0, prese
         a.bias_off, a.bias_ids, a.bias_val, a.n_bias = bias.off.data_ptr(), bias.ids.data_ptr(), bias.val.data_ptr(), bias.n
     a.counts, a.frequency, a.presence = H.ptr(counts), float(frequency_penalty), float(presence_penalty)
     a.last_token, a.finished = H.ptr(last_token), H.ptr(finished)
-    H.check(H.load().kx_shape_logits(C.byref(a), _stream()), "kx_shape_logits")
+    if frequency_rows is None and presence_rows is None:
+        H.check(H.load().kx_shape_logits(C.byref(a), _stream()), "kx_shape_logits")
+    else:
+        H.check(H.load().kx_shape_logits_rows(C.byref(a), H.ptr(frequency_rows), H.ptr(presence_rows), _stream()), "kx_shape_logits_rows")
 
 
 def guidance_logits(cond, uncond, *, scale, out=None, finished=None, positions=None, advance=0):
