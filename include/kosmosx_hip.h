@@ -591,7 +591,8 @@ int kx_attention_decode(const void* qkv, void* kcache, void* vcache, void* out, 
  *   the FULL [Tmax, 32] tables (one centring, as for the prefill); xpos_rows [4, B, 32] fp32 scratch.  x and xpos_rows
  *   are zeroed by the caller before the first step (see kx_step_prepare).  Both step paths
  *   (weight streaming up to 16 sequences, tile GEMMs above) run their qkv launch with xpos_T = B on xpos_rows. */
-typedef enum { KX_RAGGED_ERR_TABLE = 1, KX_RAGGED_ERR_CACHE = 2, KX_RAGGED_ERR_GATHER = 4 /* kx_kv_cache_gather */ } kx_ragged_error;
+typedef enum { KX_RAGGED_ERR_TABLE = 1, KX_RAGGED_ERR_CACHE = 2, KX_RAGGED_ERR_GATHER = 4 /* kx_kv_cache_gather */,
+               KX_RAGGED_ERR_COMMIT = 8 /* kx_kv_cache_commit */ } kx_ragged_error;
 int kx_attention_decode_ragged(const void* qkv, void* kcache, void* vcache, void* out, int32_t odt, float* stats_out,
                                int64_t B, int64_t H, const int32_t* positions, int64_t Tmax, int32_t prec,
                                int32_t* error_word, void* stream);
@@ -1484,6 +1485,73 @@ int kx_sample_logits_rows(const kx_sample_args* args, int32_t* positions, int64_
  * (KX_ERR_INVALID_ARG naming counts); the values of an array are used in arithmetic only — the caller passes finite ones, as it
  * passes finite scalars.  Nothing else about the launch, its ownership rules or its limits changes. */
 int kx_shape_logits_rows(const kx_shape_args* args, const float* frequency_rows, const float* presence_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Contrastive search on the device (added within ABI 7: six functions are appended; no struct, no existing layout moves and the
+ * kx_struct_id list is unchanged, so kx_version() stays 7 and KX_STRUCT_COUNT 13).
+ *
+ * A step of contrastive search takes the k <= 16 most likely next tokens of each of B sequences, runs them as M = B * k rows of
+ * kx_decoder_decode_step_prefix (prefix = the sequence so far, prefix_seq[r] = r / k, prefix_len == positions == P_b repeated k times,
+ * tail caches [L, M, heads, 1, 64]) and keeps, per sequence, the candidate j with the largest
+ *     score_j = one_minus_alpha * p_j - alpha * max over i < P_b of dot(u_j, history[b, i]),
+ * u being unit vectors of the hidden states.  Row b * k + j is candidate j of sequence b everywhere below.
+ *
+ * kx_contrast_candidates: sequence b's current logits row is row b * k_prev + chosen[b] of logits [rows, V] (row pitch ld), or row b
+ *   with chosen == NULL (k_prev = 1): addressed, not copied.  One launch writes its k ids of largest value, the lowest id first among
+ *   equal values — bit for bit the top_id of kx_step_logprobs with top_n = k, whose device code it shares — to step_tokens[b * k + j]
+ *   (the next step's tokens), prob[b * k + j] = expf(that launch's top_logprob) and, when cand_id / cand_prob are given, the same to
+ *   slot ((b * out_ld + out_col) * k + j) of both.  A sequence with finished[b] != 0 (finished may be NULL), or whose chosen[b] is
+ *   outside [0, k_prev), writes nothing (kx_kv_cache_commit reports the latter).  Host checks: null pointers, k outside 1..16 or above
+ *   V, k_prev outside 1..16, rows < B * k_prev, ld < V, out_col outside [0, out_ld).
+ * kx_contrast_hidden: out row = u = h / ||h||_2 in fp32, h = decoder.layer_norm (w->ln_g, w->ln_b, w->eps) of a row of the final
+ *   residual stream — what the output projection multiplies.  step != 0: x [B, dim] is the x of a decode step of B rows (T == 1) that
+ *   has just run with `workspace` and `prec`; the residual is x alone, or x + xb of the workspace where that step ran its
+ *   two-workgroup residual form — decided by the very helper the step asks, from w, B, prec and the tuning keys.  step == 0:
+ *   x [B, T, dim] holds rows as they are (kx_decoder_prefill leaves the final residual in its x), workspace and prec are unused.
+ *   Row (b, t) goes to out + b * out_ld + t * dim (out_ld in floats, >= T * dim); with lengths (int32 [B], device) rows t >=
+ *   lengths[b] are not written.  residual_out (optional, fp32 [B * T, dim]): the rows v the kernel normalised, x or the summed pair,
+ *   for a caller that wants to restate the result.  The arithmetic, every operation a single fp32 one: v_i = x_i + xb_i (the pair only);
+ *   mean = (sum v_i) / dim; c_i = v_i - mean; var = (sum c_i * c_i) / dim; r = 1 / sqrtf(var + eps); h_i = (c_i * r) * g_i + b_i
+ *   (two products and one sum, not contracted); n = sqrtf(sum h_i * h_i); u_i = h_i / n.  Each sum: 256 threads over elements
+ *   tid, tid + 256, ... in ascending order, a butterfly over the 64 lanes, then (w0 + w1) + (w2 + w3) — a function of dim alone.
+ * kx_contrast_select: u [B * k, D] (kx_contrast_hidden's rows), prob [B * k], history [B, cap, D] fp32, P_b = hist_rows[b * p_stride]
+ *   (int32, device).  Two launches.  The first splits the history along i, CS = 32 rows per workgroup, grid (ceil(cap / 32), B):
+ *   a workgroup stages its sequence's k candidate vectors once (k * D * 4 <= 128 KB of LDS), reads the history 16 bytes per lane and
+ *   writes k partial maxima to scratch (kx_contrast_scratch_bytes(B, k, cap) bytes).  Every dot product is summed in one order that
+ *   depends on D alone: lane l takes the 4-element vectors l, l + 64, ... ascending with acc = fma(h3, c3, fma(h2, c2, fma(h1, c1,
+ *   fma(h0, c0, acc)))), then a butterfly over the 64 lanes (xor 32 .. 1) — the chunking, the grid, B, k and the place of a row or a
+ *   candidate do not enter, and the maximum over i is exact in any order.  No workgroup waits on another; no atomics on floats.  The
+ *   second, one workgroup per sequence, takes penalty_j = the maximum of the partial maxima, score_j = (one_minus_alpha * p_j) -
+ *   (alpha * penalty_j) as two products and one difference each rounded once (one_minus_alpha is the caller's fp32), chooses the
+ *   largest score, the lowest j among equal ones, a NaN score losing to every number, and writes next_token[b] = step_tokens[b * k + j],
+ *   chosen[b] = j, history[b, P_b] = u[b * k + j] (bitwise), hist_len[b] = P_b + 1, finished[b] = 1 when the token is eos_id (eos_id
+ *   < 0: none) and, where given, out_tokens[b * out_ld + out_col], chosen_trace[b * out_ld + out_col] and cand_penalty[(b * out_ld +
+ *   out_col) * k + j'] for every j'.  A row that enters finished writes pad_id to next_token[b] and out_tokens and nothing else.  A row
+ *   with P_b < 1 or P_b >= cap writes nothing and ORs KX_RAGGED_ERR_CACHE into *error_word.  Host checks: null pointers, k outside
+ *   1..16, B outside 1..65535, D % 4, k * D * 4 > 128 KB, cap < 2, alpha or one_minus_alpha outside [0, 1], out_col outside
+ *   [0, out_ld), u / history not 16-byte aligned or overlapping, scratch_bytes too small.
+ * kx_kv_cache_commit: for every layer and head, tail row 0 of row b * k + chosen[b] of the tail caches [L, B * k, heads, Ttail, 64]
+ *   goes to row P_b = positions[b * k] of sequence b of the caches [L, B, heads, Tmax, 64], k and v, 16 bytes per thread; then
+ *   positions[b * k .. b * k + k - 1] = P_b + 1.  Both cache dtypes (elem_bytes 2 or 4) and both layouts (tuning key 9, applied to the
+ *   caches and the tails).  A row with finished[b] != 0 (finished may be NULL) is skipped.  chosen[b] outside [0, k) or P_b outside
+ *   [0, Tmax) writes nothing, leaves the positions and ORs KX_RAGGED_ERR_COMMIT into the sticky *error_word.  Host checks as for
+ *   kx_kv_cache_gather: null pointers, elem_bytes, shape ranges, k outside 1..16, 16-byte alignment, overlap of tails and caches.
+ * None of them allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int kx_contrast_candidates(const float* logits, int64_t ld, int64_t rows, int64_t B, int64_t V, int32_t k, const int32_t* chosen,
+                           int64_t k_prev, const uint8_t* finished, int64_t* step_tokens, float* prob, int64_t* cand_id,
+                           float* cand_prob, int64_t out_ld, int64_t out_col, void* stream);
+int kx_contrast_hidden(const kx_decoder_weights* w, const float* x, void* workspace, int64_t B, int64_t T, int32_t prec, int32_t step,
+                       const int32_t* lengths, float* out, int64_t out_ld, float* residual_out, void* stream);
+size_t kx_contrast_scratch_bytes(int64_t B, int32_t k, int64_t cap);
+int kx_contrast_select(const float* u, const float* prob, float* history, int64_t B, int32_t k, int64_t D, int64_t cap,
+                       const int32_t* hist_rows, int64_t p_stride, int32_t* hist_len, float alpha, float one_minus_alpha,
+                       const int64_t* step_tokens, uint8_t* finished, int64_t eos_id, int64_t pad_id, int64_t* next_token,
+                       int32_t* chosen, int64_t* out_tokens, int64_t out_ld, int64_t out_col, float* cand_penalty,
+                       int32_t* chosen_trace, float* scratch, size_t scratch_bytes, int32_t* error_word, void* stream);
+int kx_kv_cache_commit(const void* ktail, const void* vtail, void* kcache, void* vcache, int64_t L, int64_t B, int32_t k,
+                       int64_t heads, int64_t Tmax, int64_t Ttail, int32_t elem_bytes, const int32_t* chosen, int32_t* positions,
+                       const uint8_t* finished, int32_t* error_word, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * In-process kernel timing (bench.py's roofline leg; the reference's own ad-hoc equivalents are the

@@ -761,6 +761,22 @@ static int step_attention(const StepRows& r, const void* qkv, void* kc, void* vc
   return kx_attention_decode(qkv, kc, vc, out, odt, stats_out, B, H, r.t, Tmax, prec, stream);
 }
 
+// Whether a step of M rows streams the weights (prec: the operand precision, KX_PREC_F32W24 / W16 already folded into KX_PREC_F32),
+// and whether its residual stream is then the pair x + xb of the workspace (see decode_step_impl).  decode_step_impl and
+// kx_contrast_hidden both ask here, so what the one wrote is what the other reads.
+static bool step_streams(const kx_decoder_weights* w, int64_t M, int32_t prec) {
+  const int64_t D = w->dim, F = w->ffn;
+  return (prec == KX_PREC_BF16 || prec == KX_PREC_F32) && M <= 16 && kx_tuning_get(KX_TUNE_GEMM_TILE) == 0 && D % 32 == 0 &&
+         F % 32 == 0 && (size_t)M * (esz(prec) * D + 16) <= 144 * 1024 && !(prec == KX_PREC_F32 && kx_tuning_get(KX_TUNE_DECODE_STREAM_F32) == 1);
+}
+static bool step_pair(const kx_decoder_weights* w, int64_t M) {
+  const int64_t D = w->dim, F = w->ffn;
+  return kx_tuning_get(KX_TUNE_DECODE_KSPLIT) != 1 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 1 &&
+         D / 16 <= (kx_cu_count() * 3) / 4 && D % 128 == 0 && F % 128 == 0 &&
+         M <= 4;   // (five rows and more take the wave-per-row LayerNorm prologue, which walks each row three times: reading a
+                   //  pair there cost more than the idle CUs — B = 8: 1.43 -> 1.55 ms per step in bf16)
+}
+
 static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* x, int64_t B, const StepRows& r, const float* xq_cs,
                             const float* xq_ss, const float* xk_cs, const float* xk_ss, void* kcache, void* vcache, int64_t Tmax,
                             void* logits, int32_t ldt, void* workspace, size_t workspace_bytes, int32_t prec, void* stream) {
@@ -787,23 +803,18 @@ static int decode_step_impl(const char* fn, const kx_decoder_weights* w, float* 
   const Stage st(s, prec, d.splitk);
   KX_TRY(st.clear_words());
   const int ct = cdt(prec);
-  const size_t es = esz(prec);
   const size_t layer_bytes = (size_t)(r.cache_seq || r.prefix_seq ? r.Bc : r.K > 0 ? B / r.K : B) * Tmax * D * qes(prec);   // the cache holds q/k/v-typed values (fp32 for f16c)
   // One token per sequence, up to 16 sequences: the step is 120 dependent launches of weight-streaming work, and launches
   // are what it costs (~6 us each) — tile 16 does each GEMM in one launch and takes the LayerNorm and
   // statistics-finalize kernels in as prologues: 5 launches per layer instead of 13.  bf16 operands, or fp32 operands on the
   // exact-f32 MFMA (KX_PREC_F32: what the Python side asks for in every precision that holds the north star's tolerance).
-  if ((prec == KX_PREC_BF16 || prec == KX_PREC_F32) && M <= 16 && kx_tuning_get(KX_TUNE_GEMM_TILE) == 0 && D % 32 == 0 &&
-      F % 32 == 0 && (size_t)M * (es * D + 16) <= 144 * 1024 && !(prec == KX_PREC_F32 && kx_tuning_get(KX_TUNE_DECODE_STREAM_F32) == 1)) {
+  if (step_streams(w, M, prec)) {
     // The residual GEMMs have N = D columns = D / 16 workgroups (128 at full size: half the CUs stream).  Where that leaves
     // CUs idle they run as TWO workgroups per column block, each over half of K, and the residual stream becomes a pair
     // x = xa + xb (kx_gemm_args.ksplit): part 0 writes (xa' + xb') + bias + its product to the next pair's first member,
     // part 1 its product to the second; the LayerNorm prologues and the next residual read sum the pair in that order.
     // No cross-workgroup reduction, deterministic.  Tuning key 11 = 1 keeps one workgroup per block (in place: x += ...).
-    const bool pair = kx_tuning_get(KX_TUNE_DECODE_KSPLIT) != 1 && kx_tuning_get(KX_TUNE_GEMV_VARIANT) != 1 &&
-                      D / 16 <= (kx_cu_count() * 3) / 4 && D % 128 == 0 && F % 128 == 0 &&
-                      M <= 4;   // (five rows and more take the wave-per-row LayerNorm prologue, which walks each row three times: reading a
-                                //  pair there cost more than the idle CUs — B = 8: 1.43 -> 1.55 ms per step in bf16)
+    const bool pair = step_pair(w, M);
     // Block-scaled 16-bit planes, three rows and more: the residual GEMMs multiply fp16 pieces (kx_gemm_args.w_tiled = 3), and what
     // they read — the attention output, gelu(fc1) — is written AS pieces by its producer (KX_F16P, w_tiled = 4): the same bits the
     // consumer would make of the fp32 rows, made once instead of in every lane of every workgroup.
@@ -989,4 +1000,83 @@ extern "C" int kx_decoder_decode_step_prefix(const kx_decoder_weights* w, const 
   return device_step("kx_decoder_decode_step_prefix", prefix_seq && prefix_len && kprefix && vprefix && ktail && vtail, range, w, tokens, embed, pos, vocab,
                      max_pos, pos_shift, x, M, r, xq_cs, xq_ss, xk_cs, xk_ss, xpos_rows, const_cast<void*>(kprefix),
                      const_cast<void*>(vprefix), Tmax, logits, ldt, workspace, workspace_bytes, prec, stream);
+}
+
+// ---------------- Contrastive search: the unit hidden rows (contract: include/kosmosx_hip.h, "Contrastive search on the device") ----------------
+namespace {
+__device__ __forceinline__ float hidden_block_sum(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float r = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return r;
+}
+
+// One workgroup per row.  v_i = x_i (+ xb_i); mean = sum(v) / D; c_i = v_i - mean; var = sum(c_i^2) / D; h_i = c_i * (1 / sqrt(var + eps))
+// * g_i + b_i; u_i = h_i / sqrt(sum(h_i^2)) — every operation a single fp32 one, the sums over a thread's strided elements in
+// ascending order, then a butterfly over the wave and a fixed tree over the four waves.
+__global__ __launch_bounds__(256) void contrast_hidden_kernel(const float* __restrict__ x, const float* __restrict__ xb,
+                                                              const float* __restrict__ g, const float* __restrict__ bta, int D, float eps,
+                                                              long long T, const int* __restrict__ lengths, float* __restrict__ out,
+                                                              long long out_ld, float* __restrict__ residual_out) {
+  __shared__ float red[4];
+  const long long r = blockIdx.x, b = r / T, t = r - b * T;
+  if (lengths && t >= lengths[b]) return;                                 // (uniform over the workgroup)
+  const float* xr = x + r * D;
+  const float* xr2 = xb ? xb + r * D : nullptr;
+  const int tid = threadIdx.x;
+  float s = 0.f;
+  for (int i = tid; i < D; i += 256) {
+    const float v = xr2 ? xr[i] + xr2[i] : xr[i];
+    if (residual_out) residual_out[r * D + i] = v;
+    s += v;
+  }
+  const float mean = hidden_block_sum(s, red) / (float)D;
+  float q = 0.f;
+  for (int i = tid; i < D; i += 256) {
+    const float c = (xr2 ? xr[i] + xr2[i] : xr[i]) - mean;
+    q += c * c;
+  }
+  const float rstd = 1.0f / sqrtf(hidden_block_sum(q, red) / (float)D + eps);
+  float ss = 0.f;
+  for (int i = tid; i < D; i += 256) {
+    const float c = (xr2 ? xr[i] + xr2[i] : xr[i]) - mean;
+    const float h = __fadd_rn(__fmul_rn(__fmul_rn(c, rstd), g[i]), bta[i]);
+    ss += h * h;
+  }
+  const float nrm = sqrtf(hidden_block_sum(ss, red));
+  float* o = out + b * out_ld + t * D;
+  for (int i = tid; i < D; i += 256) {
+    const float c = (xr2 ? xr[i] + xr2[i] : xr[i]) - mean;
+    o[i] = __fadd_rn(__fmul_rn(__fmul_rn(c, rstd), g[i]), bta[i]) / nrm;
+  }
+}
+}  // namespace
+
+extern "C" int kx_contrast_hidden(const kx_decoder_weights* w, const float* x, void* workspace, int64_t B, int64_t T, int32_t prec,
+                                  int32_t step, const int32_t* lengths, float* out, int64_t out_ld, float* residual_out, void* stream) {
+  KX_REQUIRE(w && x && out, "kx_contrast_hidden: null w / x / out");
+  KX_CHECK_BINDING(w, kx_decoder_weights, kx_decoder_layer, "kx_contrast_hidden");
+  KX_REQUIRE(w->ln_g && w->ln_b, "kx_contrast_hidden: the decoder's last LayerNorm (ln_g / ln_b) is missing");
+  KX_REQUIRE(B >= 1 && T >= 1 && B * T <= 0x7fffffffll, "kx_contrast_hidden: B=%lld, T=%lld: empty or over the grid limit", (long long)B,
+             (long long)T);
+  KX_REQUIRE(w->dim >= 1 && out_ld >= T * w->dim, "kx_contrast_hidden: out_ld=%lld is less than T * dim=%lld", (long long)out_ld,
+             (long long)(T * w->dim));
+  KX_REQUIRE(!step || T == 1, "kx_contrast_hidden: a decode step's rows are given with T == 1 (T=%lld)", (long long)T);
+  KX_REQUIRE(!step || workspace, "kx_contrast_hidden: a decode step's rows need the step's workspace");
+  const float* xb = nullptr;
+  if (step) {                                           // the step's own question: did the residual stream end as the pair x + xb?
+    KX_REQUIRE(((uintptr_t)workspace & 255) == 0, "kx_contrast_hidden: workspace must be 256-byte aligned");
+    if (prec == KX_PREC_F32W24 || prec == KX_PREC_F32W16) prec = KX_PREC_F32;
+    KX_REQUIRE(prec == KX_PREC_BF16 || prec == KX_PREC_F32 || prec == KX_PREC_F16C, "kx_contrast_hidden: bad step precision %d", (int)prec);
+    if (step_streams(w, B, prec) && step_pair(w, B)) xb = dec_plan(w, B, 1, prec, (char*)workspace).xb;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  KxProfScope prof(KX_K_LAYERNORM, B * T, w->dim, 0, s);
+  hipLaunchKernelGGL(contrast_hidden_kernel, dim3((unsigned)(B * T)), dim3(256), 0, s, x, xb, w->ln_g, w->ln_b, (int)w->dim, w->eps,
+                     (long long)T, (const int*)lengths, out, (long long)out_ld, residual_out);
+  KX_CHECK_LAUNCH("kx_contrast_hidden");
+  return KX_OK;
 }

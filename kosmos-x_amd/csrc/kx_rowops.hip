@@ -364,25 +364,12 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restr
 // sampler's pair; the thread that held the winner pops it.  Integer comparisons only: the ids depend on the row's values alone,
 // not on how the threads split it.  Pass 2 is block_sumexp, so slot j's log-prob is bit for bit what token_logprob_kernel gives
 // for that id.  A skipped row leaves before any barrier (uniform over the workgroup) with exact zeros and ids -1.
+// (row_top: passes 1 and 2 and the rounds between them on one row, shared with contrast_candidates_kernel — the same instructions
+// in the same order, so the two kernels give the same ids and the same log-prob bits for a row)
 template <int CAP>
-__global__ __launch_bounds__(256) void step_logprobs_kernel(const float* __restrict__ logits, long long ld, int V,
-                                                            const long long* __restrict__ token,
-                                                            const unsigned char* __restrict__ skip,
-                                                            float* __restrict__ token_logprob, long long out_ld, long long out_col,
-                                                            int top_n, float* __restrict__ top_logprob,
-                                                            long long* __restrict__ top_id) {
-  __shared__ float red[4];
-  __shared__ unsigned long long wred[4];
-  __shared__ int win[CAP > 0 ? CAP : 1];
+__device__ __forceinline__ void row_top(const float* __restrict__ lr, int V, int top_n, float* red, unsigned long long* wred,
+                                        int* win, float& mx_out, float& s_out) {
   const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
-  const long long o = b * out_ld + out_col;
-  if (skip && skip[b]) {
-    if (tid == 0) token_logprob[o] = 0.f;
-    if (tid < top_n) { top_logprob[o * top_n + tid] = 0.f; top_id[o * top_n + tid] = -1; }
-    return;
-  }
-  const float* lr = logits + b * ld;
   unsigned key[CAP > 0 ? CAP : 1];
   int id[CAP > 0 ? CAP : 1];
 #pragma unroll
@@ -439,7 +426,31 @@ __global__ __launch_bounds__(256) void step_logprobs_kernel(const float* __restr
       if (tid == 0) win[r] = best ? (int)(0xffffffffu - (unsigned)best) : -1;   // nothing left (V < top_n): id -1
     }
   }
-  const float s = block_sumexp(lr, V, red, mx);       // (its barriers also publish `win`)
+  s_out = block_sumexp(lr, V, red, mx);               // (its barriers also publish `win`)
+  mx_out = mx;
+}
+
+template <int CAP>
+__global__ __launch_bounds__(256) void step_logprobs_kernel(const float* __restrict__ logits, long long ld, int V,
+                                                            const long long* __restrict__ token,
+                                                            const unsigned char* __restrict__ skip,
+                                                            float* __restrict__ token_logprob, long long out_ld, long long out_col,
+                                                            int top_n, float* __restrict__ top_logprob,
+                                                            long long* __restrict__ top_id) {
+  __shared__ float red[4];
+  __shared__ unsigned long long wred[4];
+  __shared__ int win[CAP > 0 ? CAP : 1];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const long long o = b * out_ld + out_col;
+  if (skip && skip[b]) {
+    if (tid == 0) token_logprob[o] = 0.f;
+    if (tid < top_n) { top_logprob[o * top_n + tid] = 0.f; top_id[o * top_n + tid] = -1; }
+    return;
+  }
+  const float* lr = logits + b * ld;
+  float mx, s;
+  row_top<CAP>(lr, V, top_n, red, wred, win, mx, s);
   if (tid == 0) {
     const long long tg = token[b];
     token_logprob[o] = ((tg < 0) | (tg >= V)) ? 0.f : (lr[tg] - mx) - logf(s);
@@ -449,6 +460,41 @@ __global__ __launch_bounds__(256) void step_logprobs_kernel(const float* __restr
       const int w = win[tid];
       top_id[o * top_n + tid] = w;
       top_logprob[o * top_n + tid] = w < 0 ? -INFINITY : (lr[w] - mx) - logf(s);
+    }
+  }
+}
+
+// The candidates of a contrastive-search step (kx_contrast_candidates): sequence b's current logits row is row
+// b * k_prev + chosen[b] of `logits` (chosen == NULL: row b) — addressed, never copied.  row_top gives its k best ids and their
+// log-probs, bit for bit kx_step_logprobs' top_n = k pairs; prob = expf(log-prob).  A finished sequence, or one whose row index
+// leaves [0, rows), leaves before any barrier (uniform over the workgroup) and writes nothing.
+template <int CAP>
+__global__ __launch_bounds__(256) void contrast_candidates_kernel(const float* __restrict__ logits, long long ld, long long rows, int V,
+                                                                  int k, const int* __restrict__ chosen, long long k_prev,
+                                                                  const unsigned char* __restrict__ finished,
+                                                                  long long* __restrict__ step_tokens, float* __restrict__ prob,
+                                                                  long long* __restrict__ cand_id, float* __restrict__ cand_prob,
+                                                                  long long out_ld, long long out_col) {
+  __shared__ float red[4];
+  __shared__ unsigned long long wred[4];
+  __shared__ int win[CAP];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  if (finished && finished[b]) return;
+  const long long row = chosen ? b * k_prev + (long long)chosen[b] : b;
+  if ((row < 0) | (row >= rows) | (chosen != nullptr && ((chosen[b] < 0) | (chosen[b] >= k_prev)))) return;
+  const float* lr = logits + row * ld;
+  float mx, s;
+  row_top<CAP>(lr, V, k, red, wred, win, mx, s);
+  if (tid < k) {
+    const int w = win[tid];                           // (k <= V, checked on the host: never -1)
+    const float p = expf((lr[w] - mx) - logf(s));
+    step_tokens[b * k + tid] = w;
+    prob[b * k + tid] = p;
+    if (cand_id) {
+      const long long o = (b * out_ld + out_col) * k + tid;
+      cand_id[o] = w;
+      cand_prob[o] = p;
     }
   }
 }
@@ -674,4 +720,36 @@ extern "C" int kx_vit_assemble(const float* patch_out, const float* cls, const f
                  (((uintptr_t)patch_out | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)x) & 15) == 0,
              "kx_vit_assemble: null pointer, bad shape, dim %% 4 != 0 or unaligned buffers");
   return kx_launch_vit_assemble(patch_out, cls, pos, x, B, tokens, dim, (hipStream_t)stream);
+}
+
+extern "C" int kx_contrast_candidates(const float* logits, int64_t ld, int64_t rows, int64_t B, int64_t V, int32_t k,
+                                      const int32_t* chosen, int64_t k_prev, const uint8_t* finished, int64_t* step_tokens,
+                                      float* prob, int64_t* cand_id, float* cand_prob, int64_t out_ld, int64_t out_col, void* stream) {
+  KX_REQUIRE(logits, "kx_contrast_candidates: logits is null");
+  KX_REQUIRE(step_tokens, "kx_contrast_candidates: step_tokens is null");
+  KX_REQUIRE(prob, "kx_contrast_candidates: prob is null");
+  KX_REQUIRE(!cand_id == !cand_prob, "kx_contrast_candidates: cand_id and cand_prob are given together");
+  KX_REQUIRE(B >= 1 && B <= 0x7fffffffll, "kx_contrast_candidates: B=%lld (B >= 1)", (long long)B);
+  KX_REQUIRE(V >= 1 && V <= 0x7fffffffll, "kx_contrast_candidates: V=%lld (V >= 1)", (long long)V);
+  KX_REQUIRE(ld >= V, "kx_contrast_candidates: ld=%lld is less than V=%lld", (long long)ld, (long long)V);
+  KX_REQUIRE(k >= 1 && k <= 16 && k <= V, "kx_contrast_candidates: k=%d outside 1..16 (and at most V=%lld)", (int)k, (long long)V);
+  KX_REQUIRE(chosen ? (k_prev >= 1 && k_prev <= 16) : k_prev == 1, "kx_contrast_candidates: k_prev=%lld outside 1..16 (1 without chosen)",
+             (long long)k_prev);
+  KX_REQUIRE(rows >= B * k_prev, "kx_contrast_candidates: rows=%lld is less than B * k_prev=%lld", (long long)rows,
+             (long long)(B * k_prev));
+  KX_REQUIRE(!cand_id || (out_col >= 0 && out_col < out_ld), "kx_contrast_candidates: out_col=%lld outside [0, out_ld=%lld)",
+             (long long)out_col, (long long)out_ld);
+  hipStream_t s = (hipStream_t)stream;
+  KxProfScope prof(KX_K_MISC, B, V, k, s);
+  const dim3 grid((unsigned)B), block(256);
+#define KX_CONTRAST_CAND(CAP)                                                                                                    \
+  hipLaunchKernelGGL(contrast_candidates_kernel<CAP>, grid, block, 0, s, logits, (long long)ld, (long long)rows, (int)V, (int)k, \
+                     (const int*)chosen, (long long)k_prev, finished, (long long*)step_tokens, prob, (long long*)cand_id, cand_prob, \
+                     (long long)out_ld, (long long)out_col)
+  if (k <= 4) KX_CONTRAST_CAND(4);                    // kx_step_logprobs' own buckets: the same instantiation of row_top
+  else if (k <= 8) KX_CONTRAST_CAND(8);
+  else KX_CONTRAST_CAND(16);
+#undef KX_CONTRAST_CAND
+  KX_CHECK_LAUNCH("kx_contrast_candidates");
+  return KX_OK;
 }

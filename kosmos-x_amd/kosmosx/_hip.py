@@ -21,6 +21,7 @@ KX_ACT_NONE, KX_ACT_GELU, KX_ACT_QUICK_GELU = 0, 1, 2
 KX_ATTN_FULL, KX_ATTN_CAUSAL = 0, 1
 KX_RAGGED_ERR_TABLE, KX_RAGGED_ERR_CACHE = 1, 2
 KX_RAGGED_ERR_GATHER = 4
+KX_RAGGED_ERR_COMMIT = 8
 KX_TUNE_LN_VARIANT = 0   # kx_set_tuning key (csrc/kx_gemm_plan.h): 0 shipped rule, 1 workgroup-per-row kernel, else wave-per-row kernel
 KX_ACT_RELU, KX_ACT_SWISH = 5, 6
 ACTS = {"none": KX_ACT_NONE, "gelu": KX_ACT_GELU, "quick_gelu": KX_ACT_QUICK_GELU, "relu": KX_ACT_RELU, "swish": KX_ACT_SWISH}
@@ -362,6 +363,13 @@ SYMBOLS = {
     "kx_patchify": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, vp]),
     "kx_vit_assemble": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, vp]),
     "kx_attention_backward": (C.c_int, [vp, vp, vp, i32] + [vp] * 7 + [i64] * 7 + [i32, i32, vp]),
+    # contrastive search on the device (header: "Contrastive search on the device")
+    "kx_contrast_candidates": (C.c_int, [vp, i64, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "kx_contrast_hidden": (C.c_int, [C.POINTER(DecoderWeights), vp, vp, i64, i64, i32, i32, vp, vp, i64, vp, vp]),
+    "kx_contrast_scratch_bytes": (C.c_size_t, [i64, i32, i64]),
+    "kx_contrast_select": (C.c_int, [vp, vp, vp, i64, i32, i64, i64, vp, i64, vp, f32, f32, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp,
+                                     vp, vp, C.c_size_t, vp, vp]),
+    "kx_kv_cache_commit": (C.c_int, [vp] * 4 + [i64, i64, i32, i64, i64, i64, i32, vp, vp, vp, vp, vp]),
 }
 
 

@@ -85,7 +85,15 @@ mixed batch gets the bits of a call of its own.  Presence and frequency penaltie
 (kx_shape_logits_rows); a row's ``max_new_tokens`` is a budget the sampler launch itself enforces through ``finished``.  Without the
 keyword, or with B empty dicts: no buffer, no upload, the entry points above.
 
-Not offered: per-row ``eos_token_id``, constraints and stop sequences, row options with beams or prompt lookup; guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
+Contrastive search (``penalty_alpha`` = a with ``top_k`` = k candidates, ``output_contrast``; contrast_loop): every step takes the k most
+likely next tokens of each sequence (kx_contrast_candidates: kx_step_logprobs' selection on the row the previous choice addresses), steps
+them as B * k rows over the sequences' own caches — the prefix step, prefix = the sequence so far, tail = one row — takes the unit
+hidden rows (kx_contrast_hidden), chooses per sequence the candidate with the largest (1 - a) * p - a * max similarity to a history of
+unit vectors that starts with the prefill's rows (kx_contrast_select) and commits its K/V row (kx_kv_cache_commit).  Five launches
+beside the step; the host reads only the stop poll.  A mode of its own: with None nothing of it exists.
+
+Not offered: contrastive search with any sampler, processor, constraint, automaton, guidance, beams, sessions, speculation or
+chunked prefill, ``top_k`` above 16; per-row ``eos_token_id``, constraints and stop sequences, row options with beams or prompt lookup; guidance with beams, prompt lookup, parallel sampling or sessions, an unconditional row without the spliced
 image, log-probs of the guided distribution; the shaping keywords with beams or prompt lookup, penalties over the prompt, counts that survive a session
 turn; the truncation samplers with beams or prompt lookup, ``min_tokens_to_keep`` above 1, log-probs of the truncated distribution; token automata with prompt lookup, per-row tables other than through TokenAutomaton.union, an automaton
 that reads the prompt, stop strings and regular expressions (the tokenizer); log-probs with beams or prompt lookup, of the processed distribution, or top-k out of ``score()``; beams that share their prompt's cache rows, forking a session, parallel sampling with prompt lookup or
@@ -143,22 +151,24 @@ class LoopOptions:
     shape: object                       # check_shape_args' dict, or None
     sampler: dict                       # what the sampler launch takes beyond its old arguments: min_p, check_truncation_args' keywords
     guidance: object                    # check_guidance_args' scale, or None
+    contrast: object = None             # check_contrast_args' dict (alpha, k, trace), or None: contrast_loop runs the call when set
     rows: object = None                 # check_row_options' table: B dicts holding every ROW_KEYS entry resolved, or None
 
     @classmethod
-    def resolved(cls, kw: dict, cons, starts, shape, truncation: dict, guide, rows=None):
+    def resolved(cls, kw: dict, cons, starts, shape, truncation: dict, guide, rows=None, contrast=None):
         """From the keyword arguments by name and what the checks returned for them."""
         min_p = {} if shape is None or shape["min_p"] == 0.0 else dict(min_p=shape["min_p"])
         return cls(**{f.name: kw[f.name] for f in dataclasses.fields(cls) if f.name in kw}, constraints=cons, shape=shape,
                    automaton=None if starts is None else (kw["token_automaton"], starts), sampler={**min_p, **truncation},
-                   guidance=None if guide is None else guide["scale"], rows=rows)
+                   guidance=None if guide is None else guide["scale"], rows=rows, contrast=contrast)
 
 
 def loop_options(vocab: int, batch: int, *, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
                  eos_token_id=None, pad_token_id=1, sequence_ids=None, eos_poll=8, output_logits=False, no_repeat_ngram_size=0,
                  bad_words_ids=None, min_new_tokens=0, stop_sequences=None, output_logprobs=False, top_logprobs=0,
                  token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                 guidance_scale=1.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None, max_new_tokens=None) -> LoopOptions:
+                 guidance_scale=1.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None, max_new_tokens=None,
+                 penalty_alpha=None, output_contrast=False) -> LoopOptions:
     """The plain loop's keyword arguments -> the LoopOptions generate_loop takes, or the ValueError of the first check that refuses
     one: check_constraint_args, check_logprob_args, check_automaton_args, check_shape_args, check_truncation_args,
     check_row_options, in this order (then the scale through check_guidance_args); host only.  ``vocab``: the model's; ``batch``: the rows B the per-row values are
@@ -218,15 +228,19 @@ def loop_options(vocab: int, batch: int, *, do_sample=False, temperature=1.0, to
     the ``skip`` snapshot keeps the log-prob slots behind the budget at 0.0 / -1.  With an automaton a spent budget is told from
     a dead end by the launch's kept count (0: no candidate), also when both fall into one launch.  With ``row_options`` the presence
     and frequency penalties are the rows' resolved ones alone: the shaping launch runs for a bias or a row's penalty, never for the
-    call's scalar that every row overrode.  None, or B empty dicts: no buffer, no upload, the entry points above."""
+    call's scalar that every row overrode.  None, or B empty dicts: no buffer, no upload, the entry points above.
+    ``penalty_alpha`` / ``output_contrast`` (check_contrast_args): contrastive search; the resolved dict travels as
+    ``LoopOptions.contrast`` and it is contrast_loop, not generate_loop, that runs such a call.  None: nothing of it exists."""
     kw = _keywords(locals(), "vocab", "batch")
     cons = check_constraint_args(vocab, **_own(check_constraint_args, kw))
     check_logprob_args(vocab, **_own(check_logprob_args, kw))
     starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
     shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
     truncation = check_truncation_args(**_own(check_truncation_args, kw))
+    contrast = check_contrast_args(vocab, **_own(check_contrast_args, kw))
     rows = check_row_options(vocab, batch, **_own(check_row_options, kw))
-    return LoopOptions.resolved(kw, cons, starts, shape, truncation, check_guidance_args(batch, **_own(check_guidance_args, kw)), rows)
+    return LoopOptions.resolved(kw, cons, starts, shape, truncation, check_guidance_args(batch, **_own(check_guidance_args, kw)), rows,
+                                contrast)
 
 
 def generate_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_tokens: torch.Tensor, max_new_tokens: int,
@@ -995,6 +1009,173 @@ def parallel_loop(decoder, prec: str, state: dict, logits: torch.Tensor, prompt_
                          N, opts, pos_shift=pos_shift, lengths=[plens[b] for b in seq], text_lengths=[tlens[b] for b in seq], prompt_rows=T)
 
 
+MAX_CONTRAST_K = 16                     # kx_contrast_candidates' k limit (kx_step_logprobs' top_n)
+
+
+def check_contrast_args(vocab: int, *, penalty_alpha=None, output_contrast=False, top_k=0, do_sample=False, num_beams=1,
+                        prompt_lookup_num_tokens=0, num_return_sequences=1, return_session=False, guidance_scale=1.0, row_options=None,
+                        token_automaton=None, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, stop_sequences=None,
+                        logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
+                        eta_cutoff=0.0, repetition_penalty=1.0, temperature=1.0, top_p=1.0, output_logprobs=False, prefill_chunk=None):
+    """ValueError (naming ``penalty_alpha``, or ``output_contrast`` without it) for what generate() refuses of contrastive search,
+    before the device check and any launch; after check_truncation_args, so every other keyword is already known to be good.
+    ``penalty_alpha`` None: off, returns None (no buffer, no launch, no entry point fetched).  A number in [0, 1] (no bool, finite)
+    turns contrastive search on and makes ``top_k`` the number of candidates, 1..16 and at most the vocabulary.  It is a
+    deterministic mode of its own: together with sampling, beams, prompt lookup, parallel samples, sessions, guidance, row options,
+    an automaton, a constraint, a shaping or truncation keyword, a repetition penalty, a temperature, top-p, log-probs or a chunked
+    prefill it is refused.  Returns dict(alpha, k, trace)."""
+    import math
+    if penalty_alpha is None:
+        if output_contrast:
+            raise ValueError("output_contrast returns the trace of contrastive search: it needs penalty_alpha")
+        return None
+    a = penalty_alpha
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or not 0.0 <= a <= 1.0:
+        raise ValueError(f"penalty_alpha must be a number in [0, 1] (or None: off), got {a!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= MAX_CONTRAST_K:
+        raise ValueError(f"penalty_alpha = {a!r} makes top_k the number of candidates per step: it must be an integer in "
+                         f"1..{MAX_CONTRAST_K}, got {top_k!r}")
+    if top_k > vocab:
+        raise ValueError(f"penalty_alpha = {a!r}: top_k = {top_k} candidates exceed the vocabulary of {vocab}")
+    why = {
+        "do_sample": "contrastive search is deterministic: it chooses among the top_k candidates by score",
+        "num_beams": "beams rank whole hypotheses; a contrastive choice per beam is a search of its own",
+        "prompt_lookup_num_tokens": "a verify step accepts greedy picks, which contrastive search does not make",
+        "num_return_sequences": "the call is deterministic: the copies of one prompt would all be equal",
+        "return_session": "a session keeps the plain loop's state; the history of unit vectors is not part of it",
+        "guidance_scale": "the candidates would be taken from the guided row but stepped as unguided ones",
+        "row_options": "the rows' options are the sampler's",
+        "token_automaton": "the candidates are the model's own top_k: a ban would have to be applied before they are taken",
+        "no_repeat_ngram_size": "the constraints edit the row the sampler reads, and no sampler runs",
+        "bad_words_ids": "the constraints edit the row the sampler reads, and no sampler runs",
+        "min_new_tokens": "the constraints edit the row the sampler reads, and no sampler runs",
+        "stop_sequences": "the constraints edit the row the sampler reads, and no sampler runs",
+        "logit_bias": "the shaping launch edits the row the sampler reads, and no sampler runs",
+        "presence_penalty": "the shaping launch edits the row the sampler reads, and no sampler runs",
+        "frequency_penalty": "the shaping launch edits the row the sampler reads, and no sampler runs",
+        "min_p": "it is a stage of the sampler, and no sampler runs",
+        "typical_p": "it is a stage of the sampler, and no sampler runs",
+        "epsilon_cutoff": "it is a stage of the sampler, and no sampler runs",
+        "eta_cutoff": "it is a stage of the sampler, and no sampler runs",
+        "repetition_penalty": "the degeneration penalty is what contrastive search uses against repetition",
+        "temperature": "candidate_prob is the model's own probability",
+        "top_p": "the candidates are the top_k, nothing else",
+        "output_logprobs": "the trace (output_contrast) already holds the candidates' probabilities",
+        "prefill_chunk": "the history is filled from the one-piece prefill's residual rows",
+    }
+    on = dict(do_sample=bool(do_sample), num_beams=num_beams not in (1, None),
+              prompt_lookup_num_tokens=prompt_lookup_num_tokens not in (0, None), num_return_sequences=num_return_sequences not in (1, None),
+              return_session=bool(return_session), guidance_scale=guidance_scale != 1.0, row_options=row_options is not None,
+              token_automaton=token_automaton is not None, no_repeat_ngram_size=no_repeat_ngram_size != 0,
+              bad_words_ids=bad_words_ids is not None, min_new_tokens=min_new_tokens != 0, stop_sequences=stop_sequences is not None,
+              logit_bias=logit_bias is not None, presence_penalty=presence_penalty != 0.0, frequency_penalty=frequency_penalty != 0.0,
+              min_p=min_p != 0.0, typical_p=typical_p != 1.0, epsilon_cutoff=epsilon_cutoff != 0.0, eta_cutoff=eta_cutoff != 0.0,
+              repetition_penalty=repetition_penalty != 1.0, temperature=temperature != 1.0, top_p=top_p != 1.0,
+              output_logprobs=bool(output_logprobs), prefill_chunk=prefill_chunk is not None)
+    for name, bad in on.items():
+        if bad:
+            raise ValueError(f"penalty_alpha = {a!r} (contrastive search) is not offered together with {name}: {why[name]}; see "
+                             "DESIGN.md §8")
+    return dict(alpha=float(a), k=top_k, trace=bool(output_contrast))
+
+
+def contrast_loop(decoder, prec: str, state: dict, logits: torch.Tensor, max_new_tokens: int, opts: LoopOptions, *, pos_shift: int = 0,
+                  lengths=None):
+    """Contrastive search on a prefilled state (``opts.contrast``: check_contrast_args' dict): ``logits`` [B, T, V] the one-piece
+    prefill's output, ``state`` the incremental state it filled with the final residual rows kept (state["residual"], [B, T, D]),
+    ``lengths`` the ragged batch's rows per sequence (spliced rows included; None: T for every row), ``pos_shift`` as in generate_loop.
+    Sequence b has P_b cache rows, an int32 device word repeated k times ([B * k]: the positions AND the prefix lengths of the step).
+    Every buffer is allocated before the first step.  Per token, five launches beside the step:
+    kx_contrast_candidates (the k ids and probabilities of the sequence's current logits row — row b * k + chosen[b] of the previous
+    step's [B * k, V] logits, addressed, not copied — written as the step's tokens), kx_decoder_decode_step_prefix at M = B * k rows
+    (prefix = the sequence's own caches, prefix_seq[r] = r // k, tails [L, M, heads, 1, 64]), kx_contrast_hidden (the M unit hidden
+    rows), kx_contrast_select (two launches: the partial maxima over the history, then the choice, which also appends the chosen
+    unit vector to the history, writes the token and the trace and sets ``finished`` on the EOS) and kx_kv_cache_commit (the chosen
+    tail row into cache row P_b; P_b += 1).  ``output_logits`` adds one indexed copy per token.  The host reads the stop poll (every
+    ``eos_poll`` tokens, with an ``eos_token_id``) and, once after the last step, the kernels' sticky error word.
+    Returns the tokens int64 [B, n]; then the fp32 [B, n, V] logits with ``output_logits`` — column g the model's own row step g's
+    candidates were taken from; then with the trace a dict: candidate_id int64 / candidate_prob / candidate_penalty fp32 [B, n, k],
+    chosen int32 [B, n], history fp32 [B, cap, D] (the unit vectors), history_len int32 [B]."""
+    c = opts.contrast
+    k, alpha, trace = c["k"], c["alpha"], c["trace"]
+    eos, pad, N = opts.eos_token_id, int(opts.pad_token_id), int(max_new_tokens)
+    B, T, V = logits.shape
+    dev = logits.device
+    M = B * k
+    plens = [T] * B if lengths is None else list(lengths)
+    kc, vc = state["kcache"], state["vcache"]
+    L, _, nh, cap, hd = kc.shape
+    D = nh * hd
+    w = decoder._pack(state["prec"])[0]
+    resid = state.pop("residual")
+    state.pop("keep_residual", None)
+    # every buffer before the first step
+    lens_dev = torch.tensor(plens, dtype=torch.int32, device=dev)
+    history = torch.zeros((B, cap, D), dtype=torch.float32, device=dev)
+    ops.contrast_hidden(w, resid, history, lengths=lens_dev)
+    del resid
+    hist_len = lens_dev.clone()
+    positions = lens_dev.repeat_interleave(k).contiguous()                # P_b, k times: the step's positions and prefix lengths
+    seq = torch.arange(M, dtype=torch.int32, device=dev) // k
+    state.update(positions=positions, pos_max=max(plens))
+    state["prefix"] = dict(ktail=torch.empty((L, M, nh, 1, hd), dtype=kc.dtype, device=dev),
+                           vtail=torch.empty((L, M, nh, 1, hd), dtype=kc.dtype, device=dev), prefix_seq=seq.to(torch.int32), prefix_len=positions)
+    decoder._ragged_scratch(state, dev, rows=M)
+    err = state["error"]
+    out = torch.full((B, N), pad, dtype=torch.int64, device=dev)
+    step_tokens = torch.zeros(M, dtype=torch.int64, device=dev)
+    prob = torch.zeros(M, dtype=torch.float32, device=dev)
+    u = torch.empty((M, D), dtype=torch.float32, device=dev)
+    nxt = torch.full((B,), pad, dtype=torch.int64, device=dev)
+    chosen = torch.zeros(B, dtype=torch.int32, device=dev)
+    finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+    scratch = ops.contrast_scratch(B, k, cap, dev)
+    step_logits = torch.empty((M, V), dtype=torch.float32, device=dev)
+    cand_id = cand_prob = cand_pen = chosen_tr = None
+    if trace:
+        cand_id = torch.full((B, N, k), -1, dtype=torch.int64, device=dev)
+        cand_prob = torch.zeros((B, N, k), dtype=torch.float32, device=dev)
+        cand_pen = torch.zeros((B, N, k), dtype=torch.float32, device=dev)
+        chosen_tr = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+    kept = torch.empty((B, N, V), dtype=torch.float32, device=dev) if opts.output_logits else None
+    rows_b = torch.arange(B, device=dev) * k
+    first = logits[torch.arange(B, device=dev), lens_dev.long() - 1] if lengths is not None else logits[:, -1]     # [B, V]
+    n = 0
+    for g in range(N):
+        if g == 0:
+            if kept is not None:
+                kept[:, 0] = first
+            ops.contrast_candidates(first, k=k, step_tokens=step_tokens, prob=prob, finished=finished, cand_id=cand_id,
+                                    cand_prob=cand_prob, col=0)
+        else:
+            if kept is not None:
+                kept[:, g] = step_logits[rows_b + chosen.long()]
+            ops.contrast_candidates(step_logits, k=k, step_tokens=step_tokens, prob=prob, chosen=chosen, k_prev=k, finished=finished,
+                                    cand_id=cand_id, cand_prob=cand_prob, col=g)
+        decoder._forward_incremental(None, state, None, prec, next_token=step_tokens, pos_shift=pos_shift, logits_out=step_logits)
+        ops.contrast_hidden(w, state["x_step"], u, workspace=state["step_ws"], prec=state["step_pid"])
+        ops.contrast_select(u, prob, history, hist_rows=positions, p_stride=k, hist_len=hist_len, alpha=alpha, step_tokens=step_tokens,
+                            finished=finished, next_token=nxt, chosen=chosen, scratch=scratch, error_word=err, eos_token_id=eos,
+                            pad_token_id=pad, out_tokens=out, cand_penalty=cand_pen, chosen_trace=chosen_tr, col=g)
+        ops.kv_cache_commit(state["prefix"]["ktail"], state["prefix"]["vtail"], kc, vc, chosen, positions, err, finished=finished)
+        n = g + 1
+        if n == N:
+            break
+        if eos is not None and opts.eos_poll > 0 and n % opts.eos_poll == 0:
+            done, word = torch.stack([finished.min().to(torch.int32), err[0]]).tolist()      # the loop's only device-to-host read
+            _raise_position_error(word, state)
+            if done:
+                break
+    _raise_position_error(int(err.item()), state)
+    res = [out[:, :n]]
+    if kept is not None:
+        res.append(kept[:, :n])
+    if trace:
+        res.append(dict(candidate_id=cand_id[:, :n], candidate_prob=cand_prob[:, :n], candidate_penalty=cand_pen[:, :n],
+                        chosen=chosen_tr[:, :n], history=history, history_len=hist_len))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 MAX_STEP_ROWS = 16                      # the weight-streaming step's rows: B * (D + 1) of a lookup step
 
 
@@ -1231,7 +1412,8 @@ def check_prefill_chunk(prefill_chunk):
     return prefill_chunk
 
 
-def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True, chunk=None, capacity=None):
+def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0, budget: bool = True, chunk=None, capacity=None,
+             keep_residual: bool = False):
     """The prompt's prefill, under torch.no_grad(): ``prompt`` as run_generate takes it, ``new_rows`` (+ ``spare``) the positions the
     caller will add, checked against the tables when ``budget``.  Returns the tokens as prefilled (trimmed to the longest prompt, the
     padding masked), the host lengths (None: a uniform batch), T (prefix rows included), the state, the prefill's logits and the
@@ -1240,7 +1422,8 @@ def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0,
     with the XPos centring of the whole T (state["xpos_centre"]), every later slice by Decoder._extend — the first slice always
     writes its C logits rows, a later one only if it holds a row the loops read, last position or len_b - 1; those rows are
     returned as [B, 1, V] with ``prompt_rows`` = T.
-    ``capacity`` (sessions): the cache rows per sequence instead of T + ``new_rows``; the budget is checked against it too."""
+    ``capacity`` (sessions): the cache rows per sequence instead of T + ``new_rows``; the budget is checked against it too.
+    ``keep_residual`` (contrastive search; one-piece prefill only): the prefill's final residual rows stay in state["residual"]."""
     tokens, lens = prompt["tokens"], None
     if prompt_lengths is not None:
         lens = resolve_prompt_lengths(prompt_lengths, tokens.shape[0], tokens.shape[1], min_len=prompt["min_len"])
@@ -1259,6 +1442,8 @@ def _prefill(model, prompt: dict, prompt_lengths, new_rows: int, spare: int = 0,
     # a score() candidate reads cache rows < len_b only.
     passed_x = prompt["passed_x"](tokens)                                   # (the prompt's ids are range-checked here or in the prefill, once)
     state = {"max_len": T + new_rows + spare if capacity is None else capacity}   # (rejected drafts still occupy table and cache rows)
+    if keep_residual:
+        state["keep_residual"] = True
     if chunk is None or chunk >= T:
         logits = model.decoder._forward_incremental(tokens if passed_x is None else None, state, passed_x, model.precision)
         return tokens, lens, T, state, logits, None
@@ -1301,12 +1486,17 @@ def run_generate(model, prompt: dict, max_new_tokens: int, kw: dict):
     starts = check_automaton_args(vocab, batch, **_own(check_automaton_args, kw))
     shape = check_shape_args(vocab, batch, **_own(check_shape_args, kw))
     truncation = check_truncation_args(**_own(check_truncation_args, kw))
+    contrast = check_contrast_args(vocab, **_own(check_contrast_args, kw))
     rows = check_row_options(vocab, batch, max_new_tokens=max_new_tokens, **_own(check_row_options, kw))
     chunk = check_prefill_chunk(kw["prefill_chunk"])
     capacity = check_session_args(decoder, beams=beams, drafts=drafts, **_own(check_session_args, kw))
     prompt["check"](**({} if guide is None or kw["negative_prompt_ids"] is None else dict(negative_prompt_ids=kw["negative_prompt_ids"])))
-    opts = LoopOptions.resolved(kw, cons, starts, shape, truncation, guide, rows)   # what the four plain-loop paths below take
+    opts = LoopOptions.resolved(kw, cons, starts, shape, truncation, guide, rows, contrast)   # what the plain-loop paths below take
     with torch.no_grad():
+        if contrast is not None:                                          # (everything below but ragged prompts was refused with it)
+            tokens, lens, T, state, logits, _ = _prefill(model, prompt, kw["prompt_lengths"], max_new_tokens, keep_residual=True)
+            return contrast_loop(decoder, prec, state, logits, max_new_tokens, opts, pos_shift=prompt["pos_shift"],
+                                 lengths=None if lens is None else [prompt["prefix_rows"] + l for l in lens])
         if guide is not None:
             # every sequence as two rows of one ragged batch: the prompt (rows 0..B-1) and its negative (rows B..2B-1), prefilled
             # through _prefill unchanged; generate_loop gives the sampler the first B rows and feeds both halves the same token
@@ -1362,7 +1552,8 @@ def _raise_position_error(word: int, state: dict):
     """The sticky word of the ragged step kernels (kx_ragged_error): a row's device position left the table / the cache."""
     if word:
         what = " and ".join(name for bit, name in ((H.KX_RAGGED_ERR_TABLE, "the position / XPos tables"),
-                                                   (H.KX_RAGGED_ERR_CACHE, "the KV cache")) if word & bit)
+                                                   (H.KX_RAGGED_ERR_CACHE, "the KV cache"),
+                                                   (H.KX_RAGGED_ERR_COMMIT, "the rows a cache commit may write")) if word & bit)
         raise IndexError(f"index out of range in self: a row's device position left {what} (host-side maximum "
                          f"{state.get('pos_max')}, cache of {state.get('max_len')} rows); that row's step wrote nothing")
 

@@ -970,6 +970,8 @@ class Decoder(_PackedMixin, nn.Module):
                                            state["vcache"].data_ptr(), Tmax, buf.data_ptr(), buf.numel(),
                                            H.PRECS[prec], _stream()), "kx_decoder_prefill")
             state.update(len=T, max_len=Tmax, batch=B, prec=prec)
+            if state.get("keep_residual"):                 # contrastive search: the final residual rows (kx_decoder_prefill leaves them in x)
+                state["residual"] = x
             return logits
         t, Tmax, B = state["len"], state["max_len"], state["batch"]           # ---- later steps: one token ----
         positions = state.get("positions")
@@ -1090,6 +1092,7 @@ class Decoder(_PackedMixin, nn.Module):
         buf = self._ws.get(need, dev)
         caches = (state["kcache"].data_ptr(), state["vcache"].data_ptr(), Tmax)
         if prefix is not None:
+            state["step_ws"], state["step_pid"] = buf, pid    # (what kx_contrast_hidden asks the step's residual form with)
             fn, rows = "kx_decoder_decode_step_prefix", (M, positions.data_ptr(), prefix["prefix_seq"].data_ptr(),
                                                          prefix["prefix_len"].data_ptr(), B)
             caches += (kt.data_ptr(), vt.data_ptr(), kt.shape[3])
@@ -1337,7 +1340,7 @@ class Kosmos(nn.Module):
                  prefill_chunk=None, return_session=False, session_capacity=None, output_logprobs=False, top_logprobs=0,
                  token_automaton=None, automaton_start=None, logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
                  guidance_scale=1.0, negative_prompt_ids=None, negative_prompt_lengths=None, negative_images=None,
-                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None):
+                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, row_options=None, penalty_alpha=None, output_contrast=False):
         """Continue the multimodal prompt by up to ``max_new_tokens`` tokens -> int64 [B, n_new] (the new tokens only;
         rows that drew ``eos_token_id`` are padded with ``pad_token_id`` after it); with ``output_logits`` also the fp32
         [B, n_new, vocab] logits each token was drawn from.  Tower -> resampler -> splice as in forward(), prefill of the
@@ -1465,7 +1468,17 @@ class Kosmos(nn.Module):
         ``pad_token_id`` like a row that drew an EOS.  It composes with ``prompt_lengths``, parallel sampling, guidance, sessions
         (every turn takes its own) and everything the plain loop composes with; with ``num_beams`` > 1 or
         ``prompt_lookup_num_tokens`` > 0, a wrong length, an unknown key or a value the scalar keyword would refuse: ValueError naming
-        ``row_options[b]['key']``.  None or B empty dicts change nothing: the same launches."""
+        ``row_options[b]['key']``.  None or B empty dicts change nothing: the same launches.
+        ``penalty_alpha`` = a in [0, 1] (None: off): contrastive search (kosmosx.generation.contrast_loop).  ``top_k`` = k in 1..16 is
+        then the number of candidates: every step takes the k most likely next tokens, runs them as k rows over the sequence's own
+        KV cache in one pass over the weights and emits the one with the largest (1 - a) * p - a * max cosine similarity of its
+        hidden state (decoder.layer_norm of the final residual, unit length) to those of everything before it — the image rows
+        included, which are ordinary history rows.  Deterministic; needs ``do_sample=False``.  It composes with ``prompt_lengths``,
+        ``eos_token_id`` / ``pad_token_id`` / ``eos_poll`` and ``output_logits`` (column g: the model's own row step g's candidates
+        were taken from); ``output_contrast=True`` appends a dict of device tensors — candidate_id int64, candidate_prob and
+        candidate_penalty fp32 [B, n, k], chosen int32 [B, n], history fp32 [B, cap, D] and history_len int32 [B].  With anything
+        else that changes what is drawn or how the call runs: ValueError naming ``penalty_alpha``.  None changes
+        nothing: the same launches."""
         kw = generation._keywords(locals(), "self", "text_tokens", "images", "max_new_tokens")
         if not isinstance(text_tokens, torch.Tensor) or not isinstance(images, torch.Tensor):
             raise TypeError("text_tokens and images must be instances of torch.Tensor")
@@ -1645,7 +1658,7 @@ class KosmosLanguage(nn.Module):
                  session_capacity=None, output_logprobs=False, top_logprobs=0, token_automaton=None, automaton_start=None,
                  logit_bias=None, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, guidance_scale=1.0,
                  negative_prompt_ids=None, negative_prompt_lengths=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
-                 row_options=None):
+                 row_options=None, penalty_alpha=None, output_contrast=False):
         """Continue the prompt ``x`` [B, T] by up to ``max_new_tokens`` tokens -> int64 [B, n_new]; see Kosmos.generate
         (``prompt_lengths``: row b's prompt is ``x[b, :prompt_lengths[b]]``, at least one token; ``num_return_sequences`` = n > 1
         with ``do_sample``: n samples per prompt over one shared prompt KV cache, int64 [B * n, n_new], as there; ``num_beams`` and the
@@ -1660,7 +1673,8 @@ class KosmosLanguage(nn.Module):
         ``negative_prompt_ids`` and ``negative_prompt_lengths``: classifier-free guidance against a negative prompt, as there —
         a negative prompt has at least one token, and with ``negative_prompt_ids`` None row b's unconditional context is its last
         prompt token, as in `transformers`; ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff``: the truncation samplers inside the
-        sampler launch, as there; ``row_options``: B dicts of per-row sampling options and budgets, as there)."""
+        sampler launch, as there; ``row_options``: B dicts of per-row sampling options and budgets, as there; ``penalty_alpha`` and
+        ``output_contrast``: contrastive search over ``top_k`` candidates per step, as there)."""
         kw = generation._keywords(locals(), "self", "x", "max_new_tokens")
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be an instance of torch.Tensor")

@@ -1229,3 +1229,193 @@ def kv_cache_gather(src_k, src_v, dst_k, dst_v, t, src_row, error_word, layout="
     H.check(H.load().kx_kv_cache_gather(src_k.data_ptr(), src_v.data_ptr(), dst_k.data_ptr(), dst_v.data_ptr(), L, Bs, Bd, nh,
                                         Tmax, int(t), src_k.element_size(), src_row.data_ptr(), error_word.data_ptr(), _stream()),
             "kx_kv_cache_gather")
+
+
+# ---- contrastive search on the device (include/kosmosx_hip.h, "Contrastive search on the device") ----
+
+def _contrast_tensor(fn, name, t, dtype, shape=None, optional=False):
+    if t is None:
+        if optional:
+            return
+        raise TypeError(f"{fn}: {name} is missing")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise TypeError(f"{fn}: {name} is a contiguous {dtype} tensor" + (f" of shape {list(shape)}" if shape is not None else ""))
+
+
+def _contrast_k(fn, k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 16:
+        raise ValueError(f"{fn}: k = {k!r} is outside 1..16")
+    return k
+
+
+def contrast_candidates(logits, *, k, step_tokens, prob, chosen=None, k_prev=1, finished=None, cand_id=None, cand_prob=None, col=0):
+    """kx_contrast_candidates: the k most likely ids of every sequence's current logits row and their probabilities.  ``logits``
+    fp32 [rows, V] with unit column stride; sequence b reads row b * k_prev + chosen[b] (``chosen`` int32 [B]) or, without ``chosen``,
+    row b.  Writes ``step_tokens`` int64 [B * k], ``prob`` fp32 [B * k] and, when given, column ``col`` of ``cand_id`` int64 /
+    ``cand_prob`` fp32 [B, N, k]: the ids and expf(log-prob) of step_logprobs(top_n=k) on that row, bit for bit.  Rows with
+    ``finished`` [B] uint8 set write nothing.  Returns None."""
+    fn = "contrast_candidates"
+    _need_cuda(logits, step_tokens, prob, chosen, finished, cand_id, cand_prob)
+    k = _contrast_k(fn, k)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise TypeError(f"{fn}: logits is a non-empty fp32 [rows, V] tensor with unit column stride")
+    rows, V = logits.shape
+    if rows > 1 and logits.stride(0) < V:
+        raise TypeError(f"{fn}: logits rows overlap (row stride {logits.stride(0)} < V = {V})")
+    if k > V:
+        raise ValueError(f"{fn}: k = {k} exceeds the vocabulary of {V}")
+    if step_tokens is None or step_tokens.dim() != 1 or step_tokens.shape[0] % k:
+        raise TypeError(f"{fn}: step_tokens is a contiguous int64 [B * k] tensor")
+    B = step_tokens.shape[0] // k
+    _contrast_tensor(fn, "step_tokens", step_tokens, torch.int64, (B * k,))
+    _contrast_tensor(fn, "prob", prob, torch.float32, (B * k,))
+    _contrast_tensor(fn, "chosen", chosen, torch.int32, (B,), optional=True)
+    _contrast_tensor(fn, "finished", finished, torch.uint8, (B,), optional=True)
+    if chosen is None:
+        k_prev = 1
+    if isinstance(k_prev, bool) or not isinstance(k_prev, int) or not 1 <= k_prev <= 16:
+        raise ValueError(f"{fn}: k_prev = {k_prev!r} is outside 1..16")
+    if rows < B * k_prev:
+        raise ValueError(f"{fn}: logits has {rows} rows, fewer than B * k_prev = {B * k_prev}")
+    N = 1
+    if (cand_id is None) != (cand_prob is None):
+        raise TypeError(f"{fn}: cand_id and cand_prob are given together")
+    if cand_id is not None:
+        if cand_id.dim() != 3:
+            raise TypeError(f"{fn}: cand_id is a contiguous int64 [{B}, N, {k}] tensor")
+        N = cand_id.shape[1]
+        _contrast_tensor(fn, "cand_id", cand_id, torch.int64, (B, N, k))
+        _contrast_tensor(fn, "cand_prob", cand_prob, torch.float32, (B, N, k))
+        if isinstance(col, bool) or not isinstance(col, int) or not 0 <= col < N:
+            raise ValueError(f"{fn}: col = {col!r} is outside the {N} columns of cand_id")
+    H.check(H.load().kx_contrast_candidates(logits.data_ptr(), logits.stride(0) if rows > 1 else max(logits.stride(0), V), rows, B, V, k,
+                                            H.ptr(chosen), k_prev, H.ptr(finished), step_tokens.data_ptr(), prob.data_ptr(),
+                                            H.ptr(cand_id), H.ptr(cand_prob), N, int(col) if cand_id is not None else 0, _stream()),
+            "kx_contrast_candidates")
+
+
+def contrast_hidden(weights, x, out, *, workspace=None, prec=None, lengths=None, residual_out=None):
+    """kx_contrast_hidden: the fp32 unit vectors u = h / ||h||, h = decoder.layer_norm of the rows of the final residual stream.
+    ``weights``: the decoder's bound kx_decoder_weights.  ``x`` fp32 [M, 1, D] or [M, D] with ``workspace`` (the tensor the step ran
+    in) and ``prec`` (the step's precision id): the rows of the decode step that has just run, ``out`` fp32 [M, D].  Without
+    ``workspace``: ``x`` fp32 [B, T, D] rows as they are (a prefill's), written to out[b, t] of ``out`` fp32 [B, cap >= T, D];
+    ``lengths`` int32 [B]: rows t >= lengths[b] are not written.  ``residual_out`` fp32, as many elements as ``x``: the residual rows
+    the kernel normalised (x, or the pair x + xb of a step that ran its two-workgroup form).  Returns ``out``."""
+    fn = "contrast_hidden"
+    _need_cuda(x, out, workspace, lengths, residual_out)
+    if residual_out is not None and (residual_out.dtype != torch.float32 or not residual_out.is_contiguous() or residual_out.numel() != x.numel()):
+        raise TypeError(f"{fn}: residual_out is a contiguous fp32 tensor of x's size")
+    D = int(weights.dim)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[-1] != D or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.shape[-1] != D:
+        raise TypeError(f"{fn}: x and out are contiguous fp32 tensors whose last dimension is the model's {D}")
+    if workspace is not None:
+        M = x.numel() // D
+        if prec is None or lengths is not None or out.numel() != M * D:
+            raise TypeError(f"{fn}: a step's rows take prec, no lengths and out [{M}, {D}]")
+        B, T, step, ld, ws = M, 1, 1, D, workspace.data_ptr()
+    else:
+        if x.dim() != 3 or out.dim() != 3 or out.shape[0] != x.shape[0] or out.shape[1] < x.shape[1]:
+            raise TypeError(f"{fn}: x is [B, T, {D}] and out [B, cap >= T, {D}]")
+        B, T, step, ld, ws, prec = x.shape[0], x.shape[1], 0, out.shape[1] * D, 0, 0
+        _contrast_tensor(fn, "lengths", lengths, torch.int32, (B,), optional=True)
+    H.check(H.load().kx_contrast_hidden(C.byref(weights), x.data_ptr(), ws, B, T, int(prec), step, H.ptr(lengths), out.data_ptr(), ld,
+                                        H.ptr(residual_out), _stream()), "kx_contrast_hidden")
+    return out
+
+
+def contrast_scratch(B, k, cap, device):
+    """The fp32 scratch contrast_select takes for B sequences, k candidates and ``cap`` history rows (partial maxima)."""
+    return torch.empty(max(H.load().kx_contrast_scratch_bytes(B, k, cap) // 4, 1), dtype=torch.float32, device=device)
+
+
+def contrast_select(u, prob, history, *, hist_rows, hist_len, alpha, step_tokens, finished, next_token, chosen, scratch, error_word,
+                    p_stride=1, eos_token_id=None, pad_token_id=1, out_tokens=None, cand_penalty=None, chosen_trace=None, col=0):
+    """kx_contrast_select: the degeneration penalty and the choice.  ``u`` fp32 [B * k, D] unit vectors of the candidates, ``prob``
+    fp32 [B * k], ``history`` fp32 [B, cap, D]; P_b = hist_rows[b * p_stride] (int32).  penalty_j = max over i < P_b of
+    dot(u[b * k + j], history[b, i]); score_j = fp32(1 - alpha) * p_j - alpha * penalty_j; the largest score wins, the lowest j among
+    equal ones.  Writes next_token [B] int64, chosen [B] int32, history[b, P_b], hist_len[b] = P_b + 1, finished[b] on the EOS and
+    column ``col`` of out_tokens int64 [B, N], chosen_trace int32 [B, N], cand_penalty fp32 [B, N, k] (each optional).  A finished row
+    writes its pad token only.  Returns None."""
+    import ctypes
+    fn = "contrast_select"
+    _need_cuda(u, prob, history, hist_rows, hist_len, step_tokens, finished, next_token, chosen, scratch, error_word, out_tokens,
+               cand_penalty, chosen_trace)
+    if history is None or history.dim() != 3:
+        raise TypeError(f"{fn}: history is a contiguous fp32 [B, cap, D] tensor")
+    B, cap, D = history.shape
+    if u is None or u.dim() != 2 or u.shape[1] != D or u.shape[0] % B or not 1 <= u.shape[0] // B <= 16:
+        raise TypeError(f"{fn}: u is a contiguous fp32 [B * k, {D}] tensor, k in 1..16")
+    k = u.shape[0] // B
+    _contrast_tensor(fn, "history", history, torch.float32)
+    _contrast_tensor(fn, "u", u, torch.float32)
+    _contrast_tensor(fn, "prob", prob, torch.float32, (B * k,))
+    _contrast_tensor(fn, "step_tokens", step_tokens, torch.int64, (B * k,))
+    _contrast_tensor(fn, "hist_len", hist_len, torch.int32, (B,))
+    _contrast_tensor(fn, "finished", finished, torch.uint8, (B,))
+    _contrast_tensor(fn, "next_token", next_token, torch.int64, (B,))
+    _contrast_tensor(fn, "chosen", chosen, torch.int32, (B,))
+    _contrast_tensor(fn, "scratch", scratch, torch.float32)
+    if isinstance(p_stride, bool) or not isinstance(p_stride, int) or p_stride < 1:
+        raise ValueError(f"{fn}: p_stride = {p_stride!r} must be a positive integer")
+    _contrast_tensor(fn, "hist_rows", hist_rows, torch.int32)
+    if hist_rows.numel() < (B - 1) * p_stride + 1:
+        raise TypeError(f"{fn}: hist_rows holds fewer than (B - 1) * p_stride + 1 = {(B - 1) * p_stride + 1} words")
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError(f"{fn}: error_word must be an int32 [1] tensor on the device (the kernels' sticky word)")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{fn}: alpha = {alpha!r} must be a number in [0, 1]")
+    a32 = ctypes.c_float(alpha).value
+    oma = ctypes.c_float(1.0 - a32).value                 # 1 - alpha, computed on the host in fp32
+    N = 1
+    for name, t, dt, tail in (("out_tokens", out_tokens, torch.int64, ()), ("chosen_trace", chosen_trace, torch.int32, ()),
+                              ("cand_penalty", cand_penalty, torch.float32, (k,))):
+        if t is not None:
+            if t.dim() != 2 + len(tail):
+                raise TypeError(f"{fn}: {name} is a contiguous {dt} [{B}, N{', k' if tail else ''}] tensor")
+            N = t.shape[1]
+    for name, t, dt, tail in (("out_tokens", out_tokens, torch.int64, ()), ("chosen_trace", chosen_trace, torch.int32, ()),
+                              ("cand_penalty", cand_penalty, torch.float32, (k,))):
+        _contrast_tensor(fn, name, t, dt, (B, N, *tail), optional=True)
+    if isinstance(col, bool) or not isinstance(col, int) or not 0 <= col < N:
+        raise ValueError(f"{fn}: col = {col!r} is outside the {N} output columns")
+    H.check(H.load().kx_contrast_select(u.data_ptr(), prob.data_ptr(), history.data_ptr(), B, k, D, cap, hist_rows.data_ptr(), p_stride,
+                                        hist_len.data_ptr(), a32, oma, step_tokens.data_ptr(), finished.data_ptr(),
+                                        -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), next_token.data_ptr(),
+                                        chosen.data_ptr(), H.ptr(out_tokens), N, col, H.ptr(cand_penalty), H.ptr(chosen_trace),
+                                        scratch.data_ptr(), scratch.numel() * 4, error_word.data_ptr(), _stream()), "kx_contrast_select")
+
+
+def kv_cache_commit(ktail, vtail, kcache, vcache, chosen, positions, error_word, *, finished=None, layout="head_major"):
+    """kx_kv_cache_commit: cache[l, b, h, P_b] = tail[l, b * k + chosen[b], h, 0] for the k and v caches ([L, B, heads, Tmax, 64]) and
+    tails ([L, B * k, heads, Ttail, 64]; fp32 or bf16, contiguous), P_b = positions[b * k]; then positions[b * k : b * k + k] = P_b + 1.
+    ``chosen`` int32 [B], ``positions`` int32 [B * k]; rows with ``finished`` [B] uint8 set are skipped.  A chosen index outside
+    [0, k) or a P_b outside [0, Tmax) writes nothing and sets KX_RAGGED_ERR_COMMIT in ``error_word`` (int32 [1], sticky).
+    ``layout`` "row_major": the tensors are shaped [L, B, Tmax, heads, 64] / [L, B * k, Ttail, heads, 64], what the library copies
+    under tuning key 9 = 1; the argument only names the shape that is checked, the caller sets the key."""
+    fn = "kv_cache_commit"
+    _need_cuda(ktail, vtail, kcache, vcache, chosen, positions, error_word, finished)
+    if layout not in ("head_major", "row_major"):
+        raise ValueError(f"{fn}: layout is 'head_major' or 'row_major'")
+    if kcache.dim() != 5 or ktail.dim() != 5:
+        raise ValueError(f"{fn}: caches and tails are five-dimensional")
+    if layout == "row_major":
+        (L, B, Tmax, nh, hd), (Lt, M, Ttail, nht, hdt) = kcache.shape, ktail.shape
+    else:
+        (L, B, nh, Tmax, hd), (Lt, M, nht, Ttail, hdt) = kcache.shape, ktail.shape
+    if hd != 64 or hdt != 64 or Lt != L or nht != nh or M % B or not 1 <= M // B <= 16 or tuple(vcache.shape) != tuple(kcache.shape) \
+            or tuple(vtail.shape) != tuple(ktail.shape):
+        raise ValueError(f"{fn}: caches are [L, B, heads, Tmax, 64] and tails [L, B * k, heads, Ttail, 64], k and v alike, k in 1..16")
+    k = M // B
+    if len({ktail.dtype, vtail.dtype, kcache.dtype, vcache.dtype}) != 1 or kcache.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{fn}: the four tensors share one dtype, fp32 or bf16")
+    if not all(c.is_contiguous() for c in (ktail, vtail, kcache, vcache)):
+        raise ValueError(f"{fn}: the caches and tails must be contiguous")
+    _contrast_tensor(fn, "chosen", chosen, torch.int32, (B,))
+    _contrast_tensor(fn, "positions", positions, torch.int32, (M,))
+    _contrast_tensor(fn, "finished", finished, torch.uint8, (B,), optional=True)
+    if error_word is None or error_word.dtype != torch.int32 or error_word.numel() != 1:
+        raise TypeError(f"{fn}: error_word must be an int32 [1] tensor on the device (the kernel's sticky word)")
+    H.check(H.load().kx_kv_cache_commit(ktail.data_ptr(), vtail.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), L, B, k, nh, Tmax,
+                                        Ttail, kcache.element_size(), chosen.data_ptr(), positions.data_ptr(), H.ptr(finished),
+                                        error_word.data_ptr(), _stream()), "kx_kv_cache_commit")
